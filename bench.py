@@ -15,8 +15,16 @@ block on-device.  Weak scaling: every rank owns `--segments` segments.
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the implicit-GEMM
 conv of the wide layers on the f32 matrix cores); `roofline_other_convs` the remaining conv launches;
 `roofline_fbank` is the fbank kernel, priced against HBM (its algorithmic bytes).  Kernel
-durations are measured live with HIP events on the launch stream (sd_profile_*).
-`cpu_baseline` times the CPU oracle (torch f32) on this host's cores on a bounded sample.
+durations are measured live with HIP events on the launch stream (sd_profile_*), inside the timed steps.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds everything measured
+beside the headline: the f16 / f32-split16x3 / f32ns steps, `cpu_baseline` (the CPU oracle, torch f32, on this
+host's cores on a bounded sample), `reference_batches`, `der`, and (N > 1) rank 0's recomputation of gathered rows.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (rank 0):
+`embeddings.npy` (the gathered [N, 192] embeddings) and `affinity.npy` (rows of this rank's affinity block),
+each a fixed seeded row sample when the whole array would not fit the budget; `<name>_rows.npy` (float64)
+holds the sampled row indices.  Inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -49,11 +57,39 @@ def parse():
                     help="f32: exact f32 MFMA (configs[1], the headline). f16: f16 operands / f32 accumulate (configs[4]). "
                          "f32s: f32-split16x3 (every frame-level contraction as three f16 MFMA products per value pair, f32-level accuracy). "
                          "f32ns: the wide layers (86 %% of the flops) on exact f32 MFMA, only the narrow convs and the attention logits split")
-    ap.add_argument("--no-split-extra", action="store_true", help="skip the extra f32-split16x3 measurement appended to the f32 line")
-    ap.add_argument("--no-f16-extra", action="store_true", help="skip the extra f16 measurement appended to the f32 line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: extra precisions, CPU baseline, reference batches, DER vs CPU, "
+                         "cross-rank recomputation (off by default: a plain run times only the headline step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embeddings and (a seeded row sample of) the affinity as float32 .npy files into DIR")
+    ap.add_argument("--no-split-extra", action="store_true", help="with --full: skip the extra f32-split16x3 measurement appended to the f32 line")
+    ap.add_argument("--no-f16-extra", action="store_true", help="with --full: skip the extra f16 measurement appended to the f32 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, reference batches and DER")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for each batch size of the CPU baseline sample")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = {"embeddings": 24_000_000, "affinity": 36_000_000}     # < 64 MB in all, row indices included
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> 2-D device tensor.  Each is written whole as `<name>.npy` (float32) when it fits its budget, else as a
+    fixed row sample (numpy default_rng(0), sorted) with the sampled row indices beside it as `<name>_rows.npy` (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        rows, cols = t.shape
+        keep = max(1, min(rows, DUMP_BUDGET_BYTES[name] // (4 * cols)))
+        stale = os.path.join(out_dir, f"{name}_rows.npy")
+        if keep == rows and os.path.exists(stale):      # (left by an earlier, sampled dump into the same folder)
+            os.remove(stale)
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def usable_cores() -> int:
@@ -341,7 +377,7 @@ def main():
                            "order_ok": bool((every[:, 2] == 1.0).all())})
             if not gather["order_ok"]:
                 raise SystemExit("all-gather order check failed: full[rank::world] != this rank's embeddings")
-            gather["full"] = full
+        gather["full"] = full
         conv = _native.profile_read(_native.SD_PROF_CONV_GEMM)
         wide = _native.profile_read(_native.SD_PROF_CONV_WIDE)
         fb = _native.profile_read(_native.SD_PROF_FBANK)
@@ -358,7 +394,9 @@ def main():
     affinity_ms = aff_ms[0]
     exchange = dict(gather)         # of the headline measurement (the extra precisions below overwrite `gather`)
     full_main = exchange.pop("full", None)
-    if world > 1 and rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": full_main, "affinity": aff})
+    if args.full and world > 1 and rank == 0:
         # parity of what arrived from the OTHER ranks: rank 0 regenerates the first 16 segments of every other shard from the
         # one stream, embeds them itself and compares with the rows the collective delivered (a different batch around a
         # segment regroups its statistics sums: equal to f32 rounding, < 1e-9 cosine, not bitwise; own rows: bitwise, above)
@@ -376,7 +414,7 @@ def main():
     del full_main
     extra_f16 = None
     emb16 = None
-    if args.precision == "f32" and not args.no_f16_extra:
+    if args.full and args.precision == "f32" and not args.no_f16_extra:
         emb32 = emb.clone()
         del engine
         torch.cuda.empty_cache()
@@ -403,7 +441,7 @@ def main():
         }
 
     extra_split = None
-    if args.precision == "f32" and not args.no_split_extra:
+    if args.full and args.precision == "f32" and not args.no_split_extra:
         if extra_f16 is None:
             emb32 = emb.clone()
             del engine
@@ -439,7 +477,7 @@ def main():
         }
 
     extra_ns = None
-    if args.precision == "f32" and not args.no_split_extra:
+    if args.full and args.precision == "f32" and not args.no_split_extra:
         del engs
         torch.cuda.empty_cache()
         engn = EmbeddingEngine(state_dict, dev, max_batch=args.micro_batch, precision="f32ns")
@@ -574,7 +612,7 @@ def main():
             out["f32_split16x3"] = extra_split
         if extra_ns is not None:
             out["f32_narrow_split16x3"] = extra_ns
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             e32 = emb if args.precision == "f32" else None
             out["cpu_baseline"] = cpu_baseline(state_dict, wav, args.cpu_seconds, e32 if (extra_f16 is None and extra_split is None) else emb32,
                                                emb16 if extra_f16 is not None else (emb if args.precision == "f16" else None))
