@@ -27,6 +27,8 @@
  *   sd_topk_mean_std_f32, sd_asnorm_combine_f32   the top-k cohort statistics and combination of
  *                                   asnorm_scores [REF diar_diag.py:196-208] (its cosine products run on sd_conv1d_cl_f32)
  *   sd_viterbi_f32        replaces  viterbi_hmm [REF diar_diag.py:231-247]
+ *   sd_*_lens_*           the same arithmetic under speechbrain's relative lengths (wav_lens of
+ *                                   EncoderClassifier.encode_batch): see "Relative lengths" below
  *
  * Conventions: every pointer named *_dev / documented "device" is a HIP device
  * pointer; all functions are asynchronous on `stream`, never allocate and never
@@ -51,7 +53,7 @@ typedef void* sd_stream_t; /* hipStream_t */
 #define SD_ERR_WORKSPACE (-3)
 #define SD_ERR_HIP (-4)
 
-#define SD_ABI_VERSION 10
+#define SD_ABI_VERSION 11
 
 int sd_abi_version(void);
 /* sizeof of the structs below as this library was compiled (which: 0 sd_conv_args, 1 sd_layer, 2 sd_se_res2_block,
@@ -120,6 +122,32 @@ int sd_fbank_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n,
 int sd_fbank_windows_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
                          int B, int n, int mean_norm, float* out_dev, int ld_out,
                          void* ws_dev, size_t ws_bytes, sd_stream_t stream);
+
+/* ------------------------------------------------------- relative lengths */
+
+/* Relative lengths: rel_len_dev, device f32 [B], is speechbrain's `wav_lens` -- the share of each zero-padded row that is
+ * signal, relative to the padded length n.  NULL means all ones.  For a row of T frames (T = 1 + n / 160 at 16 kHz) let
+ * p = f32(rel_len[b] * T), the f32 product torch forms.  Two frame counts follow (unpinned restatement of speechbrain 1.0):
+ *   n_norm = round_half_even(p) clamped to [0, T]      InputNormalization(norm_type="sentence", std_norm=False):
+ *                                                        actual_size = torch.round(lengths * T)
+ *   n_mask = #{t in [0, T) : float(t) < p}             length_to_mask(lengths * L, max_len=L)
+ *          = min(T, ceil(p))                             (0 for p <= 0)
+ * They can differ by one (p = 100.3: 100 and 101); that is speechbrain's behaviour.
+ *   fbank:   computed over the whole padded row as sd_fbank_f32 does (the top_db floor stays utterance-wide over all T
+ *            frames); then the per-bin mean over frames [0, n_norm) is subtracted from all T frames.
+ *   ECAPA:   the SE squeezes (masked sum / n_mask), the global-context mean and population std of the attentive pooling,
+ *            its softmax (logits at t >= n_mask are -inf) and the pooled mean / std use frames [0, n_mask) only.  Every conv,
+ *            BN, Res2Net add, the SE gate's application (all T frames), asp_bn and fc run on the padded rows unchanged.
+ *   A row with n_norm == 0 or n_mask == 0 gets NaN features / a NaN embedding (speechbrain's empty mean and all -inf
+ *   softmax); other rows are unaffected.
+ * With rel_len_dev == NULL every _lens_ entry returns bitwise what its twin without the suffix returns.  Like the rest of the
+ * ABI they never synchronise and never allocate. */
+
+/* n_norm_dev / n_mask_dev: device int32 [B] (either may be NULL): the two counts of every row, as the kernels compute them */
+int sd_wav_lens_frames(const float* rel_len_dev, int B, int T, int* n_norm_dev, int* n_mask_dev, sd_stream_t stream);
+/* sd_fbank_f32 with mean_norm = 1 and the mean over each row's first n_norm frames (same plan, workspace and domain) */
+int sd_fbank_lens_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n, const float* rel_len_dev,
+                      float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
 
 /* --------------------------------------------------------- layer operators */
 
@@ -270,6 +298,14 @@ int sd_asp_pool_dt(const void* logit, int ldl, const void* h, int dtype, int ldh
 int sd_asp_attend_pool_supported(int dtype, int T, int C, int att);
 int sd_asp_attend_pool_dt(const void* a1, const void* wc, const void* h, int dtype, int ldh,
                           int B, int T, int C, int att, float eps, float* out, sd_stream_t stream);
+/* The three pooling operators under relative lengths (rel_len_dev: device f32 [B], NULL = all ones): every statistic,
+ * softmax and weighted sum over each row's first n_mask frames (see "Relative lengths" above); T stays the row stride */
+int sd_seg_mean_std_lens_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, const float* rel_len_dev, int C,
+                            int want_std, float eps, float* out, sd_stream_t stream);
+int sd_asp_pool_lens_dt(const void* logit, int ldl, const void* h, int dtype, int ldh,
+                        int B, int T, const float* rel_len_dev, int C, float eps, float* out, sd_stream_t stream);
+int sd_asp_attend_pool_lens_dt(const void* a1, const void* wc, const void* h, int dtype, int ldh,
+                               int B, int T, const float* rel_len_dev, int C, int att, float eps, float* out, sd_stream_t stream);
 
 /* ------------------------------------------------------------ ECAPA-TDNN */
 
@@ -342,6 +378,13 @@ int sd_ecapa_forward_f32(const sd_ecapa_weights* w, const float* feats, int B, i
  * activations in HBM (BASELINE.json configs[4]); feats and emb stay f32 */
 int sd_ecapa_forward_f16(const sd_ecapa_weights* w, const float* feats, int B, int T,
                          float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
+/* Both forwards under relative lengths (rel_len_dev: device f32 [B], NULL = all ones; "Relative lengths" above): feats
+ * from sd_fbank_lens_f32, the SE squeezes and the attentive pooling over each row's first n_mask frames.  Same
+ * workspace (sd_ecapa_workspace_bytes(w, B, T)), every precision of the weights (f32, f32-split16x3, f16). */
+int sd_ecapa_forward_lens_f32(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev,
+                              float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
+int sd_ecapa_forward_lens_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev,
+                              float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
 
 /* ------------------------------------------------------ cosine / affinity */
 

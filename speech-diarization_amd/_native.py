@@ -27,7 +27,7 @@ SD_TUNE_TILE_ROWS = 6
 SD_TUNE_T256_LOCKSTEP_TILES = 7
 SD_MAX_RES2 = 15
 SD_MAX_BLOCKS = 8
-SD_ABI_VERSION = 10
+SD_ABI_VERSION = 11
 SD_PROF_CONV_GEMM, SD_PROF_FBANK, SD_PROF_CONV_WIDE, SD_PROF_SEG_SPLITK = 0, 1, 2, 3
 
 
@@ -150,6 +150,14 @@ PROTOTYPES = {
     "sd_asnorm_combine_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sd_viterbi_workspace_bytes": (_Z, [_I, _I]),
     "sd_viterbi_f32": (_I, [_P, _I, _I, _I, _F, _F, _P, _Z, _P, _P]),
+    # relative lengths (speechbrain wav_lens)
+    "sd_wav_lens_frames": (_I, [_P, _I, _I, _P, _P, _P]),
+    "sd_fbank_lens_f32": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _Z, _P]),
+    "sd_seg_mean_std_lens_dt": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _F, _P, _P]),
+    "sd_asp_pool_lens_dt": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _F, _P, _P]),
+    "sd_asp_attend_pool_lens_dt": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _F, _P, _P]),
+    "sd_ecapa_forward_lens_f32": (_I, [C.POINTER(sd_ecapa_weights), _P, _I, _I, _P, _P, _P, _Z, _P]),
+    "sd_ecapa_forward_lens_f16": (_I, [C.POINTER(sd_ecapa_weights), _P, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -65,18 +65,20 @@ __device__ __forceinline__ float red16(float v) {
 template <int TPW>   // 16-frame tiles per wave: T <= 64 * TPW
 __global__ __launch_bounds__(256, 3) void asp_attend_pool_f16_kernel(const _Float16* __restrict__ a1, const _Float16* __restrict__ wc,
                                                                      const _Float16* __restrict__ h, int ldh, int Tn, int C,
-                                                                     float eps, float* __restrict__ out) {
+                                                                     float eps, float* __restrict__ out, const float* __restrict__ rel_len) {
   extern __shared__ __attribute__((aligned(16))) _Float16 sw[];   // [CPB / 2][WLD] weights, then the partial statistics
   const int cblocks = C / CPB;
   const int b = blockIdx.x / cblocks, cblk = blockIdx.x % cblocks;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 15, quad = lane >> 4;      // MFMA column (frame) / k group and output row group
+  // frames that take part in the softmax: all T, or the segment's mask frames (relative lengths); the rest are dead like frames past T
+  const int nv = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;
 
   // this wave's frames: 16-frame tiles wid, wid + 4, wid + 8, ... (slot j = tile 4 j + wid), so that the tiles past T
   // fall into the LAST slot of some waves, which those waves skip (T = 201: 13 tiles; wave 0 runs 4 slots, the others 3).
   // B fragments for the whole kernel: lane (col, quad) holds a1[t0 + 64 j + col][32 ks + 8 quad .. +7]
   const int t0 = wid * 16;
-  const bool full = ((TPW - 1) * 4 + __builtin_amdgcn_readfirstlane(wid)) * 16 < Tn;    // wave-uniform: the last slot has live frames
+  const bool full = ((TPW - 1) * 4 + __builtin_amdgcn_readfirstlane(wid)) * 16 < nv;    // wave-uniform: the last slot has live frames
   h8 af[TPW][AK / 32];
   {
     const h8 z = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256, 3) void asp_attend_pool_f16_kernel(const _Floa
   const _Float16* hl = h + ((size_t)b * Tn + t0 + col) * ldh + (size_t)cblk * CPB + 8 * quad;
   bool live[TPW];
 #pragma unroll
-  for (int j = 0; j < TPW; ++j) live[j] = t0 + j * 64 + col < Tn;
+  for (int j = 0; j < TPW; ++j) live[j] = t0 + j * 64 + col < nv;
   const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
   auto load_h = [&](int p, h8* dst) {
 #pragma unroll
@@ -123,7 +125,8 @@ __global__ __launch_bounds__(256, 3) void asp_attend_pool_f16_kernel(const _Floa
   float* const st = reinterpret_cast<float*>(sw + (CPB / 2) * WLD);     // [wave][channel][4]
   // frames past T are masked inside the MFMA: the accumulators start at 0 (live) or -inf (dead; a1 is zero there, so
   // the products are finite), and exp2(-inf) = 0 drops them from every sum.  Only the last slot can hold such frames
-  // (T > 64 (TPW - 1)).
+  // (T > 64 (TPW - 1)).  A mask (rel_len) can end the live frames in any slot: the other slots' dead frames are set to -inf after
+  // their MFMAs.
   f32x4 minit;
   {
     const float v = live[TPW - 1] ? 0.f : -INFINITY;
@@ -152,6 +155,11 @@ __global__ __launch_bounds__(256, 3) void asp_attend_pool_f16_kernel(const _Floa
         const h8 wf = *reinterpret_cast<const h8*>(wr + ks * 32);
         acc[TPW - 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, af[TPW - 1][ks], acc[TPW - 1], 0, 0, 0);
       }
+    }
+    if (rel_len) {
+#pragma unroll
+      for (int j = 0; j < (TPW > 1 ? TPW - 1 : 1); ++j)
+        if (!live[j]) acc[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     }
     float m[4];
 #pragma unroll
@@ -238,13 +246,13 @@ __global__ __launch_bounds__(256, 3) void asp_attend_pool_f16_kernel(const _Floa
 }
 
 template <int TPW>
-int launch_f16(const void* a1, const void* wc, const void* h, int ldh, int B, int T, int C, float eps, float* out, hipStream_t s) {
+int launch_f16(const void* a1, const void* wc, const void* h, int ldh, int B, int T, int C, float eps, float* out, hipStream_t s, const float* rel_len) {
   auto kern = asp_attend_pool_f16_kernel<TPW>;
   const size_t lds = (size_t)(CPB / 2) * WLD * sizeof(_Float16) + (size_t)4 * CPB * 4 * sizeof(float);   // 34 + 16 KB: three workgroups per CU
   static_assert(3 * ((size_t)(CPB / 2) * WLD * sizeof(_Float16) + (size_t)4 * CPB * 4 * sizeof(float)) <= 160 * 1024, "three workgroups per CU");
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)B * (C / CPB))), dim3(256), lds, s, static_cast<const _Float16*>(a1),
-                     static_cast<const _Float16*>(wc), static_cast<const _Float16*>(h), ldh, T, C, eps, out);
+                     static_cast<const _Float16*>(wc), static_cast<const _Float16*>(h), ldh, T, C, eps, out, rel_len);
   SD_CHECK_LAUNCH("asp_attend_pool_f16_kernel");
   return SD_OK;
 }
@@ -278,12 +286,14 @@ constexpr int SLD = AK + 8;   // LDS row stride of a split a1 plane in halfs (27
 template <int NT, bool SPLIT = false>   // 16-frame tiles: T <= 16 * NT
 __global__ __launch_bounds__(512, 2) void asp_attend_pool_f32_kernel(const float* __restrict__ a1, const float* __restrict__ wc,
                                                                      const float* __restrict__ h, int ldh, int Tn, int C, int cpb,
-                                                                     float eps, float* __restrict__ out, float wscale) {
+                                                                     float eps, float* __restrict__ out, float wscale,
+                                                                     const float* __restrict__ rel_len) {
   extern __shared__ __attribute__((aligned(16))) float sf[];   // [NT * 16][FLD]   (SPLIT: two planes of [NT * 16][SLD] halfs)
   const int cblocks = C / cpb;
   const int b = blockIdx.x / cblocks, cblk = blockIdx.x % cblocks;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 15, quad = lane >> 4;
+  const int nv = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;    // frames in the softmax (relative lengths: the segment's mask)
   _Float16* const s_hi = reinterpret_cast<_Float16*>(sf);
   _Float16* const s_lo = s_hi + NT * 16 * SLD;
   {
@@ -396,7 +406,7 @@ __global__ __launch_bounds__(512, 2) void asp_attend_pool_f32_kernel(const float
     if (g + 8 < ngroups) load_w(g + 8, wf);
     // softmax over the frames + weighted mean / variance (two passes), four channels per lane: packed f32 pairs
     // (channels r, r + 1), one FMA + v_exp_f32 per weight, single-instruction DPP reductions.  Frames past T are
-    // masked only in the tiles that can hold them (the dispatch guarantees T > 16 JMIN).
+    // masked only in the tiles that can hold them (the dispatch guarantees T > 16 JMIN); with a mask (rel_len) in every tile.
     constexpr int JMIN = NT == 4 ? 0 : NT == 8 ? 4 : NT == 13 ? 8 : 13;
     constexpr float LOG2E = 1.4426950408889634f;
     float m[4];
@@ -405,12 +415,12 @@ __global__ __launch_bounds__(512, 2) void asp_attend_pool_f32_kernel(const float
       float mx = -INFINITY;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        if (j >= JMIN) acc[j][r] = j * 16 + col < Tn ? acc[j][r] : -INFINITY;
+        if (j >= JMIN || rel_len) acc[j][r] = j * 16 + col < nv ? acc[j][r] : -INFINITY;
         mx = fmaxf(mx, acc[j][r]);
       }
       m[r] = mx;
     }
-    SD_DPP_RED4("v_max_f32_dpp", m[0], m[1], m[2], m[3]);      // (finite: frame 0 of every segment is live)
+    SD_DPP_RED4("v_max_f32_dpp", m[0], m[1], m[2], m[3]);      // (finite: frame 0 of every segment is live, unless a mask of 0 frames: NaN out)
     float d[4], n[4], v[4];
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
@@ -456,7 +466,8 @@ __global__ __launch_bounds__(512, 2) void asp_attend_pool_f32_kernel(const float
 }
 
 template <int NT, bool SPLIT = false>
-int launch_f32(const void* a1, const void* wc, const void* h, int ldh, int B, int T, int C, float eps, float* out, hipStream_t s, float wscale = 256.f) {
+int launch_f32(const void* a1, const void* wc, const void* h, int ldh, int B, int T, int C, float eps, float* out, hipStream_t s, float wscale,
+               const float* rel_len) {
   auto kern = asp_attend_pool_f32_kernel<NT, SPLIT>;
   const size_t lds = SPLIT ? (size_t)2 * NT * 16 * SLD * sizeof(_Float16) : (size_t)NT * 16 * FLD * sizeof(float);
   // channels per workgroup (one workgroup per CU: the a1 tile fills most of the LDS; a wave takes ~13 us per 16-channel group):
@@ -466,7 +477,7 @@ int launch_f32(const void* a1, const void* wc, const void* h, int ldh, int B, in
   while (cpb > 128 && C % (cpb / 2) == 0 && (long)B * (C / (cpb / 2)) <= 256) cpb /= 2;
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)B * (C / cpb))), dim3(512), lds, s, static_cast<const float*>(a1),
-                     static_cast<const float*>(wc), static_cast<const float*>(h), ldh, T, C, cpb, eps, out, wscale);
+                     static_cast<const float*>(wc), static_cast<const float*>(h), ldh, T, C, cpb, eps, out, wscale, rel_len);
   SD_CHECK_LAUNCH("asp_attend_pool_f32_kernel");
   return SD_OK;
 }
@@ -482,11 +493,17 @@ extern "C" int sd_asp_attend_pool_dt(const void* a1, const void* wc, const void*
   return sd_asp_attend_pool_scaled(a1, wc, h, dtype, ldh, B, T, C, att, eps, 256.f, out, stream);
 }
 
+// rel_len (device f32 [B], may be NULL = all ones): the softmax and the statistics over the first sd_mask_frames(rel_len[b], T) frames
+extern "C" int sd_asp_attend_pool_lens_dt(const void* a1, const void* wc, const void* h, int dtype, int ldh, int B, int T, const float* rel_len,
+                                          int C, int att, float eps, float* out, sd_stream_t stream) {
+  return sd_asp_attend_pool_scaled(a1, wc, h, dtype, ldh, B, T, C, att, eps, 256.f, out, stream, rel_len);
+}
+
 // w_scale (SD_DT_SPLIT16 only): the power of two the f32 attention-conv weights are multiplied with before they are split into f16
 // halves; the forward passes the data-dependent 2^s of the layer (max |w| 2^s in [512, 1024), as every other split weight); the
 // public entry above passes 2^8, the right magnitude for trained ECAPA weights (|w| ~ 0.1), and values beyond the f16 range clamp.
 int sd_asp_attend_pool_scaled(const void* a1, const void* wc, const void* h, int dtype, int ldh, int B, int T, int C,
-                              int att, float eps, float w_scale, float* out, sd_stream_t stream) {
+                              int att, float eps, float w_scale, float* out, sd_stream_t stream, const float* rel_len) {
   SD_CHECK_ARG(a1 && wc && h && out, "sd_asp_attend_pool_dt: null pointer");
   SD_CHECK_ARG(w_scale > 0.f, "sd_asp_attend_pool_dt: w_scale=%g", (double)w_scale);
   SD_CHECK_ARG(B >= 0 && (long)B * (C > 0 ? C : 1) < (1L << 31), "sd_asp_attend_pool_dt: B=%d", B);
@@ -498,19 +515,19 @@ int sd_asp_attend_pool_scaled(const void* a1, const void* wc, const void* h, int
   if (B == 0) return SD_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == SD_DT_SPLIT16) {       // f32 tensors, the logits product as three f16 MFMA products per value pair (f32-split16x3 mode)
-    if (T <= 64) return launch_f32<4, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale);
-    if (T <= 128) return launch_f32<8, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale);
-    if (T <= 208) return launch_f32<13, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale);
-    return launch_f32<16, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale);
+    if (T <= 64) return launch_f32<4, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale, rel_len);
+    if (T <= 128) return launch_f32<8, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale, rel_len);
+    if (T <= 208) return launch_f32<13, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale, rel_len);
+    return launch_f32<16, true>(a1, wc, h, ldh, B, T, C, eps, out, s, w_scale, rel_len);
   }
   if (dtype == SD_DT_F32) {
-    if (T <= 64) return launch_f32<4>(a1, wc, h, ldh, B, T, C, eps, out, s);
-    if (T <= 128) return launch_f32<8>(a1, wc, h, ldh, B, T, C, eps, out, s);
-    if (T <= 208) return launch_f32<13>(a1, wc, h, ldh, B, T, C, eps, out, s);
-    return launch_f32<16>(a1, wc, h, ldh, B, T, C, eps, out, s);
+    if (T <= 64) return launch_f32<4>(a1, wc, h, ldh, B, T, C, eps, out, s, 256.f, rel_len);
+    if (T <= 128) return launch_f32<8>(a1, wc, h, ldh, B, T, C, eps, out, s, 256.f, rel_len);
+    if (T <= 208) return launch_f32<13>(a1, wc, h, ldh, B, T, C, eps, out, s, 256.f, rel_len);
+    return launch_f32<16>(a1, wc, h, ldh, B, T, C, eps, out, s, 256.f, rel_len);
   }
-  if (T <= 64) return launch_f16<1>(a1, wc, h, ldh, B, T, C, eps, out, s);
-  if (T <= 128) return launch_f16<2>(a1, wc, h, ldh, B, T, C, eps, out, s);
-  if (T <= 192) return launch_f16<3>(a1, wc, h, ldh, B, T, C, eps, out, s);     // (the kernel relies on T > 64 (TPW - 1))
-  return launch_f16<4>(a1, wc, h, ldh, B, T, C, eps, out, s);
+  if (T <= 64) return launch_f16<1>(a1, wc, h, ldh, B, T, C, eps, out, s, rel_len);
+  if (T <= 128) return launch_f16<2>(a1, wc, h, ldh, B, T, C, eps, out, s, rel_len);
+  if (T <= 192) return launch_f16<3>(a1, wc, h, ldh, B, T, C, eps, out, s, rel_len);     // (the kernel relies on T > 64 (TPW - 1))
+  return launch_f16<4>(a1, wc, h, ldh, B, T, C, eps, out, s, rel_len);
 }

@@ -23,7 +23,8 @@ int sd_affinity_sym_f32(const float* xn, int ldx, int N, int groups, float* out,
 int sd_affinity_sym_split16(const void* xs, int ldx, int N, int groups, float* out, long ldo, float alpha, sd_stream_t stream);   // sd_affinity.hip
 int sd_cast_f32_f16(const float* x, long n, void* y, sd_stream_t stream);           // sd_pool.hip
 int sd_asp_attend_pool_scaled(const void* a1, const void* wc, const void* h, int dtype, int ldh, int B, int T, int C, int att, float eps,
-                              float w_scale, float* out, sd_stream_t stream);         // sd_asp_fused.hip: sd_asp_attend_pool_dt with the split weights' 2^s
+                              float w_scale, float* out, sd_stream_t stream,
+                              const float* rel_len = nullptr);   // sd_asp_fused.hip: sd_asp_attend_pool_lens_dt with the split weights' 2^s
 int sd_se_scale_residual_split(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy, int y_col0,
                                int B, int T, int C, int dtype, void* ys, int lds, int s_col0, sd_stream_t stream,
                                const void* res_split, int ld_rs, int rs_col0, int write_y);   // sd_pool.hip
@@ -88,6 +89,21 @@ __device__ __forceinline__ float sd_max_keep_nan(float x, float lo) {
 #else
   return x < lo ? lo : x;
 #endif
+}
+
+// Relative lengths (speechbrain's wav_lens: the share of the padded row that is signal) -> frames of a row of T frames.  Both counts
+// start from p = f32(rel * T), the f32 product torch forms (unpinned restatement of speechbrain 1.0):
+//   sd_norm_frames  InputNormalization(norm_type="sentence"): actual_size = torch.round(lengths * T) -> round half to even, clamped to [0, T]
+//   sd_mask_frames  length_to_mask(lengths * L, max_len=L): #{t in [0, T) : float(t) < p} = min(T, ceil(p)) (SE squeeze, pooling)
+// They differ by one when frac(p) is in (0, 0.5) (p = 100.3: 100 and 101): speechbrain's behaviour, kept.  A NaN or p <= 0 gives 0.
+// This is the ONE statement of the rule on the device; every masked kernel computes its row's counts from rel_len[b] with it.
+__host__ __device__ __forceinline__ int sd_norm_frames(float rel, int T) {
+  const float r = rintf(rel * (float)T);
+  return r >= (float)T ? T : (r > 0.f ? (int)r : 0);
+}
+__host__ __device__ __forceinline__ int sd_mask_frames(float rel, int T) {
+  const float c = ceilf(rel * (float)T);
+  return c >= (float)T ? T : (c > 0.f ? (int)c : 0);
 }
 
 __device__ __forceinline__ float sd_wave_max(float v) {

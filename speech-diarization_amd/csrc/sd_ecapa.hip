@@ -230,8 +230,12 @@ int run_wide(const sd_layer& l, sd_conv_args a, bool split, void* xs, long narro
     if (e_ != SD_OK) return e_; \
   } while (0)
 
+// rel_len (device f32 [B], NULL = all ones): speechbrain's relative lengths.  Every conv, BN, Res2Net add and the SE gate's application
+// run on the padded rows as without them; the SE squeezes, the global mean / std of the attentive pooling and its softmax and statistics
+// count each row's first sd_mask_frames(rel_len[b], T) frames only.  Those statistics then come from the row-masked reduction kernels
+// (no column statistics from the conv epilogues), and both pooling routes take the mask.
 int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb, void* ws_dev, size_t ws_bytes,
-            sd_stream_t stream, int dt) {
+            sd_stream_t stream, int dt, const float* rel_len = nullptr) {
   SD_TRY(check_weights(w, dt));
   SD_CHECK_ARG(B >= 0 && T > 0, "sd_ecapa_forward: B=%d T=%d", B, T);
   if (B == 0) return SD_OK;
@@ -261,6 +265,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     const char* e = sd_experiment_env("SD_COLSTAT");
     return !(e && e[0] == '0');
   }();
+  const bool colstat_on = colstat_ok && rel_len == nullptr;      // the epilogue's column statistics sum over all T rows of a segment
   bool x0_split = false;                                 // the stem's output exists as SD_DT_SPLIT16 only (b.x0s)
   // block 0: TDNNBlock(n_mels -> C, k=5) on the f32 features.  f16: the features are rounded to f16 once (the
   // operand precision of that path anyway; t2 is free here), which lets the stem run on the LDS-DMA kernel of the
@@ -330,13 +335,13 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     // geometry allows (the Res2Net scratch s0 is dead and holds them), else from a pass over t2
     {
       sd_conv_args a = conv_of(blk.tdnn2, b.r, dt, C, 0, b.t2, dt, C, 0, M, T, SD_ACT_RELU);
-      const bool stat = colstat_ok && T >= (wsplit ? 128 : 64) && C % 256 == 0 && !(wsplit && blk.tdnn2.w_split && wide_goes_narrow(blk.tdnn2, M, nt)) &&
+      const bool stat = colstat_on && T >= (wsplit ? 128 : 64) && C % 256 == 0 && !(wsplit && blk.tdnn2.w_split && wide_goes_narrow(blk.tdnn2, M, nt)) &&
                         (size_t)((M + stat_unit - 1) / stat_unit) * 6 * C * sizeof(float) <= (size_t)M * chunk * es;
       if (stat) a.colstat = static_cast<float*>(b.s0);
       int rows = 128;
       SD_TRY(run_wide(blk.tdnn2, a, wsplit, b.xs, nt, stream, r_split ? b.rs : nullptr, C, stat ? &rows : nullptr));
       if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.t2, dt, C, 0, B, T, C, 0, 0.f, b.semean, rows, stream));
-      else SD_TRY(sd_seg_mean_std_dt(b.t2, dt, C, 0, B, T, C, 0, 0.f, b.semean, stream));
+      else SD_TRY(sd_seg_mean_std_lens_dt(b.t2, dt, C, 0, B, T, rel_len, C, 0, 0.f, b.semean, stream));
     }
     // squeeze-excitation gate (per-segment, f32)
     {
@@ -367,13 +372,13 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
   // epilogue (column sums in r, dead since the last block's tdnn2)
   {
     sd_conv_args a = conv_of(w->mfa, b.xcat, dt, Cm, 0, b.h, dt, Cm, 0, M, T, SD_ACT_RELU);
-    const bool stat = colstat_ok && T >= (wsplit ? 128 : 64) && Cm % 256 == 0 && !(wsplit && w->mfa.w_split && wide_goes_narrow(w->mfa, M, nt)) &&
+    const bool stat = colstat_on && T >= (wsplit ? 128 : 64) && Cm % 256 == 0 && !(wsplit && w->mfa.w_split && wide_goes_narrow(w->mfa, M, nt)) &&
                       (size_t)((M + stat_unit - 1) / stat_unit) * 6 * Cm * sizeof(float) <= (size_t)M * C * es;
     if (stat) a.colstat = static_cast<float*>(b.r);
     int rows = 128;
     SD_TRY(run_wide(w->mfa, a, wsplit, b.xs, nt, stream, b.xcs, Cm, stat ? &rows : nullptr));
     if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.h, dt, Cm, 0, B, T, Cm, 1, w->asp_eps, b.stats, rows, stream));
-    else SD_TRY(sd_seg_mean_std_dt(b.h, dt, Cm, 0, B, T, Cm, 1, w->asp_eps, b.stats, stream));
+    else SD_TRY(sd_seg_mean_std_lens_dt(b.h, dt, Cm, 0, B, T, rel_len, Cm, 1, w->asp_eps, b.stats, stream));
   }
   // attentive statistics pooling with global context
   {
@@ -395,11 +400,12 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       // (split16 mode: the same f32 tensors, the logits product on the f16 matrix cores with split operands)
       // (the weights' 2^s: asp_conv.split_scale_inv = 2^-s from the host, data dependent like every other split weight's)
       const float ws = w->asp_conv.split_scale_inv > 0.f ? 1.f / w->asp_conv.split_scale_inv : 256.f;
-      SD_TRY(sd_asp_attend_pool_scaled(b.a1, w->asp_conv.w, b.h, split ? SD_DT_SPLIT16 : dt, Cm, B, T, Cm, w->att_channels, w->asp_eps, ws, b.pooled, stream));
+      SD_TRY(sd_asp_attend_pool_scaled(b.a1, w->asp_conv.w, b.h, split ? SD_DT_SPLIT16 : dt, Cm, B, T, Cm, w->att_channels, w->asp_eps, ws, b.pooled, stream,
+                                            rel_len));
     } else {
       sd_conv_args c = conv_of(w->asp_conv, b.a1, dt, w->att_channels, 0, b.e, dt, Cm, 0, M, T, SD_ACT_NONE);
       SD_TRY(run_conv(c, stream));
-      SD_TRY(sd_asp_pool_dt(b.e, Cm, b.h, dt, Cm, B, T, Cm, w->asp_eps, b.pooled, stream));
+      SD_TRY(sd_asp_pool_lens_dt(b.e, Cm, b.h, dt, Cm, B, T, rel_len, Cm, w->asp_eps, b.pooled, stream));
     }
   }
   // asp_bn (folded into the weights by the host) + fc
@@ -425,4 +431,14 @@ extern "C" int sd_ecapa_forward_f32(const sd_ecapa_weights* w, const float* feat
 extern "C" int sd_ecapa_forward_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb,
                                     void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
   return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F16);
+}
+
+extern "C" int sd_ecapa_forward_lens_f32(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev, float* emb,
+                                         void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
+  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F32, rel_len_dev);
+}
+
+extern "C" int sd_ecapa_forward_lens_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev, float* emb,
+                                         void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
+  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F16, rel_len_dev);
 }

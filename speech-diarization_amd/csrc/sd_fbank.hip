@@ -414,8 +414,9 @@ __global__ void fill_i32_kernel(int* p, int n, int v) {
 
 // top_db floor (relative to the utterance max) and per-bin mean removal over T.
 // One workgroup per utterance; thread (r, c) walks rows r, r+R, ... of column c.
+// rel_len (NULL: all T): the mean over the first sd_norm_frames(rel_len[b], T) frames, subtracted from all T.
 __global__ void fbank_finalize_kernel(float* out, int ld_out, int T, int n_mels, const int* maxbuf,
-                                      int use_floor, float top_db, int mean_norm, int R) {
+                                      int use_floor, float top_db, int mean_norm, int R, const float* rel_len) {
   extern __shared__ float part[];  // [R][n_mels]
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -431,15 +432,16 @@ __global__ void fbank_finalize_kernel(float* out, int ld_out, int T, int n_mels,
   }
   if (!use_floor && !mean_norm) return;               // (raw features: the pass only exists to mark NaN utterances)
   const float thr = use_floor ? key_f32(key) - top_db : -INFINITY;
+  const int tn = rel_len ? sd_norm_frames(rel_len[b], T) : T;
   float s = 0.f;
   if (active && mean_norm)
-    for (int t = r; t < T; t += R) s += fmaxf(base[(size_t)t * ld_out + c], thr);
+    for (int t = r; t < tn; t += R) s += fmaxf(base[(size_t)t * ld_out + c], thr);
   if (active) part[r * n_mels + c] = s;
   __syncthreads();
   float mean = 0.f;
   if (mean_norm) {
     for (int k = 0; k < R; ++k) mean += part[k * n_mels + c];
-    mean /= (float)T;
+    mean /= (float)tn;
   }
   if (active)
     for (int t = r; t < T; t += R) {
@@ -580,12 +582,18 @@ extern "C" size_t sd_fbank_workspace_bytes(const sd_fbank_plan* plan, int B, int
 }
 
 static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_);
+                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_,
+                        const float* rel_len = nullptr);
 
 extern "C" int sd_fbank_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n,
                             int mean_norm, float* out_dev, int ld_out,
                             void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
   return fbank_launch(plan, wav_dev, (long long)B * n, nullptr, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream_);
+}
+
+extern "C" int sd_fbank_lens_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n, const float* rel_len_dev,
+                                 float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
+  return fbank_launch(plan, wav_dev, (long long)B * n, nullptr, B, n, 1, out_dev, ld_out, ws_dev, ws_bytes, stream_, rel_len_dev);
 }
 
 extern "C" int sd_fbank_windows_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
@@ -597,7 +605,8 @@ extern "C" int sd_fbank_windows_f32(const sd_fbank_plan* plan, const float* wav_
 }
 
 static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
+                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_,
+                        const float* rel_len) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   SD_CHECK_ARG(plan != nullptr, "sd_fbank_f32: null plan");
   SD_CHECK_ARG(B >= 0 && n >= 0, "sd_fbank_f32: B=%d n=%d", B, n);
@@ -609,12 +618,13 @@ static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long lo
     SD_CHECK_ARG(n > plan->n_fft / 2, "sd_fbank_f32: reflect padding of %d needs more than %d samples (got %d)", plan->n_fft / 2, plan->n_fft / 2, n);
   else
     SD_CHECK_ARG(n >= 1, "sd_fbank_f32: empty waveform");
-  if (plan->generic) return sd_fbank_generic_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream);
+  if (plan->generic) return sd_fbank_generic_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream,
+                                                   rel_len);
   SD_CHECK_ARG(ws_dev != nullptr && ws_bytes >= sd_fbank_workspace_bytes(plan, B, n),
                "sd_fbank_f32: workspace too small (%zu < %zu)", ws_bytes, sd_fbank_workspace_bytes(plan, B, n));
   // utterances whose padded signal fits the CU's LDS: ONE launch, one workgroup per utterance (sd_fbank_utt16.hip)
   if (n_total >= 4 && sd_fbank_utt16_supported(plan, n))    // (16-byte loads: four samples behind `wav`)
-    return sd_fbank_utt16_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, stream);
+    return sd_fbank_utt16_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, stream, rel_len);
   const int T = 1 + n / HOP;
   Fbank2Args a;
   a.wav = wav_dev; a.B = B; a.n = n; a.T = T;
@@ -644,7 +654,7 @@ static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long lo
     int R = 320 / plan->n_mels; if (R < 1) R = 1; if (R > T) R = T;
     int threads = ((R * plan->n_mels + 63) / 64) * 64;
     hipLaunchKernelGGL(fbank_finalize_kernel, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float),
-                       stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R);
+                       stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R, rel_len);
     SD_CHECK_LAUNCH("fbank_finalize_kernel");
   }
   return SD_OK;

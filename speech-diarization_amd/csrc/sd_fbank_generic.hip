@@ -111,6 +111,7 @@ struct FinArgs {
   const float* mel; int ldm; int R; int row0;       // mel rows of utterance b: (b * R + row0 + t), t < T
   float* out; int ld_out; int B0; int T; int n_mels;
   int log_mode; float log_eps; float top_db; int use_floor; int mean_norm;
+  const float* rel_len;    // mean_norm: the mean over the first sd_norm_frames(rel_len[B0 + b], T) frames (NULL: all T)
 };
 
 constexpr int FIN_THREADS = 256;
@@ -152,15 +153,16 @@ __global__ __launch_bounds__(FIN_THREADS) void fbg_finalize_kernel(FinArgs p) {
   const int rg = tid / p.n_mels, col = tid - rg * p.n_mels;
   auto floored = [&](float x) -> float { return thr != thr ? thr : (x < thr ? thr : x); };      // keeps a NaN x
   if (p.mean_norm) {
+    const int tn = p.rel_len ? sd_norm_frames(p.rel_len[p.B0 + b], p.T) : p.T;
     float s = 0.f;
     if (rg < RG)
-      for (int t = rg; t < p.T; t += RG) s += floored(dst[(size_t)t * p.ld_out + col]);
+      for (int t = rg; t < tn; t += RG) s += floored(dst[(size_t)t * p.ld_out + col]);
     colsum[tid] = s;
     __syncthreads();
     if (tid < p.n_mels) {
       float sum = 0.f;
       for (int k = 0; k < RG; ++k) sum += colsum[k * p.n_mels + tid];
-      mean_s[tid] = sum / (float)p.T;
+      mean_s[tid] = sum / (float)tn;
     }
     __syncthreads();
   }
@@ -242,7 +244,8 @@ size_t sd_fbank_generic_workspace_bytes(const sd_fbank_plan* plan, int B, int n)
 }
 
 int sd_fbank_generic_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                            int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, hipStream_t stream) {
+                            int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, hipStream_t stream,
+                            const float* rel_len) {
   const int T = sd_fbank_generic_num_frames(plan, n);
   SD_CHECK_ARG(T >= 1, "sd_fbank_f32: %d samples give no frame at n_fft=%d", n, plan->n_fft);
   const int nfp = plan->g_nfp, nmp = plan->g_nmp;
@@ -271,7 +274,7 @@ int sd_fbank_generic_launch(const sd_fbank_plan* plan, const float* wav_dev, lon
     a.M = (int)M; a.T = 1; a.cin = nfp; a.cin_pad = nfp; a.cout = plan->n_mels; a.taps = 1; a.dil = 1;
     a.act = SD_ACT_NONE; a.act2 = SD_ACT_NONE;
     if (int e = sd_conv1d_cl_f32(&a, stream)) return e;
-    FinArgs fa{mel, nmp, T, 0, out_dev, ld_out, b0, T, plan->n_mels, plan->log_mode, plan->log_eps, plan->top_db, use_floor, mean_norm};
+    FinArgs fa{mel, nmp, T, 0, out_dev, ld_out, b0, T, plan->n_mels, plan->log_mode, plan->log_eps, plan->top_db, use_floor, mean_norm, rel_len};
     hipLaunchKernelGGL(fbg_finalize_kernel, dim3((unsigned)nb), dim3(FIN_THREADS), 0, stream, fa);
     SD_CHECK_LAUNCH("fbg_finalize_kernel");
   }

@@ -21,8 +21,10 @@ int sd_fbank_generic_create_tables(sd_fbank_plan* plan, const float* window, con
 void sd_fbank_generic_destroy_tables(sd_fbank_plan* plan);
 int sd_fbank_generic_num_frames(const sd_fbank_plan* plan, int n);
 size_t sd_fbank_generic_workspace_bytes(const sd_fbank_plan* plan, int B, int n);
+// rel_len (device f32 [B] or NULL, with mean_norm): the per-bin mean over each row's first sd_norm_frames(rel_len[b], T) frames
 int sd_fbank_generic_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                            int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, hipStream_t stream);
+                            int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, hipStream_t stream,
+                            const float* rel_len);
 
 // device tables of the factored kernel from the window (n_fft values) and the mel filterbank [n_fft / 2 + 1][n_mels]; utterances of up to
 // 32 100 samples = 201 frames (the padded signal must fit the CU's LDS beside the table ring)
@@ -30,4 +32,4 @@ int sd_fbank_utt16_create_tables(sd_fbank_plan* plan, const float* window, const
 void sd_fbank_utt16_destroy_tables(sd_fbank_plan* plan);
 bool sd_fbank_utt16_supported(const sd_fbank_plan* plan, int n);
 int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                          int mean_norm, float* out_dev, int ld_out, hipStream_t stream);
+                          int mean_norm, float* out_dev, int ld_out, hipStream_t stream, const float* rel_len);

@@ -84,6 +84,7 @@ struct U16Args {
   const long long* starts; long long n_total;
   const char* tables;
   int n_mels; int pad_mode; int log_mode; float log_eps; float top_db; int use_floor; int mean_norm;
+  const float* rel_len;      // mean_norm: the mean over the first sd_norm_frames(rel_len[b], T) frames (NULL: all T)
   float* out; int ld_out;
   unsigned inv_mels;
 };
@@ -567,18 +568,19 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
   float* const part = reinterpret_cast<float*>(a2s);          // (the stage-2 matrix is dead) [24][96] partial column sums, then [96] means behind them
   float* const mean = part + 24 * 96;
   if (p.mean_norm) {
+    const int tn = p.rel_len ? sd_norm_frames(p.rel_len[b], p.T) : p.T;      // frames of the mean; every frame is shifted by it
     const int per_row = (p.n_mels + 3) >> 2;
     int RG = U16_THREADS / per_row; RG = RG > 24 ? 24 : RG;
     const int rg = tid / per_row, c0 = (tid - rg * per_row) * 4;
     if (rg < RG) {
       float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
       int t = rg;
-      for (; t + RG < p.T; t += 2 * RG) {
+      for (; t + RG < tn; t += 2 * RG) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
           if (c0 + c < p.n_mels) { s0[c] += fmaxf(lm[t * MELP + c0 + c], thr); s1[c] += fmaxf(lm[(t + RG) * MELP + c0 + c], thr); }
       }
-      if (t < p.T) {
+      if (t < tn) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
           if (c0 + c < p.n_mels) s0[c] += fmaxf(lm[t * MELP + c0 + c], thr);
@@ -591,7 +593,7 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
     if (tid < p.n_mels) {
       float sum = 0.f;
       for (int k = 0; k < RG; ++k) sum += part[k * 96 + tid];
-      mean[tid] = sum / (float)p.T;
+      mean[tid] = sum / (float)tn;
     }
     __syncthreads();
   }
@@ -777,7 +779,7 @@ bool sd_fbank_utt16_supported(const sd_fbank_plan* plan, int n) {
 }
 
 int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                          int mean_norm, float* out_dev, int ld_out, hipStream_t stream) {
+                          int mean_norm, float* out_dev, int ld_out, hipStream_t stream, const float* rel_len) {
   const int T = 1 + n / HOP;
   U16Args a;
   a.wav = wav_dev; a.B = B; a.n = n; a.T = T;
@@ -787,6 +789,7 @@ int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long 
   a.top_db = plan->top_db;
   a.use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
   a.mean_norm = mean_norm;
+  a.rel_len = rel_len;
   a.out = out_dev; a.ld_out = ld_out;
   const int per_row = plan->n_mels % 4 == 0 ? plan->n_mels / 4 : plan->n_mels;
   a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + per_row - 1) / per_row);

@@ -63,7 +63,7 @@ __device__ __forceinline__ f32x4 combine_max(f32x4* part, int rp, int cg, f32x4 
 // chip, 16 x 16 for the few segments of a small batch (16 segments x 1024 channels: 64 workgroups of 50 dependent steps each took 15-17 us)
 template <typename T, int CGv = CG, int RPv = RP>
 __global__ __launch_bounds__(256) void seg_mean_std_kernel(const T* x, int ld, int col0, int Tn, int C,
-                                                           int want_std, float eps, float* out) {
+                                                           int want_std, float eps, float* out, const float* rel_len) {
   static_assert(CGv * RPv == 256, "one workgroup");
   __shared__ f32x4 part[RPv * CGv];
   const int b = blockIdx.y;
@@ -71,18 +71,19 @@ __global__ __launch_bounds__(256) void seg_mean_std_kernel(const T* x, int ld, i
   const int c = (blockIdx.x * CGv + cg) * 4;
   const bool ok = c < C;
   const T* base = x + (size_t)b * Tn * ld + col0 + (ok ? c : 0);
+  const int nt = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;     // frames that count (relative lengths: speechbrain's mask)
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
   if (ok)
-    for (int t = rp; t < Tn; t += RPv) s += ld4(base + (size_t)t * ld);
+    for (int t = rp; t < nt; t += RPv) s += ld4(base + (size_t)t * ld);
   s = combine_sum<CGv, RPv>(part, rp, cg, s);
-  const float invT = 1.0f / (float)Tn;
+  const float invT = 1.0f / (float)nt;
   const f32x4 mean = s * invT;
   const int ostride = want_std ? 2 * C : C;
   if (ok && rp == 0) st4(out + (size_t)b * ostride + c, mean);
   if (!want_std) return;
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if (ok)
-    for (int t = rp; t < Tn; t += RPv) {
+    for (int t = rp; t < nt; t += RPv) {
       const f32x4 d = ld4(base + (size_t)t * ld) - mean;
       v += d * d;
     }
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int 
 
 template <typename T>
 __global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, const T* h, int ldh,
-                                                       int Tn, int C, float eps, float* out) {
+                                                       int Tn, int C, float eps, float* out, const float* rel_len) {
   __shared__ f32x4 part[RP * CG];
   const int b = blockIdx.y;
   const int cg = threadIdx.x & (CG - 1), rp = threadIdx.x >> 6;
@@ -171,10 +172,11 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, 
   const bool ok = c < C;
   const T* lb = logit + (size_t)b * Tn * ldl + (ok ? c : 0);
   const T* hb = h + (size_t)b * Tn * ldh + (ok ? c : 0);
+  const int nt = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;     // frames past the mask: logit -inf, out of every sum
   const float ninf = -INFINITY;
   f32x4 mx = {ninf, ninf, ninf, ninf};
   if (ok)
-    for (int t = rp; t < Tn; t += RP) {
+    for (int t = rp; t < nt; t += RP) {
       const f32x4 l = ld4(lb + (size_t)t * ldl);
 #pragma unroll
       for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], l[e]);
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, 
   mx = combine_max(part, rp, cg, mx);
   f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = {0.f, 0.f, 0.f, 0.f};
   if (ok)
-    for (int t = rp; t < Tn; t += RP) {
+    for (int t = rp; t < nt; t += RP) {
       const f32x4 l = ld4(lb + (size_t)t * ldl);
       const f32x4 hv = ld4(hb + (size_t)t * ldh);
 #pragma unroll
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, 
   const f32x4 mu = num / den;
   f32x4 var = {0.f, 0.f, 0.f, 0.f};
   if (ok)
-    for (int t = rp; t < Tn; t += RP) {
+    for (int t = rp; t < nt; t += RP) {
       const f32x4 l = ld4(lb + (size_t)t * ldl);
       const f32x4 hv = ld4(hb + (size_t)t * ldh);
 #pragma unroll
@@ -233,7 +235,7 @@ __device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void asp_pool_lds_kernel(const T* logit, int ldl, const T* h, int ldh,
-                                                           int Tn, int C, float eps, float* out) {
+                                                           int Tn, int C, float eps, float* out, const float* rel_len) {
   constexpr int APC = AspTile<T>::APC;
   constexpr int APR = 256 / APC;
   constexpr int VEC = 16 / sizeof(T);          // elements per 16-byte piece
@@ -245,12 +247,13 @@ __global__ __launch_bounds__(256) void asp_pool_lds_kernel(const T* logit, int l
   const int b = blockIdx.y;
   const int c0 = blockIdx.x * APC;
   const int tid = threadIdx.x;
+  const int nt = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;     // frames past the mask are neither staged nor read
   {
     typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
     const int q = (tid % TPR) * VEC, r = tid / TPR;
     const T* lb = logit + (size_t)b * Tn * ldl + c0 + q;
     const T* hb = h + (size_t)b * Tn * ldh + c0 + q;
-    for (int t = r; t < Tn; t += 256 / TPR) {
+    for (int t = r; t < nt; t += 256 / TPR) {
       *reinterpret_cast<vec_t*>(sl + t * APC + q) = *reinterpret_cast<const vec_t*>(lb + (size_t)t * ldl);
       *reinterpret_cast<vec_t*>(sh + t * APC + q) = *reinterpret_cast<const vec_t*>(hb + (size_t)t * ldh);
     }
@@ -267,10 +270,10 @@ __global__ __launch_bounds__(256) void asp_pool_lds_kernel(const T* logit, int l
     return s;
   };
   float mx = -INFINITY;
-  for (int t = rp; t < Tn; t += APR) mx = fmaxf(mx, to_f32(sl[t * APC + c]));
+  for (int t = rp; t < nt; t += APR) mx = fmaxf(mx, to_f32(sl[t * APC + c]));
   mx = combine(mx, red, true);
   float den = 0.f, num = 0.f;
-  for (int t = rp; t < Tn; t += APR) {
+  for (int t = rp; t < nt; t += APR) {
     const float w = expf(to_f32(sl[t * APC + c]) - mx);
     den += w;
     num += w * to_f32(sh[t * APC + c]);
@@ -279,7 +282,7 @@ __global__ __launch_bounds__(256) void asp_pool_lds_kernel(const T* logit, int l
   num = combine(num, red + APR * APC, false);
   const float mu = num / den;
   float var = 0.f;
-  for (int t = rp; t < Tn; t += APR) {
+  for (int t = rp; t < nt; t += APR) {
     const float w = expf(to_f32(sl[t * APC + c]) - mx);
     const float d = to_f32(sh[t * APC + c]) - mu;
     var += w * d * d;
@@ -407,6 +410,12 @@ int sd_cast_f32_f16(const float* x, long n, void* y, sd_stream_t stream) {
 
 extern "C" int sd_seg_mean_std_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, int C, int want_std, float eps,
                                   float* out, sd_stream_t stream) {
+  return sd_seg_mean_std_lens_dt(x, x_dtype, ld, col0, B, T, nullptr, C, want_std, eps, out, stream);
+}
+
+// rel_len (device f32 [B], may be NULL = all ones): each segment's statistics over its first sd_mask_frames(rel_len[b], T) rows
+extern "C" int sd_seg_mean_std_lens_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, const float* rel_len, int C, int want_std,
+                                       float eps, float* out, sd_stream_t stream) {
   if (int e = check_cl_dt("sd_seg_mean_std_dt", x, x_dtype, ld, col0, C)) return e;
   SD_CHECK_ARG(B > 0 && T > 0 && out && sd_aligned16(out), "sd_seg_mean_std_dt: B=%d T=%d / null or unaligned output", B, T);
   dim3 grid((C / 4 + CG - 1) / CG, B);
@@ -414,13 +423,13 @@ extern "C" int sd_seg_mean_std_dt(const void* x, int x_dtype, int ld, int col0, 
   if ((long)grid.x * B < 256) {           // a small batch: 16 channel groups x 16 row phases per workgroup
     dim3 g16((C / 4 + 15) / 16, B);
     if (x_dtype == SD_DT_F16)
-      hipLaunchKernelGGL((seg_mean_std_kernel<_Float16, 16, 16>), g16, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out);
+      hipLaunchKernelGGL((seg_mean_std_kernel<_Float16, 16, 16>), g16, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
     else
-      hipLaunchKernelGGL((seg_mean_std_kernel<float, 16, 16>), g16, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out);
+      hipLaunchKernelGGL((seg_mean_std_kernel<float, 16, 16>), g16, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
   } else if (x_dtype == SD_DT_F16)
-    hipLaunchKernelGGL(seg_mean_std_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out);
+    hipLaunchKernelGGL(seg_mean_std_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
   else
-    hipLaunchKernelGGL(seg_mean_std_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out);
+    hipLaunchKernelGGL(seg_mean_std_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
   SD_CHECK_LAUNCH("seg_mean_std_kernel");
   return SD_OK;
 }
@@ -512,6 +521,12 @@ int sd_colstat_finish_rows(const float* colstat, const float* pivot, const void*
 
 extern "C" int sd_asp_pool_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, int C, float eps,
                               float* out, sd_stream_t stream) {
+  return sd_asp_pool_lens_dt(logit, ldl, h, dtype, ldh, B, T, nullptr, C, eps, out, stream);
+}
+
+// rel_len (device f32 [B], may be NULL = all ones): softmax and statistics over the first sd_mask_frames(rel_len[b], T) frames
+extern "C" int sd_asp_pool_lens_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, const float* rel_len, int C,
+                                   float eps, float* out, sd_stream_t stream) {
   if (int e = check_cl_dt("sd_asp_pool(logit)", logit, dtype, ldl, 0, C)) return e;
   if (int e = check_cl_dt("sd_asp_pool(h)", h, dtype, ldh, 0, C)) return e;
   SD_CHECK_ARG(B > 0 && T > 0 && out && sd_aligned16(out), "sd_asp_pool: B=%d T=%d / null or unaligned output", B, T);
@@ -523,15 +538,33 @@ extern "C" int sd_asp_pool_dt(const void* logit, int ldl, const void* h, int dty
   const float* lf = static_cast<const float*>(logit); const float* hf = static_cast<const float*>(h);
   if (C % apc == 0 && lds <= 64 * 1024) {
     dim3 g2(C / apc, B);
-    if (half) hipLaunchKernelGGL(asp_pool_lds_kernel<_Float16>, g2, dim3(256), lds, s, lh, ldl, hh, ldh, T, C, eps, out);
-    else hipLaunchKernelGGL(asp_pool_lds_kernel<float>, g2, dim3(256), lds, s, lf, ldl, hf, ldh, T, C, eps, out);
+    if (half) hipLaunchKernelGGL(asp_pool_lds_kernel<_Float16>, g2, dim3(256), lds, s, lh, ldl, hh, ldh, T, C, eps, out, rel_len);
+    else hipLaunchKernelGGL(asp_pool_lds_kernel<float>, g2, dim3(256), lds, s, lf, ldl, hf, ldh, T, C, eps, out, rel_len);
     SD_CHECK_LAUNCH("asp_pool_lds_kernel");
     return SD_OK;
   }
   dim3 grid((C / 4 + CG - 1) / CG, B);
-  if (half) hipLaunchKernelGGL(asp_pool_kernel<_Float16>, grid, dim3(256), 0, s, lh, ldl, hh, ldh, T, C, eps, out);
-  else hipLaunchKernelGGL(asp_pool_kernel<float>, grid, dim3(256), 0, s, lf, ldl, hf, ldh, T, C, eps, out);
+  if (half) hipLaunchKernelGGL(asp_pool_kernel<_Float16>, grid, dim3(256), 0, s, lh, ldl, hh, ldh, T, C, eps, out, rel_len);
+  else hipLaunchKernelGGL(asp_pool_kernel<float>, grid, dim3(256), 0, s, lf, ldl, hf, ldh, T, C, eps, out, rel_len);
   SD_CHECK_LAUNCH("asp_pool_kernel");
+  return SD_OK;
+}
+
+__global__ __launch_bounds__(256) void wav_lens_frames_kernel(const float* rel_len, int B, int T, int* n_norm, int* n_mask) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float r = rel_len ? rel_len[b] : 1.f;
+  if (n_norm) n_norm[b] = sd_norm_frames(r, T);
+  if (n_mask) n_mask[b] = sd_mask_frames(r, T);
+}
+
+extern "C" int sd_wav_lens_frames(const float* rel_len_dev, int B, int T, int* n_norm_dev, int* n_mask_dev, sd_stream_t stream) {
+  SD_CHECK_ARG(B >= 0 && T > 0, "sd_wav_lens_frames: B=%d T=%d", B, T);
+  if (B == 0) return SD_OK;
+  SD_CHECK_ARG(n_norm_dev || n_mask_dev, "sd_wav_lens_frames: no output");
+  hipLaunchKernelGGL(wav_lens_frames_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rel_len_dev, B, T,
+                     n_norm_dev, n_mask_dev);
+  SD_CHECK_LAUNCH("wav_lens_frames_kernel");
   return SD_OK;
 }
 

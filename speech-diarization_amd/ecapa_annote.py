@@ -13,6 +13,32 @@ import torch
 from .speech_encode import eres2netv2_encode_batch, using_ecapa_encoder, using_eres2netv2_encoder
 
 
+MIN_NUM_SAMPLES = 5 * 160      # the engine's shortest segment: ECAPA's reflect padding needs 5 frames
+
+
+def masked_signals(waveforms: torch.Tensor, masks: torch.Tensor, min_num_samples: int = MIN_NUM_SAMPLES):
+    """pyannote 3.x's rule for a speechbrain embedding under frame masks: (signals [B, max_kept], wav_lens f32 [B], too_short bool [B]),
+    or (None, None, too_short) when every row keeps fewer than `min_num_samples` samples.
+      1. imask = nearest-interpolate(masks, num_samples) > 0.5;
+      2. the kept samples of each row in order, zero-padded to the longest kept row;
+      3. wav_lens = kept / max_kept (f32);
+      4. rows keeping fewer than min_num_samples samples get wav_lens = 1 (their embedding is to be replaced by NaN)."""
+    B, n = waveforms.shape
+    if masks.dim() != 2 or masks.shape[0] != B:
+        raise ValueError(f"masks must be [{B}, num_frames], got {tuple(masks.shape)}")
+    imasks = torch.nn.functional.interpolate(masks.float().unsqueeze(1), size=n, mode="nearest").squeeze(1) > 0.5
+    imasks = imasks.to(waveforms.device)
+    kept = imasks.sum(dim=1)
+    too_short = kept < min_num_samples
+    max_kept = int(kept.max())
+    if max_kept < min_num_samples:
+        return None, None, too_short
+    signals = torch.nn.utils.rnn.pad_sequence([w[m] for w, m in zip(waveforms, imasks)], batch_first=True)
+    wav_lens = (kept / max_kept).to(torch.float32)
+    wav_lens[too_short] = 1.0
+    return signals, wav_lens, too_short
+
+
 class ECAPAEncoder(torch.nn.Module):
     def __init__(self, device: str | int = 0):
         super().__init__()
@@ -22,14 +48,20 @@ class ECAPAEncoder(torch.nn.Module):
 
     def forward(self, waveforms: torch.Tensor, masks: torch.Tensor | None = None) -> torch.Tensor:
         """waveforms: (batch, num_samples) or (batch, 1, num_samples) -> (batch, dimension),
-        on the encoder's device [REF ecapa_annote.py:13-22]."""
+        on the encoder's device [REF ecapa_annote.py:13-22].  masks (batch, num_frames), optional: pyannote's frame
+        weights; the kept samples of each row are compacted and embedded with relative lengths (`masked_signals`),
+        rows keeping fewer than 800 samples come back as NaN.  None or all ones: the unmasked call."""
         if waveforms.dim() == 3:
             if waveforms.shape[1] != 1:
                 raise ValueError("expected mono waveforms [B, 1, n]")
             waveforms = waveforms[:, 0, :]
-        if masks is not None and not bool(torch.all(masks != 0)):
-            raise NotImplementedError("masked embedding is not part of the reference's adapter")
-        return self.model.encode_batch(waveforms).squeeze(1)
+        if masks is None or bool(torch.all(masks == 1)):
+            return self.model.encode_batch(waveforms).squeeze(1)
+        signals, wav_lens, too_short = masked_signals(waveforms, masks)
+        if signals is None:                  # every row too short: no launch
+            return torch.full((waveforms.shape[0], self.dimension), float("nan"), device=self.model.device)
+        emb = self.model.encode_batch(signals, wav_lens).squeeze(1)
+        return emb.masked_fill(too_short.to(emb.device).unsqueeze(1), float("nan"))
 
 
 class ERes2NetV2Encoder(torch.nn.Module):

@@ -198,6 +198,7 @@ class EmbeddingEngine:
         # "f32s" = f32-split16x3: the f32 schedule (f32 activations) whose wide layers run three f16 MFMA products per value
         # pair at f32-level accuracy; a property of the packed weights (sd_ecapa_weights.split16), same entry point
         self._forward = self._lib.sd_ecapa_forward_f16 if precision == "f16" else self._lib.sd_ecapa_forward_f32
+        self._forward_lens = self._lib.sd_ecapa_forward_lens_f16 if precision == "f16" else self._lib.sd_ecapa_forward_lens_f32
         self._ws = None
         self._ws_frozen = False
 
@@ -234,14 +235,21 @@ class EmbeddingEngine:
         """After a hipGraph capture of `embed`: the captured launches hold the workspace pointers, so it may no longer move."""
         self._ws_frozen = True
 
-    def embed(self, wav: torch.Tensor) -> torch.Tensor:
-        """wav: f32 [B, n] on this engine's device -> f32 [B, dim] on the device (async on the current stream)."""
+    def embed(self, wav: torch.Tensor, rel_lens: torch.Tensor | None = None) -> torch.Tensor:
+        """wav: f32 [B, n] on this engine's device -> f32 [B, dim] on the device (async on the current stream).
+        rel_lens (optional): speechbrain's relative lengths, f32 [B] on the device (validated by the caller: encode_batch);
+        the fbank mean and the SE / pooling statistics then count each row's leading frames only (include/sd_hip.h,
+        "Relative lengths").  The counts come from T of the padded n, so micro-batching does not change them."""
         if wav.dim() != 2:
             raise AssertionError("wav must be [B, n]")
         if wav.device != self.device:
             raise ValueError(f"wav is on {wav.device}, engine on {self.device}")
         wav = wav.contiguous().float()
         B, n = wav.shape
+        if rel_lens is not None:
+            if rel_lens.shape != (B,) or rel_lens.dtype != torch.float32 or rel_lens.device != self.device:
+                raise ValueError(f"rel_lens must be f32 [{B}] on {self.device}, got {rel_lens.dtype} {tuple(rel_lens.shape)} on {rel_lens.device}")
+            rel_lens = rel_lens.contiguous()
         out = torch.empty((B, self.dim), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
@@ -256,6 +264,13 @@ class EmbeddingEngine:
             for lo in range(0, B, mb):
                 nb = min(mb, B - lo)
                 x = wav[lo:lo + nb]
+                if rel_lens is not None:
+                    rl = rel_lens[lo:lo + nb].data_ptr()
+                    N.check(self._lib.sd_fbank_lens_f32(self.plan.handle, x.data_ptr(), nb, n, rl, feats.data_ptr(), self.weights.cfg.input_size,
+                                                        fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_lens_f32")
+                    N.check(self._forward_lens(W, feats.data_ptr(), nb, T, rl, out[lo:lo + nb].data_ptr(),
+                                               ec_ws.data_ptr(), ec_ws.numel(), stream), f"sd_ecapa_forward_lens_{self.precision}")
+                    continue
                 N.check(self._lib.sd_fbank_f32(self.plan.handle, x.data_ptr(), nb, n, 1, feats.data_ptr(), self.weights.cfg.input_size,
                                                fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_f32")
                 N.check(self._forward(W, feats.data_ptr(), nb, T, out[lo:lo + nb].data_ptr(),

@@ -20,6 +20,7 @@ import math
 from dataclasses import dataclass
 
 import numpy as np
+import torch
 
 from . import _native as N
 
@@ -71,6 +72,19 @@ def mel_filters_speechbrain(n_mels: int = 80, sr: int = 16000, f_min: float = 0.
     freqs = np.linspace(0.0, sr // 2, N_FREQ)
     slope = (freqs[:, None] - centre[None, :]) / band[None, :]
     return np.maximum(0.0, np.minimum(slope + 1.0, -slope + 1.0)).astype(np.float32)
+
+
+def length_frames(wav_lens, T: int):
+    """speechbrain's relative lengths -> (n_norm, n_mask), int64 tensors [B]: the frames of a row of T frames that its sentence
+    mean-norm and its masks count.  The host statement of the rule `sd_norm_frames` / `sd_mask_frames` apply on the device
+    (include/sd_hip.h, "Relative lengths"; an unpinned restatement of speechbrain 1.0).  With p = f32(wav_lens * T):
+      n_norm = round_half_even(p) clamped to [0, T]   InputNormalization(sentence): torch.round(lengths * T)
+      n_mask = #{t in [0, T) : float(t) < p}          length_to_mask(lengths * L, max_len=L) = min(T, ceil(p))"""
+    p = torch.as_tensor(wav_lens, dtype=torch.float32).reshape(-1) * T         # f32 product, as torch forms it
+    p = torch.nan_to_num(p, nan=0.0)
+    n_norm = torch.round(p).clamp(0, T).to(torch.int64)
+    n_mask = torch.ceil(p).clamp(0, T).to(torch.int64)
+    return n_norm, n_mask
 
 
 @dataclass(frozen=True)

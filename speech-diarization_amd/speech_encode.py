@@ -122,6 +122,26 @@ def load_ecapa_state_dict(path: str | os.PathLike | None = None) -> dict:
     return make_ecapa_state_dict(SYNTHETIC_SEED)
 
 
+def check_wav_lens(wav_lens, batch: int) -> torch.Tensor | None:
+    """`encode_batch`'s wav_lens argument -> None (no lengths, or all ones: the unmasked path) or a CPU f32 [batch] tensor.
+    Raises ValueError for a wrong shape, a non-finite value or a value outside (0, 1], before anything is launched."""
+    if wav_lens is None:
+        return None
+    wl = torch.as_tensor(wav_lens)
+    if not (wl.dtype.is_floating_point or wl.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"wav_lens must be a real tensor, got {wl.dtype}")
+    wl = wl.detach().to("cpu", torch.float32)
+    if wl.shape != (batch,):
+        raise ValueError(f"wav_lens must have shape [{batch}] (one relative length per row), got {tuple(wl.shape)}")
+    if not bool(torch.isfinite(wl).all()):
+        raise ValueError("wav_lens must be finite")
+    if not bool(((wl > 0) & (wl <= 1)).all()):
+        raise ValueError(f"wav_lens must lie in (0, 1], got min {float(wl.min()):g} max {float(wl.max()):g}")
+    if bool((wl == 1).all()):
+        return None
+    return wl.contiguous()
+
+
 class HipEcapaEncoder:
     """Stands in for speechbrain's `EncoderClassifier`: `.encode_batch(wavs) -> Tensor[B, 1, 192]`."""
 
@@ -137,13 +157,15 @@ class HipEcapaEncoder:
     def encode_batch(self, wavs: torch.Tensor, wav_lens: torch.Tensor | None = None, normalize: bool = False) -> torch.Tensor:
         if wavs.dim() == 1:
             wavs = wavs.unsqueeze(0)
-        if wav_lens is not None and not bool(torch.all(wav_lens == 1)):
-            raise NotImplementedError("relative lengths are not supported: the reference never passes wav_lens, "
-                                      "zero-padded tails count as signal [REF anti_stick_diarize.py:163-168]")
+        # wav_lens: speechbrain's relative lengths (the reference's own callers pass none: their zero-padded tails count as
+        # signal [REF anti_stick_diarize.py:163-168]); None or all ones is that unmasked path, bit for bit
+        wl = check_wav_lens(wav_lens, wavs.shape[0])
         if normalize:
             raise NotImplementedError("normalize=True (speechbrain mean_var_norm_emb) is not used by the reference")
         x = wavs.to(self.device, dtype=torch.float32, non_blocking=True)
-        return self.engine.embed(x).unsqueeze(1)
+        if wl is None:
+            return self.engine.embed(x).unsqueeze(1)
+        return self.engine.embed(x, rel_lens=wl.to(self.device)).unsqueeze(1)
 
     __call__ = encode_batch
 
