@@ -112,9 +112,13 @@ class EcapaRef:
 # ------------------------------------------------------------------ naive numpy version
 
 def _np_conv(x, w, b, dil):
-    """x [B, T, Cin], w [Cout, Cin, k] -> [B, T, Cout], 'same' reflect padding."""
+    """x [B, T, Cin], w [Cout, Cin, k] -> [B, T, Cout], 'same' reflect padding.  Like F.pad(mode="reflect"), refuses
+    pad >= T (a single reflection cannot reach that far; reflecting twice would invent a value speechbrain never computes)."""
     B, T, _ = x.shape
     k = w.shape[2]
+    pad = dil * (k - 1) // 2
+    if pad >= T:
+        raise ValueError(f"reflect padding {pad} needs more than {pad} frames, got T = {T}")
     out = np.zeros((B, T, w.shape[0]), dtype=x.dtype) + b[None, None, :]
     t = np.arange(T)
     for j in range(k):

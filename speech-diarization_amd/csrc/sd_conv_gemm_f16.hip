@@ -1264,7 +1264,8 @@ static int conv1d_cl_split16_narrow(const sd_conv_args* a, hipStream_t stream) {
   SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16), "sd_conv1d_cl_split16: w must be SD_DT_SPLIT16, y f32 or SD_DT_SPLIT16");
   SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "sd_conv1d_cl_split16: M=%d must be a positive multiple of T=%d", a->M, a->T);
   SD_CHECK_ARG(a->cin > 0 && a->cin % 4 == 0 && a->cin_pad >= a->cin && a->cin_pad % 32 == 0, "sd_conv1d_cl_split16: cin=%d (a multiple of 4) cin_pad=%d (of 32)", a->cin, a->cin_pad);
-  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1 && (a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_split16: cout=%d taps=%d dil=%d T=%d", a->cout, a->taps, a->dil, a->T);
+  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_split16: cout=%d taps=%d dil=%d", a->cout, a->taps, a->dil);
+  SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_split16: reflect padding %d needs T > pad (T=%d)", (a->taps / 2) * a->dil, a->T);
   SD_CHECK_ARG(a->lda % 4 == 0 && a->a_col0 % 4 == 0 && a->a_col0 + a->cin <= a->lda && sd_aligned16(a->x) && sd_aligned16(a->w),
                "sd_conv1d_cl_split16: f32 x needs lda / a_col0 multiples of 4, the slice inside the row, 16-byte aligned x and w");
   SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_split16: output slice outside row");

@@ -10,10 +10,14 @@ from __future__ import annotations
 
 import torch
 
+from .engine import min_samples
 from .speech_encode import eres2netv2_encode_batch, using_ecapa_encoder, using_eres2netv2_encoder
+from .synth import EcapaConfig
 
 
-MIN_NUM_SAMPLES = 5 * 160      # the engine's shortest segment: ECAPA's reflect padding needs 5 frames
+# the engine's shortest segment for the spkrec geometry: ECAPA's reflect padding (k = 3, dil = 4) needs 5 frames = 640 samples;
+# ECAPAEncoder uses the floor of the weights it loaded (EmbeddingEngine.min_samples)
+MIN_NUM_SAMPLES = min_samples(EcapaConfig())
 
 
 def masked_signals(waveforms: torch.Tensor, masks: torch.Tensor, min_num_samples: int = MIN_NUM_SAMPLES):
@@ -50,14 +54,15 @@ class ECAPAEncoder(torch.nn.Module):
         """waveforms: (batch, num_samples) or (batch, 1, num_samples) -> (batch, dimension),
         on the encoder's device [REF ecapa_annote.py:13-22].  masks (batch, num_frames), optional: pyannote's frame
         weights; the kept samples of each row are compacted and embedded with relative lengths (`masked_signals`),
-        rows keeping fewer than 800 samples come back as NaN.  None or all ones: the unmasked call."""
+        rows keeping fewer samples than the engine's shortest segment (`EmbeddingEngine.min_samples`: 640 = 5 frames for the
+        spkrec geometry) come back as NaN.  None or all ones: the unmasked call."""
         if waveforms.dim() == 3:
             if waveforms.shape[1] != 1:
                 raise ValueError("expected mono waveforms [B, 1, n]")
             waveforms = waveforms[:, 0, :]
         if masks is None or bool(torch.all(masks == 1)):
             return self.model.encode_batch(waveforms).squeeze(1)
-        signals, wav_lens, too_short = masked_signals(waveforms, masks)
+        signals, wav_lens, too_short = masked_signals(waveforms, masks, self.model.engine.min_samples)
         if signals is None:                  # every row too short: no launch
             return torch.full((waveforms.shape[0], self.dimension), float("nan"), device=self.model.device)
         emb = self.model.encode_batch(signals, wav_lens).squeeze(1)

@@ -18,11 +18,22 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .features import FbankPlan
+from .features import HOP, FbankPlan
 from .synth import EcapaConfig, config_from_state_dict
 
 BN_EPS = 1e-5  # torch.nn.BatchNorm1d default, as used by speechbrain's BatchNorm1d
 K_ALIGN = 32   # K step of the conv/GEMM kernel
+
+
+def min_frames(cfg: EcapaConfig) -> int:
+    """The shortest segment, in frames, the network takes: every "same" conv pads with reflection, which needs pad < T, and the
+    largest pad is max dil * (k - 1) / 2 over the convs (the k = 1 layers pad nothing).  5 for the spkrec geometry (k = 3, dil = 4)."""
+    return 1 + max(d * (k - 1) // 2 for k, d in zip(cfg.kernel_sizes, cfg.dilations))
+
+
+def min_samples(cfg: EcapaConfig) -> int:
+    """The shortest segment in samples: T = 1 + n // 160 frames, so (min_frames - 1) * 160.  640 for the spkrec geometry."""
+    return (min_frames(cfg) - 1) * HOP
 
 
 def _np(x) -> np.ndarray:
@@ -194,6 +205,7 @@ class EmbeddingEngine:
             self.weights = EcapaWeights(state_dict, self.device, precision)
             self.plan = FbankPlan("speechbrain", n_mels=self.weights.cfg.input_size)
         self.dim = self.weights.cfg.lin_neurons
+        self.min_samples = min_samples(self.weights.cfg)
         self.precision = precision
         # "f32s" = f32-split16x3: the f32 schedule (f32 activations) whose wide layers run three f16 MFMA products per value
         # pair at f32-level accuracy; a property of the packed weights (sd_ecapa_weights.split16), same entry point
@@ -253,8 +265,9 @@ class EmbeddingEngine:
         out = torch.empty((B, self.dim), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        if n < 5 * 160:
-            raise ValueError(f"segment of {n} samples is too short: ECAPA's reflect padding needs at least 5 frames (800 samples)")
+        if n < self.min_samples:
+            raise ValueError(f"segment of {n} samples is too short: ECAPA's reflect padding needs at least "
+                             f"{min_frames(self.weights.cfg)} frames ({self.min_samples} samples)")
         with self._lock, torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             mb = min(self.max_batch, B)
@@ -293,8 +306,9 @@ class EmbeddingEngine:
         out = torch.empty((B, self.dim), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        if n < 5 * 160:
-            raise ValueError(f"window of {n} samples is too short: ECAPA's reflect padding needs at least 5 frames (800 samples)")
+        if n < self.min_samples:
+            raise ValueError(f"window of {n} samples is too short: ECAPA's reflect padding needs at least "
+                             f"{min_frames(self.weights.cfg)} frames ({self.min_samples} samples)")
         if signal.numel() < 1:
             raise ValueError("empty signal")
         with self._lock, torch.cuda.device(self.device):

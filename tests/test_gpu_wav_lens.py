@@ -316,16 +316,19 @@ def test_bad_wav_lens_raise_before_launch(dev):
 
 # ------------------------------------------------------------------ 7. pyannote-style masks on ECAPAEncoder
 
-def test_ecapa_encoder_masks(dev):
+def test_ecapa_encoder_masks_from_the_640_sample_floor(dev):
+    """pyannote's mask rule on ECAPAEncoder.  A row is too short (NaN) below the engine's floor, 640 samples = 5 frames: speechbrain's
+    reflect padding (k = 3, dil = 4) needs pad < T, so a row keeping 1 mask frame (320 samples) is NaN and one keeping exactly 640
+    samples is embedded like every other kept row (earlier the floor was 800 samples and a 640-sample row came back NaN)."""
     from speech_diarization_amd import synth
     from speech_diarization_amd.ecapa_annote import ECAPAEncoder
     enc = ECAPAEncoder(0)
-    B, n, F = 4, 32000, 100                                     # 320 samples per mask frame
+    B, n, F = 5, 32000, 100                                     # 320 samples per mask frame
     w = torch.from_numpy(synth.synthetic_segments(7, B, n))
     plain = enc(w)
     assert torch.equal(enc(w, torch.ones(B, F)), plain)
     masks = torch.zeros(B, F)
-    frames = [100, 60, 35, 2]                                   # row 3 keeps 640 samples: too short
+    frames = [100, 60, 35, 1, 2]                                # row 3 keeps 320 samples: too short; row 4 keeps 640: the floor
     for b, k in enumerate(frames):
         masks[b, :k] = 1.0
     got = enc(w.unsqueeze(1), masks)
@@ -336,8 +339,9 @@ def test_ecapa_encoder_masks(dev):
     wl = torch.tensor(kept) / max(kept)
     wl[3] = 1.0
     want = enc.model.encode_batch(comp, wl).squeeze(1)
-    assert torch.equal(got[:3], want[:3])
-    assert torch.isnan(got[3]).all() and torch.isfinite(got[:3]).all()
+    ok = [0, 1, 2, 4]
+    assert torch.equal(got[ok], want[ok])
+    assert torch.isnan(got[3]).all() and torch.isfinite(got[ok]).all()
     short = torch.zeros(B, F)
-    short[:, :2] = 1.0
+    short[:, :1] = 1.0
     assert torch.isnan(enc(w, short)).all()
