@@ -29,6 +29,8 @@
  *   sd_viterbi_f32        replaces  viterbi_hmm [REF diar_diag.py:231-247]
  *   sd_*_lens_*           the same arithmetic under speechbrain's relative lengths (wav_lens of
  *                                   EncoderClassifier.encode_batch): see "Relative lengths" below
+ *   sd_*_packed_*         segments of different lengths in one launch, each embedded as if alone (the reference's
+ *                                   per-segment loop [REF diar_diag.py:341-350] at batch throughput): see "Packed spans"
  *
  * Conventions: every pointer named *_dev / documented "device" is a HIP device
  * pointer; all functions are asynchronous on `stream`, never allocate and never
@@ -385,6 +387,42 @@ int sd_ecapa_forward_lens_f32(const sd_ecapa_weights* w, const float* feats, int
                               float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
 int sd_ecapa_forward_lens_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev,
                               float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
+
+/* ------------------------------------------------------------ packed spans */
+
+/* Packed spans: B segments of different lengths in ONE launch, each embedded as if it were alone (what a B = 1 call of
+ * sd_fbank_f32 + sd_ecapa_forward_f32 on it returns, up to f32 rounding), with no padding to the longest.
+ *   Span s is signal[starts[s] .. starts[s] + lens[s]) of one device-resident f32 signal.  It has T_s = 1 + lens[s] / 160 frames; the
+ *   frames of all spans are stored back to back in span order: frame_start[s] = sum_{r < s} T_r, M = frame_start[B] rows in all, and
+ *   row m of every activation belongs to the span s with frame_start[s] <= m < frame_start[s + 1].
+ *   Tables (device): starts int64 [B], lens int32 [B] (samples), frame_start int32 [B + 1].
+ *   Floor: lens[s] >= 640 samples (5 frames, the reflect padding of the k = 3 / dilation 4 convs; the caller's check).  Precision: exact
+ *   f32 only -- the weights must be packed SD_DT_F32 with split16 = 0 (SD_ERR_UNSUPPORTED otherwise, nothing launched).
+ *   Nothing about span s depends on another span (its length, content or position in the pack): the fbank of a span takes the route a
+ *   call for it alone takes (bitwise that call), the convs reflect inside the span, every statistic, gate and softmax runs over the
+ *   span's rows in a fixed order.  A malformed table (not monotone, a span below the floor, frame_start[B] != M, lens that do not give
+ *   frame_start) gives wrong numbers but never an access outside the buffers: rows are clamped into [0, M).
+ * Like the rest of the ABI the entries never allocate and never synchronise. */
+size_t sd_fbank_packed_workspace_bytes(const sd_fbank_plan* plan, int B, int M, int n_max);
+/* feats of every span -> out [M][ld_out], mean-normalised (speechbrain's front end; plans with zero padding only); n_max >= max lens[s]:
+ * the one-launch kernel takes spans up to 32 100 samples, the folded kernel + finalize the longer ones (two launches for a mixed pack) */
+int sd_fbank_packed_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
+                        const int* lens_dev, const int* frame_start_dev, int B, int M, int n_max,
+                        float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
+/* sd_conv1d_cl_f32 over packed spans (a->M = total rows; a->T ignored): the reflect padding and a per-segment bias (bias[s * cout + n])
+ * are those of the row's span; always the 128x128 kernel, whatever sd_set_tuning selects; no column statistics */
+int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream);
+/* the three statistics / gating operators of sd_seg_mean_std_dt, sd_se_scale_residual_dt and sd_asp_pool_dt over each span's rows of M */
+int sd_seg_mean_std_packed_dt(const void* x, int x_dtype, int ld, int col0, const int* frame_start_dev, int B, int M, int C,
+                              int want_std, float eps, float* out, sd_stream_t stream);
+int sd_se_scale_residual_packed_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy,
+                                   int y_col0, const int* frame_start_dev, int B, int M, int C, int dtype, sd_stream_t stream);
+int sd_asp_pool_packed_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, const int* frame_start_dev, int B, int M, int C,
+                          float eps, float* out, sd_stream_t stream);
+size_t sd_ecapa_packed_workspace_bytes(const sd_ecapa_weights* w, int B, int M);
+/* feats: device f32 [M][n_mels] from sd_fbank_packed_f32; emb: device f32 [B][emb_dim] */
+int sd_ecapa_forward_packed_f32(const sd_ecapa_weights* w, const float* feats, const int* frame_start_dev, int B, int M,
+                                float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream);
 
 /* ------------------------------------------------------ cosine / affinity */
 

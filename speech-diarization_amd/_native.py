@@ -158,6 +158,15 @@ PROTOTYPES = {
     "sd_asp_attend_pool_lens_dt": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _F, _P, _P]),
     "sd_ecapa_forward_lens_f32": (_I, [C.POINTER(sd_ecapa_weights), _P, _I, _I, _P, _P, _P, _Z, _P]),
     "sd_ecapa_forward_lens_f16": (_I, [C.POINTER(sd_ecapa_weights), _P, _I, _I, _P, _P, _P, _Z, _P]),
+    # packed spans (segments of different lengths in one launch, each embedded as if alone)
+    "sd_fbank_packed_workspace_bytes": (_Z, [_P, _I, _I, _I]),
+    "sd_fbank_packed_f32": (_I, [_P, _P, C.c_longlong, _P, _P, _P, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    "sd_conv1d_cl_packed_f32": (_I, [C.POINTER(sd_conv_args), _P, _I, _P]),
+    "sd_seg_mean_std_packed_dt": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
+    "sd_se_scale_residual_packed_dt": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "sd_asp_pool_packed_dt": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P]),
+    "sd_ecapa_packed_workspace_bytes": (_Z, [C.POINTER(sd_ecapa_weights), _I, _I]),
+    "sd_ecapa_forward_packed_f32": (_I, [C.POINTER(sd_ecapa_weights), _P, _P, _I, _I, _P, _P, _Z, _P]),
 }
 
 _lib = None

@@ -190,10 +190,12 @@ def scd_split_segments(y: np.ndarray, sr: int, segments: list[Segment], win_ms: 
 # --------------------------------------------------------------------------- segment embeddings
 
 def embed_segments(y: np.ndarray, sr: int, segs: list[Segment], batch_size: int = 32, min_duration_ms: float = 500.0,
-                   pad_duration_ms: float = 150.0, encode: Encoder | None = None) -> np.ndarray:
+                   pad_duration_ms: float = 150.0, encode: Encoder | None = None, packed: bool = False) -> np.ndarray:
     """One embedding per segment -> (num_segments, 192).  Batches of `batch_size` consecutive
     segments, zero-padded to the batch's longest; segments shorter than `min_duration_ms` are
-    widened by `pad_duration_ms` on both sides first."""
+    widened by `pad_duration_ms` on both sides first.
+    packed=True (opt-in): each (widened) snippet is embedded as if alone, as a span of `y` with no padding
+    (`HipEcapaEncoder.encode_spans`; with an injected `encode`, one call per snippet); `batch_size` is then unused."""
     if len(segs) == 0:
         return np.empty((0, EMB_DIM), dtype=np.float32)
     min_len = int(min_duration_ms / 1000.0 * sr)
@@ -205,6 +207,22 @@ def embed_segments(y: np.ndarray, sr: int, segs: list[Segment], batch_size: int 
         if piece.shape[0] < min_len:
             piece = y[max(0, s - widen): min(len(y), e + widen)]
         return piece
+
+    if packed:
+        # the same snippets as [start, end) of y (segment times are >= 0, so y[s:e] is y[min(s, len):min(e, len)])
+        n_y = len(y)
+        starts, lengths = [], []
+        for seg in segs:
+            s, e = int(seg.start * sr), int(seg.end * sr)
+            lo, hi = min(s, n_y), min(e, n_y)
+            if max(0, hi - lo) < min_len:
+                lo, hi = max(0, s - widen), min(n_y, e + widen)
+            starts.append(lo)
+            lengths.append(max(0, hi - lo))
+        if encode is not None:
+            return np.concatenate([encode(np.ascontiguousarray(y[a:a + n])[None]) for a, n in zip(starts, lengths)], axis=0)
+        from .speech_encode import using_ecapa_encoder
+        return using_ecapa_encoder().encode_spans(y, np.array(starts, np.int64), np.array(lengths, np.int64))
 
     batches = []
     for lo in range(0, len(segs), batch_size):
@@ -364,7 +382,8 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
             morph_close_ms: float = 40.0, scd_win_ms: float = 1000.0, scd_hop_ms: float = 200, scd_thr: float = 1.50,
             merge_max_gap_s: float = 0.5, merge_max_speech_s: float = 30.0, merge_mincos: float = 0.8, reseg: int = 1, *,
             cluster_cos: float = 0.70, encode: Encoder | None = None, vad_segments: Callable | None = None,
-            compat_reference_bugs: bool = False, clusterer: str | Callable = "hdbscan_two_stage") -> list[Segment]:
+            compat_reference_bugs: bool = False, clusterer: str | Callable = "hdbscan_two_stage",
+            packed_embeddings: bool = False) -> list[Segment]:
     """VAD -> SCD split -> embed -> cluster -> conservative merge -> re-embed -> frame reassignment ->
     merge_adjacent: the stage order and the positional parameters of [REF anti_stick_diarize.py:493-511] (the 17
     parameters up to `reseg`, same order and defaults; what this build adds is keyword-only).
@@ -376,7 +395,10 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     `clusterer` selects what sits inside the reference's `cluster_hdbscan_two_stage(embs, min_cluster_size=2)`
     [REF :536]: "hdbscan_two_stage" (default: the two-stage glue over `cluster.default_hdbscan_factory`),
     "ahc" (the same glue with average-linkage AHC cut at `cluster_cos` injected as the clusterer), "ahc_affinity"
-    (single-stage AHC on the GPU cosine affinity), or a `clusterer_factory(**kwargs)` callable."""
+    (single-stage AHC on the GPU cosine affinity), or a `clusterer_factory(**kwargs)` callable.
+
+    `packed_embeddings=True` embeds every segment as if alone (`embed_segments(..., packed=True)`) instead of in the reference's
+    zero-padded batches of 32 (the default)."""
     from . import cluster
     if isinstance(wav_path, np.ndarray):
         y = np.ascontiguousarray(wav_path, dtype=np.float32)
@@ -391,7 +413,7 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
         return []
     speech = [Segment(s, e) for s, e in speech_t]
     speech2 = scd_split_segments(y, sr, speech, win_ms=scd_win_ms, hop_ms=scd_hop_ms, thr=scd_thr, encode=encode)
-    embs = embed_segments(y, sr, speech2, encode=encode)
+    embs = embed_segments(y, sr, speech2, encode=encode, packed=packed_embeddings)
     if clusterer == "ahc_affinity":
         raw = cluster.ahc_cosine(cosine_affinity(embs, _on_gpu(encode)), cluster_cos)
     else:
@@ -406,7 +428,7 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     merge_input = labels if compat_reference_bugs else embs
     speech3 = conservative_merge(speech2, merge_input, max_gap_s=merge_max_gap_s, max_turn_s=merge_max_speech_s,
                                  min_cos=merge_mincos)
-    embs3 = embed_segments(y, sr, speech3, encode=encode)
+    embs3 = embed_segments(y, sr, speech3, encode=encode, packed=packed_embeddings)
     speech4 = frame_reassign(y, sr, speech, speech3, embs3, smooth_step=0.10, win=1.0, encode=encode) if reseg else speech3
     return merge_adjacent(speech4, gap=merge_max_gap_s)
 

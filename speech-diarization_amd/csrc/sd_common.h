@@ -106,6 +106,18 @@ __host__ __device__ __forceinline__ int sd_mask_frames(float rel, int T) {
   return c >= (float)T ? T : (c > 0.f ? (int)c : 0);
 }
 
+// Packed spans (sd_hip.h): the span that owns row m = the largest s < B with frame_start[s] <= m (0 if there is none).  Reads
+// frame_start[1 .. B - 1] only and returns an s in [0, B) for ANY table, so a malformed one gives wrong numbers, never a wild index.
+__device__ __forceinline__ int sd_span_of(const int* frame_start, int B, int m) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (frame_start[mid] <= m) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
 __device__ __forceinline__ float sd_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -49,9 +49,11 @@ __device__ unsigned long long sd_c32_stamp_buf[8192 * 10];
 // permuted at the source, chunk c of row r living at position c ^ ((r >> 1) & 7): the fragment reads of 16
 // consecutive rows then hit 16 different bank groups.
 // NJ: 32-column MFMA tiles per wave: 2 = the 128x128 tile; 1 = a 128x64 tile (DMA only; conv_gemm_f32_n64_kernel below)
-template <bool DMA, int NJ = 2>
+// PACKED (packed spans, sd_hip.h; conv_gemm_f32_packed_kernel): a staged row's segment is its span [pk_fs[s], pk_fs[s + 1]),
+// s = sd_span_of(pk_fs, pk_n, m), instead of [m / T * T, + T); the reflected row is clamped into [0, M)
+template <bool DMA, int NJ = 2, bool PACKED = false>
 __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int vec, const int tile_m, const int tile_n, float* smem,
-                                              const bool mirror = false) {
+                                              const bool mirror = false, const int* pk_fs = nullptr, const int pk_n = 0) {
   static_assert(NJ == 2 || (NJ == 1 && DMA), "the half-width tile exists in the LDS-DMA form only");
   constexpr int TBN = 64 * NJ;                // tile columns
   constexpr int TLDC = TBN + 4;               // padded row of the C tile
@@ -76,7 +78,7 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
   const int c4 = tid & 7;
   const int r0 = tid >> 3;
 
-  int a_seg[4], a_t[4];
+  int a_seg[4], a_t[4], a_len[4];
   const float* wptr[4];
   const float* aptr[4];
   const int ktot = p.taps * p.cin_pad;
@@ -85,9 +87,17 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
   for (int i = 0; i < 4; ++i) {
     int m = m0 + r0 + 32 * i;
     m = m < p.M ? m : p.M - 1;
-    const int seg = (m / p.T) * p.T;
-    a_seg[i] = seg;
-    a_t[i] = m - seg;
+    if constexpr (PACKED) {
+      const int s = sd_span_of(pk_fs, pk_n, m);
+      a_seg[i] = pk_fs[s];
+      a_len[i] = pk_fs[s + 1] - a_seg[i];
+      a_t[i] = m - a_seg[i];
+    } else {
+      const int seg = (m / p.T) * p.T;
+      a_seg[i] = seg;
+      a_t[i] = m - seg;
+      a_len[i] = p.T;
+    }
     int n = n0 + r0 + 32 * i;
     n = n < p.cout ? n : p.cout - 1;
     wptr[i] = W + (size_t)n * ktot + (DMA ? 0 : c4 * 4);
@@ -101,9 +111,18 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int tt = a_t[i] + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
-      aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
+      if constexpr (PACKED) {
+        const int Ts = a_len[i];
+        tt = tt < 0 ? -tt : tt;
+        tt = tt >= Ts ? 2 * (Ts - 1) - tt : tt;
+        int r = a_seg[i] + tt;
+        r = r < 0 ? 0 : (r >= p.M ? p.M - 1 : r);
+        aptr[i] = X + (size_t)r * p.lda;
+      } else {
+        tt = tt < 0 ? -tt : tt;
+        tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+        aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
+      }
     }
   };
 
@@ -275,7 +294,7 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
 #ifdef SD_STAMP
   const unsigned long long t_e2 = __builtin_amdgcn_s_memtime();
 #endif
-  sd_store_tile<float, BM, TBN, 256, 2, NJ == 2 ? 3 : 2>(p, Cs, TLDC, m0, n0, tid, vec);
+  sd_store_tile<float, BM, TBN, 256, 2, NJ == 2 ? 3 : 2, false, PACKED>(p, Cs, TLDC, m0, n0, tid, vec, pk_fs, pk_n);
   if (NJ == 2 && mirror && tile_m != tile_n) {
     // symmetric product (x = w, the affinity): the tile below the diagonal is this tile transposed, written
     // from the same LDS image.  8 lanes cover one 128-byte line of an output row (32 consecutive m), a wave
@@ -371,6 +390,15 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const sd_conv_arg
     conv_tile_f32<DMA>(p, vec, tm, tn, smem, mirror);
     __syncthreads();              // the next tile refills the LDS stage the epilogue was reading
   }
+}
+
+// The 128x128 LDS-DMA tile over packed spans (sd_conv1d_cl_packed_f32): one workgroup per tile, row tiles outer.  Every row of a tile
+// computes what it would in a launch of its span alone (same K order, same epilogue arithmetic): a span's rows do not depend on the others.
+__global__ __launch_bounds__(256, 2) void conv_gemm_f32_packed_kernel(const sd_conv_args p, const int vec, const int* frame_start, const int nspan) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int n_tiles = (p.cout + BN - 1) / BN;
+  const int tm = (int)blockIdx.x / n_tiles;
+  conv_tile_f32<true, 2, true>(p, vec, tm, (int)blockIdx.x - tm * n_tiles, smem, false, frame_start, nspan);
 }
 
 // Tiles of 16 J rows x 128 columns (J = 5, 6, 7: 80, 96, 112 rows) for launches whose 128-row tiles divide badly over the 256 CUs: a launch
@@ -1277,6 +1305,47 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
                          static_cast<hipStream_t>(stream), *a, vec, ord, (int)ntiles);
   }
   SD_CHECK_LAUNCH("conv_gemm_f32_kernel");
+  return SD_OK;
+}
+
+// Packed spans: the position-dependent layers (taps > 1: reflect padding inside the span; a per-segment bias: the span's row) on the
+// 128x128 kernel's packed form, whatever sd_set_tuning selects for uniform launches (no other kernel has the span map).  a->T is ignored.
+extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream) {
+  SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_packed_f32: null args");
+  SD_CHECK_ARG(B >= 1 && frame_start_dev != nullptr, "sd_conv1d_cl_packed_f32: B=%d, frame_start %p", B, (const void*)frame_start_dev);
+  SD_CHECK_ARG(a->w_dtype == SD_DT_F32 && a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_packed_f32: x / w / y must be f32");
+  SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_packed_f32: null x/w/y");
+  SD_CHECK_ARG(a->M > 0, "sd_conv1d_cl_packed_f32: M=%d", a->M);
+  SD_CHECK_ARG(a->cin > 0 && a->cin % 4 == 0, "sd_conv1d_cl_packed_f32: cin=%d must be a positive multiple of 4", a->cin);
+  SD_CHECK_ARG(a->cin_pad >= a->cin && a->cin_pad % BK == 0, "sd_conv1d_cl_packed_f32: cin_pad=%d must be >= cin and a multiple of %d", a->cin_pad, BK);
+  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_packed_f32: cout=%d taps=%d dil=%d", a->cout, a->taps, a->dil);
+  SD_CHECK_ARG(a->lda % 4 == 0 && a->a_col0 % 4 == 0 && a->a_col0 >= 0 && a->a_col0 + a->cin <= a->lda,
+               "sd_conv1d_cl_packed_f32: lda=%d a_col0=%d cin=%d (need multiples of 4, slice inside row)", a->lda, a->a_col0, a->cin);
+  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_packed_f32: output slice outside row");
+  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "sd_conv1d_cl_packed_f32: x and w must be 16-byte aligned");
+  if (a->tee) {
+    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
+                 "sd_conv1d_cl_packed_f32: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
+    if (a->tee_add)
+      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "sd_conv1d_cl_packed_f32: tee_add slice outside row");
+  }
+  if (a->colstat) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_conv1d_cl_packed_f32: no column statistics over packed spans");
+  int vec = a->cout % 8 == 0 && a->ldo % 4 == 0 && a->o_col0 % 4 == 0 && sd_aligned16(a->y);
+  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);
+  if (a->tee) {
+    vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 4 == 0 && sd_aligned16(a->tee);
+    if (a->tee_add) vec = vec && a->ld_ta % 4 == 0 && a->ta_col0 % 4 == 0 && sd_aligned16(a->tee_add);
+  }
+  const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
+  SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_packed_f32: grid too large");
+  const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);     // as the uniform launch: the epilogue's C tile needs BM * LDC
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_packed_kernel), (int)lds));
+  {
+    SdProfScope prof(SD_PROF_CONV_GEMM, static_cast<hipStream_t>(stream), 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
+    hipLaunchKernelGGL(conv_gemm_f32_packed_kernel, dim3((unsigned)tiles), dim3(256), lds, static_cast<hipStream_t>(stream), *a, vec,
+                       frame_start_dev, B);
+  }
+  SD_CHECK_LAUNCH("conv_gemm_f32_packed_kernel");
   return SD_OK;
 }
 

@@ -45,8 +45,8 @@ struct Buffers {
 
 int max_i(int a, int b) { return a > b ? a : b; }
 
-Buffers carve(const sd_ecapa_weights* w, int B, int T, void* ws, int act_dtype) {
-  const size_t M = (size_t)B * T;
+// M: activation rows (B * T; packed spans: the total of their frames)
+Buffers carve(const sd_ecapa_weights* w, int B, size_t M, void* ws, int act_dtype) {
   const size_t es = act_dtype == SD_DT_F16 ? 2 : 4;
   const int C = w->channels, Cm = w->mfa_channels, chunk = C / w->res2_scale;
   int se = 0;
@@ -234,18 +234,25 @@ int run_wide(const sd_layer& l, sd_conv_args a, bool split, void* xs, long narro
 // run on the padded rows as without them; the SE squeezes, the global mean / std of the attentive pooling and its softmax and statistics
 // count each row's first sd_mask_frames(rel_len[b], T) frames only.  Those statistics then come from the row-masked reduction kernels
 // (no column statistics from the conv epilogues), and both pooling routes take the mask.
+// span (device int32 [B + 1], NULL = uniform): packed spans ("Packed spans", sd_hip.h) of span_rows rows in all, exact f32 only.  The
+// position-dependent layers (the k = 5 stem, the dilated Res2Net convs, the attention TDNN with its per-segment bias) run on the packed conv,
+// the position-free 1x1 layers on the uniform operator as ONE segment of M rows (T = M: the reflect is a no-op), every statistic and the SE
+// gate on the packed reductions; the per-segment layers (B rows) as always.
 int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb, void* ws_dev, size_t ws_bytes,
-            sd_stream_t stream, int dt, const float* rel_len = nullptr) {
+            sd_stream_t stream, int dt, const float* rel_len = nullptr, const int* span = nullptr, int span_rows = 0) {
   SD_TRY(check_weights(w, dt));
   SD_CHECK_ARG(B >= 0 && T > 0, "sd_ecapa_forward: B=%d T=%d", B, T);
   if (B == 0) return SD_OK;
   SD_CHECK_ARG(feats && emb && ws_dev, "sd_ecapa_forward: null feats/emb/workspace");
-  SD_CHECK_ARG((long)B * T < (1L << 31), "sd_ecapa_forward: B*T overflows int");
+  SD_CHECK_ARG(span || (long)B * T < (1L << 31), "sd_ecapa_forward: B*T overflows int");
   SD_CHECK_ARG(sd_aligned16(ws_dev), "sd_ecapa_forward: workspace must be 16-byte aligned");
-  const Buffers b = carve(w, B, T, ws_dev, dt);
+  const int M = span ? span_rows : B * T;
+  const Buffers b = carve(w, B, (size_t)M, ws_dev, dt);
   if (ws_bytes < b.bytes) return sd_set_error(SD_ERR_WORKSPACE, "sd_ecapa_forward: workspace %zu < %zu bytes", ws_bytes, b.bytes);
+  const int Tc = span ? M : T;          // the segment length the position-free layers see
+  // the position-dependent layers: uniform -> the given runner; packed spans -> the packed conv
+  auto by_span = [&](const sd_conv_args& a, auto&& uniform) -> int { return span ? sd_conv1d_cl_packed_f32(&a, span, B, stream) : uniform(); };
 
-  const int M = B * T;
   const int C = w->channels, Cm = w->mfa_channels, chunk = C / w->res2_scale;
   const int F32 = SD_DT_F32;
   const size_t es = dt == SD_DT_F16 ? 2 : 4;
@@ -265,7 +272,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     const char* e = sd_experiment_env("SD_COLSTAT");
     return !(e && e[0] == '0');
   }();
-  const bool colstat_on = colstat_ok && rel_len == nullptr;      // the epilogue's column statistics sum over all T rows of a segment
+  const bool colstat_on = colstat_ok && rel_len == nullptr && span == nullptr;    // the epilogue's column statistics sum over all T rows of a segment
   bool x0_split = false;                                 // the stem's output exists as SD_DT_SPLIT16 only (b.x0s)
   // block 0: TDNNBlock(n_mels -> C, k=5) on the f32 features.  f16: the features are rounded to f16 once (the
   // operand precision of that path anyway; t2 is free here), which lets the stem run on the LDS-DMA kernel of the
@@ -278,13 +285,13 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       SD_TRY(sd_cast_f32_f16(feats, (long)M * w->n_mels, b.t2, stream));
       x = b.t2; xdt = SD_DT_F16;
     }
-    sd_conv_args a = conv_of(w->block0, x, xdt, w->n_mels, 0, b.x0, dt, C, 0, M, T, SD_ACT_RELU);
+    sd_conv_args a = conv_of(w->block0, x, xdt, w->n_mels, 0, b.x0, dt, C, 0, M, Tc, SD_ACT_RELU);
     // f32-split16x3, wide layers split: both readers of the stem's output (block 1's tdnn1 and its shortcut) take SD_DT_SPLIT16, so the
     // stem writes that form and nothing else (no f32 tensor, no pack pass) -- unless a small launch sends tdnn1 to the narrow kernel
     x0_split = wsplit && b.x0s && b.xcs && wide_packed(w->block0) && wide_packed(w->blocks[0].tdnn1) && !wide_goes_narrow(w->block0, M, nt) &&
                !wide_goes_narrow(w->blocks[0].tdnn1, M, nt);
     if (x0_split) { a.y = b.x0s; a.y_dtype = SD_DT_SPLIT16; }
-    SD_TRY(run_wide(w->block0, a, wsplit, b.xs, nt, stream));
+    SD_TRY(by_span(a, [&] { return run_wide(w->block0, a, wsplit, b.xs, nt, stream); }));
   }
   const void* xin = b.x0; int ldin = C, colin = 0;
   // where the current block input exists as SD_DT_SPLIT16 (null: it does not), and whether its f32 form was skipped
@@ -305,7 +312,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     const bool chain = chain_ok && dt == SD_DT_F16 && w->res2_scale >= 2 &&
                        sd_res2net_chain_supported(T, chunk, w->res2_scale - 1, r2.taps, r2.dil);
     {
-      sd_conv_args a = conv_of(blk.tdnn1, xin, dt, ldin, colin, b.r, dt, C, 0, M, T, SD_ACT_RELU);
+      sd_conv_args a = conv_of(blk.tdnn1, xin, dt, ldin, colin, b.r, dt, C, 0, M, Tc, SD_ACT_RELU);
       if (!chain) { a.tee = b.s0; a.ldt = chunk; a.tee_lo = chunk; a.tee_hi = 2 * chunk; }
       // (blocks 2..: the input is a slice of xcat, whose split twin the previous block's SE kernel has written)
       SD_TRY(run_wide(blk.tdnn1, a, wsplit, b.xs, nt, stream, in_sp, in_sp_ld));
@@ -322,25 +329,26 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       for (int j = 1; j < w->res2_scale; ++j) {
         void* src = (j & 1) ? b.s0 : b.s1;
         void* dst = (j & 1) ? b.s1 : b.s0;
-        sd_conv_args a = conv_of(blk.res2[j - 1], src, dt, chunk, 0, b.r, dt, C, j * chunk, M, T, SD_ACT_RELU);
+        sd_conv_args a = conv_of(blk.res2[j - 1], src, dt, chunk, 0, b.r, dt, C, j * chunk, M, Tc, SD_ACT_RELU);
         if (r_split) { a.y = b.rs; a.y_dtype = SD_DT_SPLIT16; }
         if (j + 1 < w->res2_scale) {
           a.tee = dst; a.ldt = chunk; a.tee_lo = 0; a.tee_hi = chunk;
           a.tee_add = b.r; a.ld_ta = C; a.ta_col0 = (j + 1) * chunk;
         }
-        SD_TRY(run_narrow(blk.res2[j - 1], a, split, stream));
+        SD_TRY(by_span(a, [&] { return run_narrow(blk.res2[j - 1], a, split, stream); }));
       }
     }
     // tdnn2; the SE squeeze (mean over T) comes out of its epilogue as per-tile column sums where the
     // geometry allows (the Res2Net scratch s0 is dead and holds them), else from a pass over t2
     {
-      sd_conv_args a = conv_of(blk.tdnn2, b.r, dt, C, 0, b.t2, dt, C, 0, M, T, SD_ACT_RELU);
+      sd_conv_args a = conv_of(blk.tdnn2, b.r, dt, C, 0, b.t2, dt, C, 0, M, Tc, SD_ACT_RELU);
       const bool stat = colstat_on && T >= (wsplit ? 128 : 64) && C % 256 == 0 && !(wsplit && blk.tdnn2.w_split && wide_goes_narrow(blk.tdnn2, M, nt)) &&
                         (size_t)((M + stat_unit - 1) / stat_unit) * 6 * C * sizeof(float) <= (size_t)M * chunk * es;
       if (stat) a.colstat = static_cast<float*>(b.s0);
       int rows = 128;
       SD_TRY(run_wide(blk.tdnn2, a, wsplit, b.xs, nt, stream, r_split ? b.rs : nullptr, C, stat ? &rows : nullptr));
       if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.t2, dt, C, 0, B, T, C, 0, 0.f, b.semean, rows, stream));
+      else if (span) SD_TRY(sd_seg_mean_std_packed_dt(b.t2, dt, C, 0, span, B, M, C, 0, 0.f, b.semean, stream));
       else SD_TRY(sd_seg_mean_std_lens_dt(b.t2, dt, C, 0, B, T, rel_len, C, 0, 0.f, b.semean, stream));
     }
     // squeeze-excitation gate (per-segment, f32)
@@ -360,9 +368,12 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       const bool skip_f32 = twin && wide_packed(w->mfa) && !wide_goes_narrow(w->mfa, M, nt) && !next_reads_f32 &&
                             (i + 1 >= w->n_blocks || wide_packed(w->blocks[i + 1].tdnn1));
       const bool res_twin = twin && in_sp != nullptr && res_is_twin;
-      SD_TRY(sd_se_scale_residual_split(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, B, T, C, dt,
-                                        twin ? b.xcs : nullptr, Cm, i * C, stream,
-                                        res_twin ? in_sp : nullptr, in_sp_ld, in_sp_col, skip_f32 ? 0 : 1));
+      if (span)      // (exact f32 only: no split copies)
+        SD_TRY(sd_se_scale_residual_packed_dt(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, span, B, M, C, dt, stream));
+      else
+        SD_TRY(sd_se_scale_residual_split(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, B, T, C, dt,
+                                          twin ? b.xcs : nullptr, Cm, i * C, stream,
+                                          res_twin ? in_sp : nullptr, in_sp_ld, in_sp_col, skip_f32 ? 0 : 1));
       res_is_twin = skip_f32;                            // the next block's shortcut exists only as the split copy
       in_sp = twin ? b.xcs : nullptr; in_sp_ld = Cm; in_sp_col = i * C;
     }
@@ -371,13 +382,14 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
   // multi-layer feature aggregation; the global mean / std of attentive pooling likewise from the
   // epilogue (column sums in r, dead since the last block's tdnn2)
   {
-    sd_conv_args a = conv_of(w->mfa, b.xcat, dt, Cm, 0, b.h, dt, Cm, 0, M, T, SD_ACT_RELU);
+    sd_conv_args a = conv_of(w->mfa, b.xcat, dt, Cm, 0, b.h, dt, Cm, 0, M, Tc, SD_ACT_RELU);
     const bool stat = colstat_on && T >= (wsplit ? 128 : 64) && Cm % 256 == 0 && !(wsplit && w->mfa.w_split && wide_goes_narrow(w->mfa, M, nt)) &&
                       (size_t)((M + stat_unit - 1) / stat_unit) * 6 * Cm * sizeof(float) <= (size_t)M * C * es;
     if (stat) a.colstat = static_cast<float*>(b.r);
     int rows = 128;
     SD_TRY(run_wide(w->mfa, a, wsplit, b.xs, nt, stream, b.xcs, Cm, stat ? &rows : nullptr));
     if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.h, dt, Cm, 0, B, T, Cm, 1, w->asp_eps, b.stats, rows, stream));
+    else if (span) SD_TRY(sd_seg_mean_std_packed_dt(b.h, dt, Cm, 0, span, B, M, Cm, 1, w->asp_eps, b.stats, stream));
     else SD_TRY(sd_seg_mean_std_lens_dt(b.h, dt, Cm, 0, B, T, rel_len, Cm, 1, w->asp_eps, b.stats, stream));
   }
   // attentive statistics pooling with global context
@@ -385,16 +397,16 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     sd_conv_args g = conv_of(w->asp_tdnn_g, b.stats, F32, 2 * Cm, 0, b.gbias, F32, w->att_channels, 0, B, 1, SD_ACT_NONE);
     g.scale = nullptr; g.shift = nullptr;
     SD_TRY(sd_seg_gemm_f32(&g, b.skp_bytes ? b.skp : nullptr, b.skp_bytes, stream));
-    sd_conv_args a = conv_of(w->asp_tdnn_h, b.h, dt, Cm, 0, b.a1, dt, w->att_channels, 0, M, T, SD_ACT_RELU);
+    sd_conv_args a = conv_of(w->asp_tdnn_h, b.h, dt, Cm, 0, b.a1, dt, w->att_channels, 0, M, Tc, SD_ACT_RELU);
     a.bias = b.gbias; a.bias_per_seg = 1; a.act2 = SD_ACT_TANH;
-    SD_TRY(run_narrow(w->asp_tdnn_h, a, split, stream));
+    SD_TRY(by_span(a, [&] { return run_narrow(w->asp_tdnn_h, a, split, stream); }));
     // asp.conv + softmax over T + weighted statistics: one kernel where the geometry allows (the
     // [M][3C] logits are then never stored), else the conv followed by the pooling kernel
     static const bool fuse_ok = [] {     // SD_ASP_FUSED=0: A/B switch for measurements
       const char* e = sd_experiment_env("SD_ASP_FUSED");
       return !(e && e[0] == '0');
     }();
-    const bool fused = fuse_ok && w->asp_conv.taps == 1 && w->asp_conv.cin_pad == w->att_channels &&
+    const bool fused = fuse_ok && !span && w->asp_conv.taps == 1 && w->asp_conv.cin_pad == w->att_channels &&
                        sd_asp_attend_pool_supported(dt, T, Cm, w->att_channels);
     if (fused) {
       // (split16 mode: the same f32 tensors, the logits product on the f16 matrix cores with split operands)
@@ -403,9 +415,10 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       SD_TRY(sd_asp_attend_pool_scaled(b.a1, w->asp_conv.w, b.h, split ? SD_DT_SPLIT16 : dt, Cm, B, T, Cm, w->att_channels, w->asp_eps, ws, b.pooled, stream,
                                             rel_len));
     } else {
-      sd_conv_args c = conv_of(w->asp_conv, b.a1, dt, w->att_channels, 0, b.e, dt, Cm, 0, M, T, SD_ACT_NONE);
+      sd_conv_args c = conv_of(w->asp_conv, b.a1, dt, w->att_channels, 0, b.e, dt, Cm, 0, M, Tc, SD_ACT_NONE);
       SD_TRY(run_conv(c, stream));
-      SD_TRY(sd_asp_pool_lens_dt(b.e, Cm, b.h, dt, Cm, B, T, rel_len, Cm, w->asp_eps, b.pooled, stream));
+      if (span) SD_TRY(sd_asp_pool_packed_dt(b.e, Cm, b.h, dt, Cm, span, B, M, Cm, w->asp_eps, b.pooled, stream));
+      else SD_TRY(sd_asp_pool_lens_dt(b.e, Cm, b.h, dt, Cm, B, T, rel_len, Cm, w->asp_eps, b.pooled, stream));
     }
   }
   // asp_bn (folded into the weights by the host) + fc
@@ -420,7 +433,24 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
 
 extern "C" size_t sd_ecapa_workspace_bytes(const sd_ecapa_weights* w, int B, int T) {
   if (!w || B <= 0 || T <= 0 || w->res2_scale <= 0) return 0;
-  return carve(w, B, T, nullptr, w->w_dtype).bytes;
+  return carve(w, B, (size_t)B * T, nullptr, w->w_dtype).bytes;
+}
+
+extern "C" size_t sd_ecapa_packed_workspace_bytes(const sd_ecapa_weights* w, int B, int M) {
+  if (!w || B <= 0 || M <= 0 || w->res2_scale <= 0) return 0;
+  return carve(w, B, (size_t)M, nullptr, SD_DT_F32).bytes;
+}
+
+extern "C" int sd_ecapa_forward_packed_f32(const sd_ecapa_weights* w, const float* feats, const int* frame_start_dev, int B, int M, float* emb,
+                                           void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
+  SD_CHECK_ARG(w != nullptr, "sd_ecapa_forward_packed_f32: null weights");
+  if (w->w_dtype != SD_DT_F32 || w->split16 != 0)
+    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_ecapa_forward_packed_f32: packed spans run the exact-f32 schedule only (weights: dtype %d, split16 %d)",
+                        w->w_dtype, w->split16);
+  SD_CHECK_ARG(B >= 0, "sd_ecapa_forward_packed_f32: B=%d", B);
+  if (B == 0) return SD_OK;
+  SD_CHECK_ARG(M > 0 && frame_start_dev != nullptr, "sd_ecapa_forward_packed_f32: M=%d, frame_start %p", M, (const void*)frame_start_dev);
+  return forward(w, feats, B, 1, emb, ws_dev, ws_bytes, stream, SD_DT_F32, nullptr, frame_start_dev, M);
 }
 
 extern "C" int sd_ecapa_forward_f32(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb,

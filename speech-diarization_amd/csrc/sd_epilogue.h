@@ -72,8 +72,10 @@ template <> struct SdOut<_Float16> {
 };
 
 // ---- fallback for outputs that cannot take 16-byte stores (cout % 8 != 0 or unaligned slices)
-template <typename TO, int ROWS, int COLS, int NT>
-__device__ __forceinline__ void sd_store_tile_scalar(const sd_conv_args& p, const float* Cs, int ldc, int m0, int n0, int tid) {
+// PACKED (packed spans, sd_hip.h): the per-segment bias row of output row m is its span's, sd_span_of(pk_fs, pk_n, m), instead of m / T
+template <typename TO, int ROWS, int COLS, int NT, bool PACKED = false>
+__device__ __forceinline__ void sd_store_tile_scalar(const sd_conv_args& p, const float* Cs, int ldc, int m0, int n0, int tid,
+                                                     const int* pk_fs = nullptr, int pk_n = 0) {
   constexpr int TPR = COLS / 8;
   constexpr int RPP = NT / TPR;
   TO* const Y = static_cast<TO*>(p.y);
@@ -87,7 +89,7 @@ __device__ __forceinline__ void sd_store_tile_scalar(const sd_conv_args& p, cons
   for (int rr = tid / TPR; rr < ROWS; rr += RPP) {
     const int m = m0 + rr;
     if (m >= p.M) break;
-    const float* sb = p.bias ? (p.bias_per_seg ? p.bias + (size_t)(m / p.T) * p.cout : p.bias) : nullptr;
+    const float* sb = p.bias ? (p.bias_per_seg ? p.bias + (size_t)(PACKED ? sd_span_of(pk_fs, pk_n, m) : m / p.T) * p.cout : p.bias) : nullptr;
 #pragma unroll 1
     for (int e = 0; e < nvalid; ++e) {
       const int n = n8 + e;
@@ -191,15 +193,17 @@ __device__ __forceinline__ void sd_store_rows(const sd_conv_args& p, const float
 // selects such a kernel for a tee_add layer; saves the registers of the prefetched rows).
 // STAT_PARTS: segments a tile may span for the column statistics: 3 (T >= ROWS / 2) or 2 (T >= ROWS: the
 // 256x256 kernel, which has no registers for the third set of accumulators).
-template <typename TO, int ROWS, int COLS, int NT, int TEE_MODE = 2, int STAT_PARTS = 3, bool YSPLIT = false>
-__device__ __forceinline__ void sd_store_tile(const sd_conv_args& p, float* Cs, int ldc, int m0, int n0, int tid, int vec) {
+// PACKED: per-segment bias by span (sd_store_tile_scalar); the host gives such a launch no column statistics
+template <typename TO, int ROWS, int COLS, int NT, int TEE_MODE = 2, int STAT_PARTS = 3, bool YSPLIT = false, bool PACKED = false>
+__device__ __forceinline__ void sd_store_tile(const sd_conv_args& p, float* Cs, int ldc, int m0, int n0, int tid, int vec,
+                                              const int* pk_fs = nullptr, int pk_n = 0) {
   constexpr int TPR = COLS / 8;     // threads per tile row
   constexpr int RPP = NT / TPR;     // rows per pass
   constexpr int PASSES = ROWS / RPP;
   static_assert(ROWS % RPP == 0, "tile rows must be a multiple of the rows covered per pass");
   static_assert(2 * STAT_PARTS * RPP * COLS <= ROWS * COLS, "column statistics are combined inside the C tile");   // (STAT_PARTS = 0: a kernel without them)
   if (!vec) {
-    sd_store_tile_scalar<TO, ROWS, COLS, NT>(p, Cs, ldc, m0, n0, tid);
+    sd_store_tile_scalar<TO, ROWS, COLS, NT, PACKED>(p, Cs, ldc, m0, n0, tid, pk_fs, pk_n);
     return;
   }
   const int nrows = p.M - m0 < ROWS ? p.M - m0 : ROWS;     // rows of this tile that exist
@@ -231,7 +235,8 @@ __device__ __forceinline__ void sd_store_tile(const sd_conv_args& p, float* Cs, 
       SdOut<float>::load8(cr, v);
       if (p.bias_per_seg) {
         float sb[8];
-        SdOut<float>::load8(p.bias + (size_t)((m0 + rr0 + ps * RPP) / p.T) * p.cout + n8, sb);
+        const int m = m0 + rr0 + ps * RPP;
+        SdOut<float>::load8(p.bias + (size_t)(PACKED ? sd_span_of(pk_fs, pk_n, m) : m / p.T) * p.cout + n8, sb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += sb[e];
       }

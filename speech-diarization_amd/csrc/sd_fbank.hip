@@ -116,6 +116,9 @@ struct Fbank2Args {
   int* maxbuf;
   int flat;
   unsigned inv_mels;        // ceil(2^32 / n_mels)
+  // packed spans (the PACKED instantiation only): the spans with n_lo < lens[s] <= n own ceil(T_s / 32) consecutive tiles each from
+  // tile_start[s] on (fbank_packed_tiles_kernel); span s's rows start at row frame_start[s] of out [M][ld_out]
+  const int* lens; const int* frame_start; const int* tile_start; int n_lo; int M;
 };
 
 #define FB2_GLDS16(gptr, lptr)                                                             \
@@ -228,7 +231,11 @@ __device__ __forceinline__ void fbank2_pass(const Fbank2Args& p, const float* xs
   }
 }
 
-__global__ __launch_bounds__(256 * V2_GROUPS, 1) void fbank_logmel_kernel(const Fbank2Args p) {
+// PACKED: the tiles are those of packed spans (Fbank2Args::tile_start), each span's frames tiled from its own frame 0 with its own n:
+// a span's tiles are those of a call for the span alone (one utterance: the flat layout starts a tile every 32 frames of it too)
+template <bool PACKED>
+__global__ __launch_bounds__(256 * V2_GROUPS, 1) void fbank_logmel_kernel(const Fbank2Args p0) {
+  Fbank2Args p = p0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = (tid >> 6) & 3;                     // which of the workgroup's four 32-frame tiles
@@ -242,7 +249,21 @@ __global__ __launch_bounds__(256 * V2_GROUPS, 1) void fbank_logmel_kernel(const 
   const long tile = (long)blockIdx.x * WAVES + wid;
   int bA, tA, nfA, nfB;
   long rowA;
-  if (p.flat) {
+  if constexpr (PACKED) {
+    const int ntiles = p0.tile_start[p0.B];
+    if ((long)blockIdx.x * WAVES >= ntiles) return;          // a workgroup past the last tile: nothing (uniform, before any barrier)
+    const int s = sd_span_of(p0.tile_start, p0.B, (int)tile);
+    const int n = p0.lens[s];
+    const long f0 = p0.frame_start[s];
+    p.n = n; p.T = 1 + n / HOP;
+    bA = s;
+    tA = (int)(tile - p0.tile_start[s]) * FT;
+    nfA = p.T - tA; if (nfA > FT) nfA = FT;
+    nfB = 0;
+    rowA = f0 + tA;
+    // (the other route's span, or rows outside [0, M) under a malformed table: the wave has no frames)
+    if (tile >= ntiles || n <= p0.n_lo || n > p0.n || tA < 0 || nfA <= 0 || f0 < 0 || f0 + p.T > p0.M) nfA = 0;
+  } else if (p.flat) {
     const long g0 = tile * FT;
     const long remaining = BT - g0;
     bA = (int)(g0 / p.T);
@@ -412,18 +433,52 @@ __global__ void fill_i32_kernel(int* p, int n, int v) {
   if (i < n) p[i] = v;
 }
 
+// spans of the folded route (n_lo < lens[s] <= n_hi) -> tile_start [B + 1]: prefix sums of ceil(T_s / 32), every other span 0 tiles.
+// One workgroup: a thread sums a run of consecutive spans, the runs are scanned in LDS.
+__global__ __launch_bounds__(1024) void fbank_packed_tiles_kernel(const int* lens, int B, int n_lo, int n_hi, int* tile_start) {
+  __shared__ int part[1024];
+  const int tid = threadIdx.x;
+  const int per = (B + 1023) / 1024;
+  const int s0 = tid * per < B ? tid * per : B, s1 = s0 + per < B ? s0 + per : B;
+  auto tiles = [&](int s) { const int n = lens[s]; return (n > n_lo && n <= n_hi) ? (1 + n / HOP + FT - 1) / FT : 0; };
+  int sum = 0;
+  for (int s = s0; s < s1; ++s) sum += tiles(s);
+  part[tid] = sum;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int v = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = tid ? part[tid - 1] : 0;
+  for (int s = s0; s < s1; ++s) { tile_start[s] = run; run += tiles(s); }
+  if (tid == 1023) tile_start[B] = part[1023];
+}
+
 // top_db floor (relative to the utterance max) and per-bin mean removal over T.
 // One workgroup per utterance; thread (r, c) walks rows r, r+R, ... of column c.
 // rel_len (NULL: all T): the mean over the first sd_norm_frames(rel_len[b], T) frames, subtracted from all T.
+// PACKED: workgroup b finalizes span b if it is on the folded route (n_lo < lens[b] <= n_hi), with its own T and R = min(R, T) as a call
+// for the span alone has them
+template <bool PACKED>
 __global__ void fbank_finalize_kernel(float* out, int ld_out, int T, int n_mels, const int* maxbuf,
-                                      int use_floor, float top_db, int mean_norm, int R, const float* rel_len) {
+                                      int use_floor, float top_db, int mean_norm, int R, const float* rel_len,
+                                      const int* lens = nullptr, const int* frame_start = nullptr, int n_lo = 0, int n_hi = 0, int M = 0) {
   extern __shared__ float part[];  // [R][n_mels]
   const int b = blockIdx.x;
+  float* base = out + (size_t)b * T * ld_out;
+  if constexpr (PACKED) {
+    const int n = lens[b], f0 = frame_start[b];
+    if (n <= n_lo || n > n_hi || f0 < 0 || f0 > M - (1 + n / HOP)) return;
+    T = 1 + n / HOP;
+    R = R < T ? R : T;
+    base = out + (size_t)f0 * ld_out;
+  }
   const int tid = threadIdx.x;
   const int c = tid % n_mels;
   const int r = tid / n_mels;
   const bool active = r < R;
-  float* base = out + (size_t)b * T * ld_out;
   const int key = maxbuf[b];
   if (key == SD_FB_POISON_KEY) {                      // a NaN sample somewhere in the utterance: NaN features, as the reference's floor / mean would give
     if (active)
@@ -642,20 +697,85 @@ static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long lo
   // replayed from a captured hipGraph did not reproduce the eager result (configs[3] test)
   hipLaunchKernelGGL(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a.maxbuf, B, (int)0x80808080);
   SD_CHECK_LAUNCH("fill_i32_kernel");
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel), V2_LDS_BYTES));
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel<false>), V2_LDS_BYTES));
   {
     // algorithmic bytes: waveform read once + log-mel written once (192 320 B per 2 s segment)
     SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
-    hipLaunchKernelGGL(fbank_logmel_kernel, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(fbank_logmel_kernel<false>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
   }
   SD_CHECK_LAUNCH("fbank_logmel_kernel");
   const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
   {
     int R = 320 / plan->n_mels; if (R < 1) R = 1; if (R > T) R = T;
     int threads = ((R * plan->n_mels + 63) / 64) * 64;
-    hipLaunchKernelGGL(fbank_finalize_kernel, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float),
-                       stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R, rel_len);
+    hipLaunchKernelGGL(fbank_finalize_kernel<false>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float),
+                       stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R, rel_len,
+                       nullptr, nullptr, 0, 0, 0);
     SD_CHECK_LAUNCH("fbank_finalize_kernel");
   }
+  return SD_OK;
+}
+
+static size_t packed_maxbuf_bytes(int B) { return ((size_t)(B > 0 ? B : 0) * sizeof(int) + 255) & ~(size_t)255; }
+
+extern "C" size_t sd_fbank_packed_workspace_bytes(const sd_fbank_plan* plan, int B, int M, int n_max) {
+  (void)plan; (void)M; (void)n_max;       // (the per-span max keys and the tile table: B and B + 1 ints)
+  if (B <= 0) return 0;
+  return packed_maxbuf_bytes(B) + (((size_t)(B + 1) * sizeof(int) + 255) & ~(size_t)255);
+}
+
+// Packed spans ("Packed spans", sd_hip.h): every span takes the route a call for it alone takes -- up to sd_fbank_utt16_max_n samples the
+// one-launch kernel (one workgroup per span, the others idle out), longer ones the folded kernel over their own tiles + the finalize pass.
+// A pack with spans on both routes is two launches (plus the tile table and the max-key reset); each span's rows are bitwise sd_fbank_f32 of
+// the span alone (B = 1, n = lens[s]).
+extern "C" int sd_fbank_packed_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
+                                   const int* lens_dev, const int* frame_start_dev, int B, int M, int n_max,
+                                   float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  SD_CHECK_ARG(plan != nullptr, "sd_fbank_packed_f32: null plan");
+  SD_CHECK_ARG(B >= 0, "sd_fbank_packed_f32: B=%d", B);
+  if (B == 0) return SD_OK;
+  SD_CHECK_ARG(M > 0 && n_max >= 1, "sd_fbank_packed_f32: M=%d n_max=%d", M, n_max);
+  SD_CHECK_ARG(wav_dev && starts_dev && lens_dev && frame_start_dev && out_dev, "sd_fbank_packed_f32: null pointer");
+  SD_CHECK_ARG(n_total >= 4, "sd_fbank_packed_f32: n_total=%lld (at least 4 samples)", n_total);
+  SD_CHECK_ARG(ld_out >= plan->n_mels, "sd_fbank_packed_f32: ld_out=%d < n_mels=%d", ld_out, plan->n_mels);
+  if (plan->generic || plan->pad_mode != SD_PAD_ZERO)
+    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_fbank_packed_f32: packed spans take the 25 ms / 10 ms plan with zero padding (speechbrain)");
+  const size_t need = sd_fbank_packed_workspace_bytes(plan, B, M, n_max);
+  SD_CHECK_ARG(ws_dev && ws_bytes >= need && sd_aligned16(ws_dev), "sd_fbank_packed_f32: workspace %zu < %zu bytes, or unaligned", ws_bytes, need);
+  // every span of the folded route has at most T_s / 32 + 1 tiles: M / 32 + B in all
+  const long blocks = ((long)M / FT + B + WAVES - 1) / WAVES;
+  SD_CHECK_ARG(blocks < (1L << 31) && (long)M / FT + B < (1L << 31), "sd_fbank_packed_f32: grid too large");
+  const int n_split = sd_fbank_utt16_max_n(plan);
+  if (n_split >= 1)
+    if (int e = sd_fbank_utt16_packed_launch(plan, wav_dev, n_total, starts_dev, lens_dev, frame_start_dev, B, M, n_max < n_split ? n_max : n_split,
+                                             out_dev, ld_out, stream))
+      return e;
+  if (n_max <= n_split) return SD_OK;
+  Fbank2Args a = {};
+  a.wav = wav_dev; a.B = B; a.n = n_max; a.T = 1 + n_max / HOP;
+  a.starts = starts_dev; a.n_total = n_total;
+  a.basis = static_cast<const _Float16*>(plan->basis16_dev); a.melw = static_cast<const __bf16*>(plan->melw16_dev);
+  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
+  a.out = out_dev; a.ld_out = ld_out;
+  a.maxbuf = static_cast<int*>(ws_dev);
+  a.flat = 0;
+  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + plan->n_mels - 1) / plan->n_mels);
+  a.lens = lens_dev; a.frame_start = frame_start_dev;
+  a.tile_start = reinterpret_cast<int*>(static_cast<char*>(ws_dev) + packed_maxbuf_bytes(B));
+  a.n_lo = n_split > 0 ? n_split : 0; a.M = M;
+  hipLaunchKernelGGL(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a.maxbuf, B, (int)0x80808080);
+  SD_CHECK_LAUNCH("fill_i32_kernel");
+  hipLaunchKernelGGL(fbank_packed_tiles_kernel, dim3(1), dim3(1024), 0, stream, lens_dev, B, a.n_lo, n_max, const_cast<int*>(a.tile_start));
+  SD_CHECK_LAUNCH("fbank_packed_tiles_kernel");
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel<true>), V2_LDS_BYTES));
+  hipLaunchKernelGGL(fbank_logmel_kernel<true>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
+  SD_CHECK_LAUNCH("fbank_logmel_kernel");
+  const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
+  int R = 320 / plan->n_mels; if (R < 1) R = 1;
+  const int threads = ((R * plan->n_mels + 63) / 64) * 64;
+  hipLaunchKernelGGL(fbank_finalize_kernel<true>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float), stream, out_dev,
+                     ld_out, 1, plan->n_mels, a.maxbuf, use_floor, plan->top_db, 1, R, nullptr, lens_dev, frame_start_dev, a.n_lo, n_max, M);
+  SD_CHECK_LAUNCH("fbank_finalize_kernel");
   return SD_OK;
 }

@@ -33,3 +33,9 @@ void sd_fbank_utt16_destroy_tables(sd_fbank_plan* plan);
 bool sd_fbank_utt16_supported(const sd_fbank_plan* plan, int n);
 int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
                           int mean_norm, float* out_dev, int ld_out, hipStream_t stream, const float* rel_len);
+// the longest utterance the one-launch kernel takes (0: none): the route boundary of packed spans
+int sd_fbank_utt16_max_n(const sd_fbank_plan* plan);
+// packed spans (sd_fbank_packed_f32): one workgroup per span, the spans of at most n_cap samples (n_cap <= sd_fbank_utt16_max_n)
+int sd_fbank_utt16_packed_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
+                                 const int* lens_dev, const int* frame_start_dev, int B, int M, int n_cap, float* out_dev, int ld_out,
+                                 hipStream_t stream);

@@ -87,6 +87,9 @@ struct U16Args {
   const float* rel_len;      // mean_norm: the mean over the first sd_norm_frames(rel_len[b], T) frames (NULL: all T)
   float* out; int ld_out;
   unsigned inv_mels;
+  // packed spans (the PACKED instantiation only): workgroup b takes span b = wav[starts[b] .. + lens[b]) if lens[b] <= n (the host's cap:
+  // the LDS was sized for it), and writes its 1 + lens[b] / 160 rows at row frame_start[b] of out [M][ld_out]; other spans are left alone
+  const int* lens; const int* frame_start; int M;
 };
 
 #ifdef SD_STAMP
@@ -216,7 +219,20 @@ __device__ __forceinline__ void u16_steps2(AddrOf&& addr_of, const unsigned (&yh
   }
 }
 
-__global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Args p) {
+// PACKED: the utterance of a workgroup is one span of the packed layout (U16Args::lens); its own n and T replace the launch's, so the
+// arithmetic is that of a launch for the span alone
+template <bool PACKED>
+__global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Args p0) {
+  U16Args p = p0;
+  size_t out_row = (size_t)blockIdx.x * p0.T;
+  if constexpr (PACKED) {
+    const int n = p0.lens[blockIdx.x];
+    const int f0 = p0.frame_start[blockIdx.x];
+    // the other route's span, or one that does not fit the rows or the LDS of this launch (a malformed table): nothing (uniform)
+    if (n < 1 || n > p0.n || f0 < 0 || f0 > p0.M - (1 + n / HOP)) return;
+    p.n = n; p.T = 1 + n / HOP;
+    out_row = (size_t)f0;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   char* const a2s = smem_raw;                                                        // stage-2 matrix fragments (16 KB); later the column sums
   char* const ring = smem_raw + A2_BYTES;                                            // streamed table fragments: 2 chunks x 8 KB
@@ -597,7 +613,7 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
     }
     __syncthreads();
   }
-  float* const orow = p.out + (size_t)b * p.T * p.ld_out;
+  float* const orow = p.out + out_row * p.ld_out;
   {
     // a NaN sample anywhere in the utterance: the reference's arithmetic carries it into the utterance maximum (top_db floor) and the mean over
     // T, i.e. into every value of the utterance's features.  Here the sample was clamped on its way into the f16 image, so the rows are
@@ -793,12 +809,48 @@ int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long 
   a.out = out_dev; a.ld_out = ld_out;
   const int per_row = plan->n_mels % 4 == 0 ? plan->n_mels / 4 : plan->n_mels;
   a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + per_row - 1) / per_row);
+  a.lens = nullptr; a.frame_start = nullptr; a.M = 0;
   const size_t lds = u16_lds_bytes(n, T);
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel), LDS_LIMIT));
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel<false>), LDS_LIMIT));
   {
     SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
-    hipLaunchKernelGGL(fbank_utt16_kernel, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
+    hipLaunchKernelGGL(fbank_utt16_kernel<false>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
   }
+  SD_CHECK_LAUNCH("fbank_utt16_kernel");
+  return SD_OK;
+}
+
+int sd_fbank_utt16_max_n(const sd_fbank_plan* plan) {
+  if (!sd_fbank_utt16_supported(plan, 1)) return 0;
+  int lo = 1, hi = (U16_MAX_T + 1) * HOP;       // supported(lo); not supported(hi): 1 + hi / 160 frames > U16_MAX_T
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (sd_fbank_utt16_supported(plan, mid)) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+int sd_fbank_utt16_packed_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
+                                 const int* lens_dev, const int* frame_start_dev, int B, int M, int n_cap, float* out_dev, int ld_out,
+                                 hipStream_t stream) {
+  const int T = 1 + n_cap / HOP;
+  U16Args a;
+  a.wav = wav_dev; a.B = B; a.n = n_cap; a.T = T;
+  a.starts = starts_dev; a.n_total = n_total;
+  a.tables = static_cast<const char*>(plan->utt16_tables_dev);
+  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
+  a.top_db = plan->top_db;
+  a.use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
+  a.mean_norm = 1;
+  a.rel_len = nullptr;
+  a.out = out_dev; a.ld_out = ld_out;
+  const int per_row = plan->n_mels % 4 == 0 ? plan->n_mels / 4 : plan->n_mels;
+  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + per_row - 1) / per_row);
+  a.lens = lens_dev; a.frame_start = frame_start_dev; a.M = M;
+  const size_t lds = u16_lds_bytes(n_cap, T);      // (monotone in n: enough for every span the kernel takes, lens[b] <= n_cap)
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel<true>), LDS_LIMIT));
+  hipLaunchKernelGGL(fbank_utt16_kernel<true>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
   SD_CHECK_LAUNCH("fbank_utt16_kernel");
   return SD_OK;
 }

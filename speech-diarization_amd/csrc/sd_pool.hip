@@ -383,6 +383,139 @@ __global__ __launch_bounds__(256) void colstat_finish_kernel(const float* __rest
   if (want_std) out[(size_t)b * 2 * C + C + c] = sqrtf(fmaxf(q * inv - m1 * m1, eps));
 }
 
+// ---- packed spans (sd_hip.h): span s is rows [frame_start[s], frame_start[s + 1]) of the activations, clamped into [0, M) (a malformed
+// table gives wrong numbers, never an access outside the M rows).  The arithmetic of the kernels above with (first row, count) in place of
+// (b T, n_mask), in ONE workgroup shape for every span and batch: a span's statistics depend on its own rows only.
+__device__ __forceinline__ void span_rows(const int* fs, int M, int s, int& r0, int& nt) {
+  int a = fs[s], e = fs[s + 1];
+  a = a < 0 ? 0 : (a > M ? M : a);
+  e = e < a ? a : (e > M ? M : e);
+  r0 = a;
+  nt = e - a;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void seg_mean_std_packed_kernel(const T* x, int ld, int col0, const int* fs, int M, int C, int want_std,
+                                                                  float eps, float* out) {
+  __shared__ f32x4 part[RP * CG];
+  const int b = blockIdx.y;
+  const int cg = threadIdx.x % CG, rp = threadIdx.x / CG;
+  const int c = (blockIdx.x * CG + cg) * 4;
+  const bool ok = c < C;
+  int r0, nt;
+  span_rows(fs, M, b, r0, nt);
+  const T* base = x + (size_t)r0 * ld + col0 + (ok ? c : 0);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int t = rp; t < nt; t += RP) s += ld4(base + (size_t)t * ld);
+  s = combine_sum(part, rp, cg, s);
+  const float invT = 1.0f / (float)nt;
+  const f32x4 mean = s * invT;
+  const int ostride = want_std ? 2 * C : C;
+  if (ok && rp == 0) st4(out + (size_t)b * ostride + c, mean);
+  if (!want_std) return;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int t = rp; t < nt; t += RP) {
+      const f32x4 d = ld4(base + (size_t)t * ld) - mean;
+      v += d * d;
+    }
+  v = combine_sum(part, rp, cg, v);
+  if (ok && rp == 0) {
+    f32x4 sd;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sd[e] = sqrtf(fmaxf(v[e] * invT, eps));
+    st4(out + (size_t)b * ostride + C + c, sd);
+  }
+}
+
+// y = x * gate[span of the row] + res (se_scale_residual_kernel's arithmetic; the span by a search in frame_start per row)
+template <typename T>
+__global__ __launch_bounds__(256) void se_scale_residual_packed_kernel(const T* x, int ldx, const float* gate, const T* res, int ldr, int r_col0,
+                                                                       T* y, int ldy, int y_col0, const int* fs, int B, int M, int C) {
+  constexpr int VEC = 16 / sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
+  const int groups = C / VEC;
+  const int gpr = groups < 256 ? groups : 256;
+  const int rows_per_pass = 256 / gpr;
+  const int tr = threadIdx.x / gpr, tg = threadIdx.x % gpr;
+  if (tr >= rows_per_pass) return;
+  for (int m = blockIdx.x * rows_per_pass + tr; m < M; m += gridDim.x * rows_per_pass) {
+    const float* g = gate + (size_t)sd_span_of(fs, B, m) * C;
+    const T* xr = x + (size_t)m * ldx;
+    const T* rr = res + (size_t)m * ldr + r_col0;
+    T* yr = y + (size_t)m * ldy + y_col0;
+    for (int gq = tg; gq < groups; gq += gpr) {
+      const int c = gq * VEC;
+      const vec_t xv = *reinterpret_cast<const vec_t*>(xr + c);
+      const vec_t rv = *reinterpret_cast<const vec_t*>(rr + c);
+      vec_t o;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) o[e] = (T)((float)xv[e] * g[c + e] + (float)rv[e]);
+      *reinterpret_cast<vec_t*>(yr + c) = o;
+    }
+  }
+}
+
+// attentive statistics pooling over each span's rows (asp_pool_kernel's arithmetic)
+template <typename T>
+__global__ __launch_bounds__(256) void asp_pool_packed_kernel(const T* logit, int ldl, const T* h, int ldh, const int* fs, int M, int C, float eps,
+                                                              float* out) {
+  __shared__ f32x4 part[RP * CG];
+  const int b = blockIdx.y;
+  const int cg = threadIdx.x & (CG - 1), rp = threadIdx.x >> 6;
+  const int c = (blockIdx.x * CG + cg) * 4;
+  const bool ok = c < C;
+  int r0, nt;
+  span_rows(fs, M, b, r0, nt);
+  const T* lb = logit + (size_t)r0 * ldl + (ok ? c : 0);
+  const T* hb = h + (size_t)r0 * ldh + (ok ? c : 0);
+  const float ninf = -INFINITY;
+  f32x4 mx = {ninf, ninf, ninf, ninf};
+  if (ok)
+    for (int t = rp; t < nt; t += RP) {
+      const f32x4 l = ld4(lb + (size_t)t * ldl);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], l[e]);
+    }
+  mx = combine_max(part, rp, cg, mx);
+  f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int t = rp; t < nt; t += RP) {
+      const f32x4 l = ld4(lb + (size_t)t * ldl);
+      const f32x4 hv = ld4(hb + (size_t)t * ldh);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float w = expf(l[e] - mx[e]);
+        den[e] += w;
+        num[e] += w * hv[e];
+      }
+    }
+  den = combine_sum(part, rp, cg, den);
+  num = combine_sum(part, rp, cg, num);
+  const f32x4 mu = num / den;
+  f32x4 var = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int t = rp; t < nt; t += RP) {
+      const f32x4 l = ld4(lb + (size_t)t * ldl);
+      const f32x4 hv = ld4(hb + (size_t)t * ldh);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float w = expf(l[e] - mx[e]);
+        const float d = hv[e] - mu[e];
+        var[e] += w * d * d;
+      }
+    }
+  var = combine_sum(part, rp, cg, var);
+  if (ok && rp == 0) {
+    f32x4 sd;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sd[e] = sqrtf(fmaxf(var[e] / den[e], eps));
+    st4(out + (size_t)b * 2 * C + c, mu);
+    st4(out + (size_t)b * 2 * C + C + c, sd);
+  }
+}
+
 }  // namespace
 
 // f32 -> f16 (round to nearest even), n % 8 == 0 elements, both 16-byte aligned: the features in front of the f16 stem
@@ -549,6 +682,74 @@ extern "C" int sd_asp_pool_lens_dt(const void* logit, int ldl, const void* h, in
   SD_CHECK_LAUNCH("asp_pool_kernel");
   return SD_OK;
 }
+
+// ---- packed spans: the three statistics / gating operators over spans [frame_start[s], frame_start[s + 1]) of M rows
+#define SD_PACKED_SPANS(fn)                                                                                                  \
+  SD_CHECK_ARG(B >= 0 && B < 65536, fn ": B=%d (0 .. 65535)", B);                                                           \
+  if (B == 0) return SD_OK;                                                                                                 \
+  SD_CHECK_ARG(M > 0 && frame_start_dev != nullptr, fn ": M=%d, frame_start %p", M, (const void*)frame_start_dev)
+
+extern "C" int sd_seg_mean_std_packed_dt(const void* x, int x_dtype, int ld, int col0, const int* frame_start_dev, int B, int M, int C,
+                                         int want_std, float eps, float* out, sd_stream_t stream) {
+  SD_PACKED_SPANS("sd_seg_mean_std_packed_dt");
+  if (int e = check_cl_dt("sd_seg_mean_std_packed_dt", x, x_dtype, ld, col0, C)) return e;
+  SD_CHECK_ARG(out && sd_aligned16(out), "sd_seg_mean_std_packed_dt: null or unaligned output");
+  const dim3 grid((C / 4 + CG - 1) / CG, B);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (x_dtype == SD_DT_F16)
+    hipLaunchKernelGGL(seg_mean_std_packed_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, frame_start_dev, M, C,
+                       want_std, eps, out);
+  else
+    hipLaunchKernelGGL(seg_mean_std_packed_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, frame_start_dev, M, C,
+                       want_std, eps, out);
+  SD_CHECK_LAUNCH("seg_mean_std_packed_kernel");
+  return SD_OK;
+}
+
+extern "C" int sd_se_scale_residual_packed_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy,
+                                              int y_col0, const int* frame_start_dev, int B, int M, int C, int dtype, sd_stream_t stream) {
+  SD_PACKED_SPANS("sd_se_scale_residual_packed_dt");
+  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(x)", x, dtype, ldx, 0, C)) return e;
+  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(res)", res, dtype, ldr, r_col0, C)) return e;
+  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(y)", y, dtype, ldy, y_col0, C)) return e;
+  SD_CHECK_ARG(gate && sd_aligned16(gate), "sd_se_scale_residual_packed_dt: null or unaligned gate");
+  const int vec = dtype == SD_DT_F16 ? 8 : 4;
+  SD_CHECK_ARG(C % vec == 0 && ldx % vec == 0 && ldr % vec == 0 && ldy % vec == 0 && r_col0 % vec == 0 && y_col0 % vec == 0,
+               "sd_se_scale_residual_packed_dt: C / strides / column offsets must be multiples of %d", vec);
+  SD_CHECK_ARG(sd_aligned16(x) && sd_aligned16(res) && sd_aligned16(y), "sd_se_scale_residual_packed_dt: x / res / y must be 16-byte aligned");
+  const int groups = C / vec;
+  const int rpp = 256 / (groups < 256 ? groups : 256);
+  long blocks = ((long)M + rpp - 1) / rpp;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == SD_DT_F16)
+    hipLaunchKernelGGL(se_scale_residual_packed_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(x), ldx, gate,
+                       static_cast<const _Float16*>(res), ldr, r_col0, static_cast<_Float16*>(y), ldy, y_col0, frame_start_dev, B, M, C);
+  else
+    hipLaunchKernelGGL(se_scale_residual_packed_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(x), ldx, gate,
+                       static_cast<const float*>(res), ldr, r_col0, static_cast<float*>(y), ldy, y_col0, frame_start_dev, B, M, C);
+  SD_CHECK_LAUNCH("se_scale_residual_packed_kernel");
+  return SD_OK;
+}
+
+extern "C" int sd_asp_pool_packed_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, const int* frame_start_dev, int B, int M, int C,
+                                     float eps, float* out, sd_stream_t stream) {
+  SD_PACKED_SPANS("sd_asp_pool_packed_dt");
+  if (int e = check_cl_dt("sd_asp_pool_packed_dt(logit)", logit, dtype, ldl, 0, C)) return e;
+  if (int e = check_cl_dt("sd_asp_pool_packed_dt(h)", h, dtype, ldh, 0, C)) return e;
+  SD_CHECK_ARG(out && sd_aligned16(out), "sd_asp_pool_packed_dt: null or unaligned output");
+  const dim3 grid((C / 4 + CG - 1) / CG, B);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == SD_DT_F16)
+    hipLaunchKernelGGL(asp_pool_packed_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(logit), ldl,
+                       static_cast<const _Float16*>(h), ldh, frame_start_dev, M, C, eps, out);
+  else
+    hipLaunchKernelGGL(asp_pool_packed_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(logit), ldl, static_cast<const float*>(h), ldh,
+                       frame_start_dev, M, C, eps, out);
+  SD_CHECK_LAUNCH("asp_pool_packed_kernel");
+  return SD_OK;
+}
+#undef SD_PACKED_SPANS
 
 __global__ __launch_bounds__(256) void wav_lens_frames_kernel(const float* rel_len, int B, int T, int* n_norm, int* n_mask) {
   const int b = blockIdx.x * 256 + threadIdx.x;

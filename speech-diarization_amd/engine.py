@@ -36,6 +36,62 @@ def min_samples(cfg: EcapaConfig) -> int:
     return (min_frames(cfg) - 1) * HOP
 
 
+SPAN_BUDGET_FRAMES = 201   # default frame budget of a packed micro-batch: this many frames (one 2 s segment) per max_batch
+
+
+def span_frame_offsets(lengths) -> np.ndarray:
+    """Packed spans (include/sd_hip.h): span s of n_s samples has T_s = 1 + n_s // 160 frames, stored back to back in span order.
+    -> frame_start int32 [B + 1]: frame_start[s] = sum of T_r over r < s, frame_start[B] = M, the rows of the pack."""
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    out = np.zeros(n.size + 1, np.int64)
+    np.cumsum(1 + n // HOP, out=out[1:])
+    if out[-1] >= 2 ** 31:
+        raise ValueError(f"packed spans: {int(out[-1])} frames do not fit one launch (at most 2^31 - 1)")
+    return out.astype(np.int32)
+
+
+def plan_span_batches(frames, budget: int) -> list:
+    """Micro-batches of packed spans: consecutive runs [lo, hi) in span order whose frames add up to at most `budget`; a span is never
+    split, and one longer than the budget goes alone."""
+    out, lo, acc = [], 0, 0
+    for i, f in enumerate(int(x) for x in frames):
+        if i > lo and acc + f > budget:
+            out.append((lo, i))
+            lo, acc = i, 0
+        acc += f
+    if len(frames) > lo:
+        out.append((lo, len(frames)))
+    return out
+
+
+def check_spans(starts, lengths, n_total: int, min_samples_: int, min_frames_: int):
+    """Host validation of packed spans, before anything is launched -> (starts int64 [B], lengths int64 [B]).  Every span must lie
+    inside the signal (no zero fill: `embed_windows` does that) and have at least `min_samples_` samples (the network's floor)."""
+    def ints(v, what):
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.ndim != 1:
+            raise ValueError(f"{what} must be a 1-d integer array, got shape {a.shape}")
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{what} must be integers, got {a.dtype}")
+        return a.astype(np.int64)
+    st, ln = ints(starts, "starts"), ints(lengths, "lengths")
+    if st.shape != ln.shape:
+        raise ValueError(f"starts and lengths differ in length: {st.size} != {ln.size}")
+    if st.size == 0:
+        return st, ln
+    if (st < 0).any():
+        raise ValueError(f"span {int(np.argmax(st < 0))} starts at {int(st[st < 0][0])}: starts must be >= 0")
+    short = ln < min_samples_
+    if short.any():
+        raise ValueError(f"segment of {int(ln[short][0])} samples is too short: ECAPA's reflect padding needs at least "
+                         f"{min_frames_} frames ({min_samples_} samples)")
+    past = st + ln > n_total
+    if past.any():
+        i = int(np.argmax(past))
+        raise ValueError(f"span {i} = [{int(st[i])}, {int(st[i] + ln[i])}) runs past the end of the signal ({n_total} samples)")
+    return st, ln
+
+
 def _np(x) -> np.ndarray:
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
@@ -220,8 +276,15 @@ class EmbeddingEngine:
     def _workspace(self, B: int, n: int):
         T = FbankPlan.num_frames(n)
         n_mels = self.weights.cfg.input_size
-        need = (B * T * n_mels * 4, max(self.plan.workspace_bytes(B, n), 256),
-                int(self._lib.sd_ecapa_workspace_bytes(C.byref(self.weights.struct), B, T)))
+        return self._grow((B * T * n_mels * 4, max(self.plan.workspace_bytes(B, n), 256),
+                           int(self._lib.sd_ecapa_workspace_bytes(C.byref(self.weights.struct), B, T))))
+
+    def _packed_workspace(self, B: int, M: int, n_max: int):
+        n_mels = self.weights.cfg.input_size
+        return self._grow((M * n_mels * 4, max(int(self._lib.sd_fbank_packed_workspace_bytes(self.plan.handle, B, M, n_max)), 256),
+                           int(self._lib.sd_ecapa_packed_workspace_bytes(C.byref(self.weights.struct), B, M))))
+
+    def _grow(self, need):
         if self._ws is None:
             self._ws = [None, None, None]
         for i, nbytes in enumerate(need):
@@ -326,6 +389,53 @@ class EmbeddingEngine:
                                       ec_ws.data_ptr(), ec_ws.numel(), stream), f"sd_ecapa_forward_{self.precision}")
         return out
 
+    def embed_spans(self, signal: torch.Tensor, starts, lengths, frame_budget: int | None = None) -> torch.Tensor:
+        """Embeddings of the B spans `signal[starts[s] : starts[s] + lengths[s]]` of ONE recording, each as if it were embedded alone
+        (`embed(span[None])` up to f32 rounding), with no padding to the longest: the spans' frames are packed back to back
+        (`sd_fbank_packed_f32` + `sd_ecapa_forward_packed_f32`, include/sd_hip.h "Packed spans").  Exact f32 only.
+        signal: f32 [n_total] on this engine's device; starts, lengths: integer arrays [B] (host or device) -> f32 [B, dim] on the
+        device.  Micro-batches of consecutive spans up to `frame_budget` frames (default max_batch x 201); a span is never split.
+        Everything is validated before the first launch."""
+        if self.precision != "f32":
+            raise NotImplementedError(f"embed_spans runs the exact-f32 schedule only (precision 'f32'); this engine is {self.precision!r}")
+        if not isinstance(signal, torch.Tensor) or signal.dim() != 1 or signal.dtype != torch.float32:
+            raise ValueError("signal must be a 1-d f32 tensor")
+        if signal.device != self.device:
+            raise ValueError(f"signal is on {signal.device}, engine on {self.device}")
+        st, ln = check_spans(starts, lengths, int(signal.numel()), self.min_samples, min_frames(self.weights.cfg))
+        budget = self.max_batch * SPAN_BUDGET_FRAMES if frame_budget is None else int(frame_budget)
+        if budget < 1:
+            raise ValueError(f"frame_budget must be positive, got {frame_budget}")
+        B = int(st.size)
+        out = torch.empty((B, self.dim), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return out
+        signal = signal.contiguous()
+        frames = 1 + ln // HOP
+        batches = plan_span_batches(frames, budget)
+        # one upload of every table: starts, lengths and each micro-batch's own frame offsets (from 0) back to back
+        offs = [span_frame_offsets(ln[lo:hi]) for lo, hi in batches]
+        fs_at = np.concatenate([[0], np.cumsum([o.size for o in offs])])
+        host = torch.from_numpy(np.concatenate([st, ln, np.concatenate(offs)]).astype(np.int64))
+        tab = host.to(self.device)
+        st_d = tab[:B]
+        ln_d = tab[B:2 * B].to(torch.int32)
+        fs_d = tab[2 * B:].to(torch.int32)
+        n_mels = self.weights.cfg.input_size
+        W = C.byref(self.weights.struct)
+        with self._lock, torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for (lo, hi), o, f0 in zip(batches, offs, fs_at[:-1]):
+                nb, M, n_max = hi - lo, int(o[-1]), int(ln[lo:hi].max())
+                feats, fb_ws, ec_ws = self._packed_workspace(nb, M, n_max)
+                fs = fs_d[int(f0):int(f0) + nb + 1]
+                N.check(self._lib.sd_fbank_packed_f32(self.plan.handle, signal.data_ptr(), signal.numel(), st_d[lo:hi].data_ptr(),
+                                                      ln_d[lo:hi].data_ptr(), fs.data_ptr(), nb, M, n_max, feats.data_ptr(), n_mels,
+                                                      fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_packed_f32")
+                N.check(self._lib.sd_ecapa_forward_packed_f32(W, feats.data_ptr(), fs.data_ptr(), nb, M, out[lo:hi].data_ptr(),
+                                                              ec_ws.data_ptr(), ec_ws.numel(), stream), "sd_ecapa_forward_packed_f32")
+        return out
+
     def features(self, wav: torch.Tensor) -> torch.Tensor:
         """The mean-normalised fbank the network consumes, [B, T, n_mels] (diagnostics / tests)."""
         wav = wav.contiguous().float()
@@ -350,6 +460,31 @@ def fbank_windows_device(signal: torch.Tensor, starts: torch.Tensor, n: int, pla
         stream = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
         N.check(lib.sd_fbank_windows_f32(plan.handle, signal.data_ptr(), signal.numel(), starts.data_ptr(), B, int(n), int(bool(mean_norm)),
                                          out.data_ptr(), plan.n_mels, ws.data_ptr(), ws.numel(), stream), "sd_fbank_windows_f32")
+    return out
+
+
+def fbank_packed_device(signal: torch.Tensor, starts, lengths, plan: FbankPlan) -> torch.Tensor:
+    """HIP fbank (mean-normalised) of the packed spans signal[starts[s] : starts[s] + lengths[s]] of one device-resident recording
+    -> [M, n_mels], span s at rows frame_start[s] .. frame_start[s + 1] (`span_frame_offsets`)."""
+    if signal.dim() != 1 or signal.device.type != "cuda":
+        raise RuntimeError("fbank_packed_device needs a 1-d GPU tensor; there is no CPU fallback")
+    lib = N.load()
+    signal = signal.contiguous().float()
+    st, ln = check_spans(starts, lengths, int(signal.numel()), 1, 1)
+    fs = span_frame_offsets(ln)
+    B, M = int(st.size), int(fs[-1])
+    out = torch.empty((M, plan.n_mels), dtype=torch.float32, device=signal.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(signal.device):
+        st_d = torch.from_numpy(st).to(signal.device)
+        ln_d = torch.from_numpy(ln.astype(np.int32)).to(signal.device)
+        fs_d = torch.from_numpy(fs).to(signal.device)
+        n_max = int(ln.max())
+        ws = torch.empty((max(int(lib.sd_fbank_packed_workspace_bytes(plan.handle, B, M, n_max)), 256),), dtype=torch.uint8, device=signal.device)
+        stream = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
+        N.check(lib.sd_fbank_packed_f32(plan.handle, signal.data_ptr(), signal.numel(), st_d.data_ptr(), ln_d.data_ptr(), fs_d.data_ptr(), B, M,
+                                        n_max, out.data_ptr(), plan.n_mels, ws.data_ptr(), ws.numel(), stream), "sd_fbank_packed_f32")
     return out
 
 

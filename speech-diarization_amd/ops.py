@@ -90,6 +90,78 @@ def conv1d_cl(x: torch.Tensor, w_packed: torch.Tensor, T: int, *, cin: int, dil:
     return out
 
 
+def _span_table(frame_start, device) -> tuple[torch.Tensor, int]:
+    fs = frame_start.to(device, dtype=torch.int32).contiguous() if isinstance(frame_start, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(frame_start, dtype=np.int32)).to(device)
+    return fs, int(fs.numel()) - 1
+
+
+def conv1d_cl_packed(x: torch.Tensor, w_packed: torch.Tensor, frame_start, *, cin: int, dil: int = 1, bias=None, bias_per_seg=False,
+                     act=None, scale=None, shift=None, act2=None, a_col0: int = 0, out: torch.Tensor | None = None, o_col0: int = 0,
+                     tee: torch.Tensor | None = None, tee_lo: int = 0, tee_hi: int = 0, tee_add: torch.Tensor | None = None,
+                     ta_col0: int = 0) -> torch.Tensor:
+    """`conv1d_cl` (exact f32) over packed spans: rows frame_start[s] .. frame_start[s + 1] of x are span s, the reflect padding and a
+    per-segment bias (bias [B, cout]) are the span's (`sd_conv1d_cl_packed_f32`)."""
+    _need_cuda(x, w_packed, bias, scale, shift, out, tee, tee_add)
+    cout, taps, cin_pad = w_packed.shape
+    M = x.shape[0]
+    fs, B = _span_table(frame_start, x.device)
+    if out is None:
+        out = torch.empty((M, cout), dtype=torch.float32, device=x.device)
+    a = N.sd_conv_args()
+    a.x, a.lda, a.a_col0, a.x_dtype = x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype)
+    a.w, a.w_dtype = w_packed.data_ptr(), _dt(w_packed.dtype)
+    a.y, a.ldo, a.o_col0, a.y_dtype = out.data_ptr(), out.stride(0), o_col0, _dt(out.dtype)
+    a.M, a.T = M, M
+    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cin_pad, cout, taps, dil
+    a.bias, a.bias_per_seg = _ptr(bias), int(bool(bias_per_seg))
+    a.act, a.act2 = _ACT[act], _ACT[act2]
+    a.scale, a.shift = _ptr(scale), _ptr(shift)
+    if tee is not None:
+        a.tee, a.ldt, a.tee_lo, a.tee_hi = tee.data_ptr(), tee.stride(0), tee_lo, tee_hi
+        if tee_add is not None:
+            a.tee_add, a.ld_ta, a.ta_col0 = tee_add.data_ptr(), tee_add.stride(0), ta_col0
+    with torch.cuda.device(x.device):
+        N.check(N.load().sd_conv1d_cl_packed_f32(C.byref(a), fs.data_ptr(), B, _stream(x)), "sd_conv1d_cl_packed_f32")
+    return out
+
+
+def seg_mean_std_packed(x: torch.Tensor, frame_start, want_std: bool = True, eps: float = 1e-12) -> torch.Tensor:
+    """Per-span mean (and std) of x [M, C] over rows frame_start[s] .. frame_start[s + 1] -> f32 [B, C] or [B, 2C]."""
+    _need_cuda(x)
+    fs, B = _span_table(frame_start, x.device)
+    C_ = x.shape[1]
+    out = torch.empty((B, (2 if want_std else 1) * C_), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        N.check(N.load().sd_seg_mean_std_packed_dt(x.data_ptr(), _dt(x.dtype), x.stride(0), 0, fs.data_ptr(), B, x.shape[0], C_,
+                                                   int(bool(want_std)), C.c_float(eps), out.data_ptr(), _stream(x)), "sd_seg_mean_std_packed_dt")
+    return out
+
+
+def se_scale_residual_packed(x: torch.Tensor, gate: torch.Tensor, res: torch.Tensor, frame_start) -> torch.Tensor:
+    """y[m] = x[m] * gate[span of m] + res[m] over packed spans."""
+    _need_cuda(x, gate, res)
+    fs, B = _span_table(frame_start, x.device)
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        N.check(N.load().sd_se_scale_residual_packed_dt(x.data_ptr(), x.stride(0), gate.data_ptr(), res.data_ptr(), res.stride(0), 0,
+                                                        y.data_ptr(), y.stride(0), 0, fs.data_ptr(), B, x.shape[0], x.shape[1], _dt(x.dtype),
+                                                        _stream(x)), "sd_se_scale_residual_packed_dt")
+    return y
+
+
+def asp_pool_packed(logit: torch.Tensor, h: torch.Tensor, frame_start, eps: float = 1e-12) -> torch.Tensor:
+    """Attentive statistics pooling (softmax over each span's rows) over packed spans -> f32 [B, 2C]."""
+    _need_cuda(logit, h)
+    fs, B = _span_table(frame_start, h.device)
+    C_ = h.shape[1]
+    out = torch.empty((B, 2 * C_), dtype=torch.float32, device=h.device)
+    with torch.cuda.device(h.device):
+        N.check(N.load().sd_asp_pool_packed_dt(logit.data_ptr(), logit.stride(0), h.data_ptr(), _dt(h.dtype), h.stride(0), fs.data_ptr(), B,
+                                               h.shape[0], C_, C.c_float(eps), out.data_ptr(), _stream(h)), "sd_asp_pool_packed_dt")
+    return out
+
+
 def seg_gemm(x: torch.Tensor, w_packed: torch.Tensor, *, cin: int, bias=None, act=None, scale=None, shift=None, act2=None,
              out: torch.Tensor | None = None, scratch: torch.Tensor | None = None) -> torch.Tensor:
     """A per-segment layer (one row per segment: SE squeeze FC, global-context bias, final FC) through `sd_seg_gemm_f32`: with `scratch`

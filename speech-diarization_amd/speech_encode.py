@@ -262,6 +262,35 @@ class HipEcapaEncoder:
         out = torch.cat(parts) if parts else torch.empty((0, self.embedding_dim), dtype=torch.float32, device=self.device)
         return out.cpu().numpy() if to_host else out
 
+    @torch.inference_mode()
+    def encode_spans(self, signal, starts, lengths, to_host: bool = True, frame_budget: int | None = None):
+        """Embeddings [B, 192] of the spans `signal[starts[s] : starts[s] + lengths[s]]` of one recording, each as if embedded alone
+        (what the reference's per-segment loop computes, [REF diar_diag.py:341-350]), in packed launches with no padding
+        (`EmbeddingEngine.embed_spans`; exact f32 only).  ONE upload of the signal.  signal: 1-d float array or tensor (host or
+        device); starts, lengths: integer arrays."""
+        sig = signal if isinstance(signal, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32))
+        if sig.dim() != 1:
+            raise ValueError(f"signal must be 1-d, got shape {tuple(sig.shape)}")
+        sig = sig.to(self.device, dtype=torch.float32, non_blocking=True)
+        out = self.engine.embed_spans(sig, starts, lengths, frame_budget=frame_budget)
+        return out.cpu().numpy() if to_host else out
+
+    @torch.inference_mode()
+    def encode_list(self, wavs, to_host: bool = True):
+        """Embeddings [N, 192] of a list of 1-d waveforms (arrays or tensors) of any lengths, each as if embedded alone: they are
+        concatenated into one buffer, uploaded once and embedded as packed spans (`encode_spans`)."""
+        parts = []
+        for i, w in enumerate(wavs):
+            t = w.detach() if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+            if t.dim() != 1:
+                raise ValueError(f"wavs[{i}] must be 1-d, got shape {tuple(t.shape)}")
+            parts.append(t.to(dtype=torch.float32))
+        lengths = np.array([p.numel() for p in parts], np.int64)
+        starts = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64) if parts else lengths
+        on_dev = bool(parts) and all(p.device == self.device for p in parts)
+        sig = torch.cat(parts) if on_dev else torch.cat([p.cpu() for p in parts]) if parts else torch.zeros(0)
+        return self.encode_spans(sig, starts, lengths, to_host=to_host)
+
 
 @lru_cache(maxsize=1)
 def using_ecapa_encoder(device: str | int = "cuda") -> HipEcapaEncoder:
@@ -276,6 +305,11 @@ def ecapa_encode_batch(wavs: np.ndarray) -> np.ndarray:
         x = torch.from_numpy(np.ascontiguousarray(wavs)).float()
         y = encoder.encode_batch(x).squeeze(1).cpu().numpy()
     return y  # [B, 192]
+
+
+def ecapa_encode_list(wavs) -> np.ndarray:
+    """One embedding per waveform of a list of any lengths, each as if embedded alone (`HipEcapaEncoder.encode_list`) -> [N, 192]."""
+    return using_ecapa_encoder().encode_list(wavs)
 
 
 def ecapa_encode_batches(batches, lanes: int = 2) -> list:
