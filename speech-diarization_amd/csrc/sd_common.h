@@ -25,9 +25,41 @@ int sd_cast_f32_f16(const float* x, long n, void* y, sd_stream_t stream);       
 int sd_asp_attend_pool_scaled(const void* a1, const void* wc, const void* h, int dtype, int ldh, int B, int T, int C, int att, float eps,
                               float w_scale, float* out, sd_stream_t stream,
                               const float* rel_len = nullptr);   // sd_asp_fused.hip: sd_asp_attend_pool_lens_dt with the split weights' 2^s
-int sd_se_scale_residual_split(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy, int y_col0,
-                               int B, int T, int C, int dtype, void* ys, int lds, int s_col0, sd_stream_t stream,
-                               const void* res_split, int ld_rs, int rs_col0, int write_y);   // sd_pool.hip
+
+// The segment map of [M][ld] activations: which rows are segment s (0 <= s < B).
+//   uniform: rows s T .. s T + T (M = B T); with rel_len (device f32 [B]) only the first sd_mask_frames(rel_len[s], T) of them count
+//   packed:  rows span[s] .. span[s + 1] of M in all ("Packed spans", sd_hip.h)
+// The per-segment operators of sd_pool.hip and the ECAPA forward take this one description.
+struct SdSegs {
+  bool packed;
+  int B;
+  int T;                      // uniform
+  const float* rel_len;       // uniform, may be null
+  const int* span;            // packed: frame_start, device int32 [B + 1]
+  int M;                      // packed
+};
+inline SdSegs sd_uniform_segs(int B, int T, const float* rel_len = nullptr) { return {false, B, T, rel_len, nullptr, 0}; }
+inline SdSegs sd_packed_segs(const int* frame_start, int B, int M) { return {true, B, 0, nullptr, frame_start, M}; }
+// sd_pool.hip: the launchers behind sd_seg_mean_std_*, sd_se_scale_residual_* (plus the SD_DT_SPLIT16 twin arguments of the f32-split16x3
+// schedule) and sd_asp_pool_*
+int sd_seg_mean_std(const void* x, int dtype, int ld, int col0, const SdSegs& sg, int C, int want_std, float eps, float* out, sd_stream_t stream);
+int sd_se_scale_residual(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy, int y_col0,
+                         const SdSegs& sg, int C, int dtype, sd_stream_t stream, void* ys = nullptr, int lds = 0, int s_col0 = 0,
+                         const void* res_split = nullptr, int ld_rs = 0, int rs_col0 = 0, int write_y = 1);
+int sd_asp_pool(const void* logit, int ldl, const void* h, int dtype, int ldh, const SdSegs& sg, int C, float eps, float* out, sd_stream_t stream);
+
+// sd_conv_gemm.hip: the argument rules every conv operator shares (sd_conv_args, sd_hip.h).  On SD_OK *vec says whether the 16-byte
+// epilogue stores apply.  The operator checks its own dtypes first and its grid after.
+struct SdConvRule {
+  const char* fn;             // the entry's name, for messages
+  int gran;                   // value granularity of cin / lda / a_col0: 4, 8; 32 for the wide split form (whose operand is cin_pad wide)
+  int kpad;                   // cin_pad granularity
+  int store;                  // store granularity of the vector epilogue (ldo, o_col0, ldt, ld_ta, ta_col0): 4 exact f32, 8 f16 / split
+  bool packed;                // packed spans: neither M % T nor the reflect check (a->T is ignored)
+  bool tee_add;               // the kernel has the tee_add epilogue
+  int colstat_T;              // column statistics need T >= this (64, 128); 0: refused (SD_ERR_UNSUPPORTED)
+};
+int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec);
 
 #define SD_CHECK_ARG(cond, ...)                            \
   do {                                                     \

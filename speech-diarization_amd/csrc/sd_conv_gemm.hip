@@ -1130,41 +1130,54 @@ int sd_conv1d_cl_f32_rows(const sd_conv_args* a, sd_stream_t stream, int* stat_r
 // twice (as is and transposed).  Internal (sd_common.h): the affinity's full-matrix call.
 int sd_conv1d_cl_f32_symmetric(const sd_conv_args* a, sd_stream_t stream) { return conv1d_cl_f32_impl(a, stream, true); }
 
+int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec) {
+  const char* fn = r.fn;
+  SD_CHECK_ARG(a != nullptr, "%s: null args", fn);
+  SD_CHECK_ARG(a->x && a->w && a->y, "%s: null x/w/y", fn);
+  if (r.packed) SD_CHECK_ARG(a->M > 0, "%s: M=%d", fn, a->M);
+  else SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "%s: M=%d must be a positive multiple of T=%d", fn, a->M, a->T);
+  const int width = r.gran == 32 ? a->cin_pad : a->cin;      // the value columns the kernel reads from each row
+  SD_CHECK_ARG(a->cin > 0 && width % r.gran == 0, "%s: cin=%d (cin_pad=%d) must be a positive multiple of %d", fn, a->cin, a->cin_pad, r.gran);
+  SD_CHECK_ARG(a->cin_pad >= a->cin && a->cin_pad % r.kpad == 0, "%s: cin_pad=%d must be >= cin and a multiple of %d", fn, a->cin_pad, r.kpad);
+  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "%s: cout=%d taps=%d (odd) dil=%d", fn, a->cout, a->taps, a->dil);
+  if (!r.packed)
+    SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "%s: reflect padding %d needs T > pad (T=%d)", fn, (a->taps / 2) * a->dil, a->T);
+  SD_CHECK_ARG(a->lda % r.gran == 0 && a->a_col0 % r.gran == 0 && a->a_col0 >= 0 && a->a_col0 + width <= a->lda,
+               "%s: lda=%d a_col0=%d width=%d (need multiples of %d, slice inside row)", fn, a->lda, a->a_col0, width, r.gran);
+  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "%s: output slice outside row (ldo=%d o_col0=%d cout=%d)", fn, a->ldo, a->o_col0, a->cout);
+  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "%s: x and w must be 16-byte aligned", fn);
+  SD_CHECK_ARG(r.tee_add || !(a->tee && a->tee_add), "%s: the tee_add epilogue is not available on this kernel", fn);
+  if (a->tee) {
+    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
+                 "%s: bad tee range [%d,%d) ldt=%d", fn, a->tee_lo, a->tee_hi, a->ldt);
+    if (a->tee_add)
+      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "%s: tee_add slice outside row", fn);
+  }
+  // 16-byte epilogue stores: groups of 8 output columns, every touched row slice aligned
+  const int g = r.store;
+  int v = a->cout % 8 == 0 && a->ldo % g == 0 && a->o_col0 % g == 0 && sd_aligned16(a->y);
+  v = v && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);   // null is aligned
+  if (a->tee) {
+    v = v && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % g == 0 && sd_aligned16(a->tee);
+    if (a->tee_add) v = v && a->ld_ta % g == 0 && a->ta_col0 % g == 0 && sd_aligned16(a->tee_add);
+  }
+  if (a->colstat) {
+    if (!r.colstat_T) return sd_set_error(SD_ERR_UNSUPPORTED, "%s: no column statistics on this kernel", fn);
+    const bool simple = (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg;
+    if (!(v && simple && a->T >= r.colstat_T && a->cout % 256 == 0 && !a->tee))
+      return sd_set_error(SD_ERR_UNSUPPORTED, "%s: colstat needs T >= %d, cout %% 256 == 0, relu/identity, per-channel bias, "
+                          "aligned slices and no tee (T=%d cout=%d act=%d/%d)", fn, r.colstat_T, a->T, a->cout, a->act, a->act2);
+  }
+  *vec = v;
+  return SD_OK;
+}
+
 static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool symmetric, int* stat_rows) {
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f32: null args");
   SD_CHECK_ARG(a->w_dtype == SD_DT_F32, "sd_conv1d_cl_f32: w_dtype %d not supported by the f32 operator", a->w_dtype);
-  SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_f32: null x/w/y");
   SD_CHECK_ARG(a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_f32: x/y must be f32 (use sd_conv1d_cl_f16 for f16 activations)");
-  SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "sd_conv1d_cl_f32: M=%d must be a positive multiple of T=%d", a->M, a->T);
-  SD_CHECK_ARG(a->cin > 0 && a->cin % 4 == 0, "sd_conv1d_cl_f32: cin=%d must be a positive multiple of 4", a->cin);
-  SD_CHECK_ARG(a->cin_pad >= a->cin && a->cin_pad % BK == 0, "sd_conv1d_cl_f32: cin_pad=%d must be >= cin and a multiple of %d", a->cin_pad, BK);
-  SD_CHECK_ARG(a->cout > 0, "sd_conv1d_cl_f32: cout=%d", a->cout);
-  SD_CHECK_ARG(a->taps >= 1 && (a->taps & 1), "sd_conv1d_cl_f32: taps=%d must be odd", a->taps);
-  SD_CHECK_ARG(a->dil >= 1, "sd_conv1d_cl_f32: dil=%d", a->dil);
-  SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_f32: reflect padding %d needs T > pad (T=%d)", (a->taps / 2) * a->dil, a->T);
-  SD_CHECK_ARG(a->lda % 4 == 0 && a->a_col0 % 4 == 0 && a->a_col0 + a->cin <= a->lda,
-               "sd_conv1d_cl_f32: lda=%d a_col0=%d cin=%d (need multiples of 4, slice inside row)", a->lda, a->a_col0, a->cin);
-  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_f32: output slice outside row (ldo=%d o_col0=%d cout=%d)", a->ldo, a->o_col0, a->cout);
-  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "sd_conv1d_cl_f32: x and w must be 16-byte aligned");
-  if (a->tee) {
-    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
-                 "sd_conv1d_cl_f32: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
-    if (a->tee_add)
-      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "sd_conv1d_cl_f32: tee_add slice outside row");
-  }
-  // 16-byte epilogue stores need every touched row slice 16-byte aligned
-  int vec = a->cout % 8 == 0 && a->ldo % 4 == 0 && a->o_col0 % 4 == 0 && sd_aligned16(a->y);
-  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);   // null is aligned
-  if (a->tee) {
-    vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 4 == 0 && sd_aligned16(a->tee);
-    if (a->tee_add) vec = vec && a->ld_ta % 4 == 0 && a->ta_col0 % 4 == 0 && sd_aligned16(a->tee_add);
-  }
-  if (a->colstat) {
-    const bool simple = (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg;
-    if (!(vec && simple && a->T >= 64 && a->cout % 256 == 0 && !a->tee))
-      return sd_set_error(SD_ERR_UNSUPPORTED, "sd_conv1d_cl_f32: colstat needs T >= 64, cout %% 256 == 0, relu/identity, per-channel bias, "
-                          "aligned slices and no tee (T=%d cout=%d act=%d/%d)", a->T, a->cout, a->act, a->act2);
-  }
+  int vec;
+  if (int e = sd_check_conv(a, {"sd_conv1d_cl_f32", 4, BK, 4, false, true, 64}, &vec)) return e;
   const long tiles_m = (a->M + BM - 1) / BM;
   const long tiles_n = (a->cout + BN - 1) / BN;
   SD_CHECK_ARG(tiles_m * tiles_n < (1L << 31), "sd_conv1d_cl_f32: grid too large");
@@ -1314,28 +1327,8 @@ extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_s
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_packed_f32: null args");
   SD_CHECK_ARG(B >= 1 && frame_start_dev != nullptr, "sd_conv1d_cl_packed_f32: B=%d, frame_start %p", B, (const void*)frame_start_dev);
   SD_CHECK_ARG(a->w_dtype == SD_DT_F32 && a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_packed_f32: x / w / y must be f32");
-  SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_packed_f32: null x/w/y");
-  SD_CHECK_ARG(a->M > 0, "sd_conv1d_cl_packed_f32: M=%d", a->M);
-  SD_CHECK_ARG(a->cin > 0 && a->cin % 4 == 0, "sd_conv1d_cl_packed_f32: cin=%d must be a positive multiple of 4", a->cin);
-  SD_CHECK_ARG(a->cin_pad >= a->cin && a->cin_pad % BK == 0, "sd_conv1d_cl_packed_f32: cin_pad=%d must be >= cin and a multiple of %d", a->cin_pad, BK);
-  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_packed_f32: cout=%d taps=%d dil=%d", a->cout, a->taps, a->dil);
-  SD_CHECK_ARG(a->lda % 4 == 0 && a->a_col0 % 4 == 0 && a->a_col0 >= 0 && a->a_col0 + a->cin <= a->lda,
-               "sd_conv1d_cl_packed_f32: lda=%d a_col0=%d cin=%d (need multiples of 4, slice inside row)", a->lda, a->a_col0, a->cin);
-  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_packed_f32: output slice outside row");
-  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "sd_conv1d_cl_packed_f32: x and w must be 16-byte aligned");
-  if (a->tee) {
-    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
-                 "sd_conv1d_cl_packed_f32: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
-    if (a->tee_add)
-      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "sd_conv1d_cl_packed_f32: tee_add slice outside row");
-  }
-  if (a->colstat) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_conv1d_cl_packed_f32: no column statistics over packed spans");
-  int vec = a->cout % 8 == 0 && a->ldo % 4 == 0 && a->o_col0 % 4 == 0 && sd_aligned16(a->y);
-  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);
-  if (a->tee) {
-    vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 4 == 0 && sd_aligned16(a->tee);
-    if (a->tee_add) vec = vec && a->ld_ta % 4 == 0 && a->ta_col0 % 4 == 0 && sd_aligned16(a->tee_add);
-  }
+  int vec;
+  if (int e = sd_check_conv(a, {"sd_conv1d_cl_packed_f32", 4, BK, 4, true, true, 0}, &vec)) return e;
   const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
   SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_packed_f32: grid too large");
   const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);     // as the uniform launch: the epilogue's C tile needs BM * LDC

@@ -1136,39 +1136,12 @@ extern "C" int sd_conv1d_cl_f16(const sd_conv_args* a, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f16: null args");
   SD_CHECK_ARG(a->w_dtype == SD_DT_F16, "sd_conv1d_cl_f16: weights must be packed f16 (w_dtype=%d)", a->w_dtype);
-  SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_f16: null x/w/y");
   SD_CHECK_ARG((a->x_dtype == SD_DT_F32 || a->x_dtype == SD_DT_F16) && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_F16),
                "sd_conv1d_cl_f16: bad x_dtype/y_dtype %d/%d", a->x_dtype, a->y_dtype);
-  SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "sd_conv1d_cl_f16: M=%d must be a positive multiple of T=%d", a->M, a->T);
-  SD_CHECK_ARG(a->cin > 0 && a->cin % 8 == 0, "sd_conv1d_cl_f16: cin=%d must be a positive multiple of 8", a->cin);
-  SD_CHECK_ARG(a->cin_pad >= a->cin && a->cin_pad % BK == 0, "sd_conv1d_cl_f16: cin_pad=%d must be >= cin and a multiple of %d", a->cin_pad, BK);
-  SD_CHECK_ARG(a->cout > 0, "sd_conv1d_cl_f16: cout=%d", a->cout);
-  SD_CHECK_ARG(a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_f16: taps=%d (odd) dil=%d", a->taps, a->dil);
-  SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_f16: reflect padding %d needs T > pad (T=%d)", (a->taps / 2) * a->dil, a->T);
-  SD_CHECK_ARG(a->lda % 8 == 0 && a->a_col0 % 8 == 0 && a->a_col0 + a->cin <= a->lda,
-               "sd_conv1d_cl_f16: lda=%d a_col0=%d cin=%d (need multiples of 8, slice inside row)", a->lda, a->a_col0, a->cin);
-  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_f16: output slice outside row");
-  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "sd_conv1d_cl_f16: x and w must be 16-byte aligned");
-  if (a->tee) {
-    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
-                 "sd_conv1d_cl_f16: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
-    if (a->tee_add)
-      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "sd_conv1d_cl_f16: tee_add slice outside row");
-  }
+  int vec;
+  if (int e = sd_check_conv(a, {"sd_conv1d_cl_f16", 8, BK, 8, false, true, 64}, &vec)) return e;
   const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
   SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_f16: grid too large");
-  int vec = a->cout % 8 == 0 && a->ldo % 8 == 0 && a->o_col0 % 8 == 0 && sd_aligned16(a->y);
-  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);   // null is aligned
-  if (a->tee) {
-    vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 8 == 0 && sd_aligned16(a->tee);
-    if (a->tee_add) vec = vec && a->ld_ta % 8 == 0 && a->ta_col0 % 8 == 0 && sd_aligned16(a->tee_add);
-  }
-  if (a->colstat) {
-    const bool simple = (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg;
-    if (!(vec && simple && a->T >= 64 && a->cout % 256 == 0 && !a->tee))
-      return sd_set_error(SD_ERR_UNSUPPORTED, "sd_conv1d_cl_f16: colstat needs T >= 64, cout %% 256 == 0, relu/identity, per-channel bias, "
-                          "aligned slices and no tee (T=%d cout=%d act=%d/%d)", a->T, a->cout, a->act, a->act2);
-  }
   const bool xa = a->x_dtype == SD_DT_F16, ya = a->y_dtype == SD_DT_F16;
   // Kernel choice, measured per shape on MI355X (tools/probe_conv.py, B*T = 1 005 000 rows): the 256x256
   // LDS-DMA kernel wins wherever the output is wide (3072x3072: 987 vs ~800 TFLOP/s, 1024x1024: 789 vs
@@ -1262,28 +1235,11 @@ extern "C" int sd_split16_pack_f32(const float* x, int ldx, int col0, int M, int
 // x plain f32 (split while staging): the 128x128 kernel
 static int conv1d_cl_split16_narrow(const sd_conv_args* a, hipStream_t stream) {
   SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16), "sd_conv1d_cl_split16: w must be SD_DT_SPLIT16, y f32 or SD_DT_SPLIT16");
-  SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "sd_conv1d_cl_split16: M=%d must be a positive multiple of T=%d", a->M, a->T);
-  SD_CHECK_ARG(a->cin > 0 && a->cin % 4 == 0 && a->cin_pad >= a->cin && a->cin_pad % 32 == 0, "sd_conv1d_cl_split16: cin=%d (a multiple of 4) cin_pad=%d (of 32)", a->cin, a->cin_pad);
-  SD_CHECK_ARG(a->cout > 0 && a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_split16: cout=%d taps=%d dil=%d", a->cout, a->taps, a->dil);
-  SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_split16: reflect padding %d needs T > pad (T=%d)", (a->taps / 2) * a->dil, a->T);
-  SD_CHECK_ARG(a->lda % 4 == 0 && a->a_col0 % 4 == 0 && a->a_col0 + a->cin <= a->lda && sd_aligned16(a->x) && sd_aligned16(a->w),
-               "sd_conv1d_cl_split16: f32 x needs lda / a_col0 multiples of 4, the slice inside the row, 16-byte aligned x and w");
-  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_split16: output slice outside row");
   SD_CHECK_ARG(!a->colstat, "sd_conv1d_cl_split16: column statistics come from the 256x256 kernel (SD_DT_SPLIT16 x) only");
-  if (a->tee) {
-    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
-                 "sd_conv1d_cl_split16: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
-    if (a->tee_add)
-      SD_CHECK_ARG(a->ta_col0 >= 0 && a->ta_col0 + (a->tee_hi - a->tee_lo) <= a->ld_ta, "sd_conv1d_cl_split16: tee_add slice outside row");
-  }
+  int vec;      // (sd_store_tile's groups of 8 columns)
+  if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 4, 32, 8, false, true, 0}, &vec)) return e;
   const long tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->cout + BN - 1) / BN;
   SD_CHECK_ARG(tiles_m * tiles_n < (1L << 31), "sd_conv1d_cl_split16: grid too large");
-  int vec = a->cout % 8 == 0 && a->ldo % 8 == 0 && a->o_col0 % 8 == 0 && sd_aligned16(a->y);      // sd_store_tile's groups of 8 columns
-  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);
-  if (a->tee) {
-    vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 8 == 0 && sd_aligned16(a->tee);
-    if (a->tee_add) vec = vec && a->ld_ta % 8 == 0 && a->ta_col0 % 8 == 0 && sd_aligned16(a->tee_add);
-  }
   if (a->y_dtype == SD_DT_SPLIT16)      // y written as split halves by the shared epilogue's vector path (ldo in VALUE columns)
     SD_CHECK_ARG(vec && a->ldo % 32 == 0, "sd_conv1d_cl_split16: an SD_DT_SPLIT16 output needs ldo %% 32 == 0 and the aligned (vector) epilogue (ldo=%d o_col0=%d cout=%d)",
                  a->ldo, a->o_col0, a->cout);
@@ -1304,30 +1260,10 @@ extern "C" int sd_conv1d_cl_split16(const sd_conv_args* a, sd_stream_t stream_) 
   if (a->x_dtype == SD_DT_F32) return conv1d_cl_split16_narrow(a, stream);
   SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && a->x_dtype == SD_DT_SPLIT16 && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16),
                "sd_conv1d_cl_split16: x and w must be split-packed (SD_DT_SPLIT16), y f32 or SD_DT_SPLIT16 (got %d/%d/%d)", a->x_dtype, a->w_dtype, a->y_dtype);
-  SD_CHECK_ARG(a->M > 0 && a->T > 0 && a->M % a->T == 0, "sd_conv1d_cl_split16: M=%d must be a positive multiple of T=%d", a->M, a->T);
-  SD_CHECK_ARG(a->cin > 0 && a->cin_pad >= a->cin && a->cin_pad % 32 == 0, "sd_conv1d_cl_split16: cin=%d cin_pad=%d (a multiple of 32)", a->cin, a->cin_pad);
-  SD_CHECK_ARG(a->cout > 0, "sd_conv1d_cl_split16: cout=%d", a->cout);
-  SD_CHECK_ARG(a->taps >= 1 && (a->taps & 1) && a->dil >= 1, "sd_conv1d_cl_split16: taps=%d (odd) dil=%d", a->taps, a->dil);
-  SD_CHECK_ARG((a->taps / 2) * a->dil < a->T, "sd_conv1d_cl_split16: reflect padding %d needs T > pad (T=%d)", (a->taps / 2) * a->dil, a->T);
-  SD_CHECK_ARG(a->lda % 32 == 0 && a->a_col0 % 32 == 0 && a->a_col0 + a->cin_pad <= a->lda,
-               "sd_conv1d_cl_split16: lda=%d a_col0=%d cin_pad=%d (value columns: multiples of 32, slice inside row)", a->lda, a->a_col0, a->cin_pad);
-  SD_CHECK_ARG(a->o_col0 >= 0 && a->o_col0 + a->cout <= a->ldo, "sd_conv1d_cl_split16: output slice outside row");
-  SD_CHECK_ARG(sd_aligned16(a->x) && sd_aligned16(a->w), "sd_conv1d_cl_split16: x and w must be 16-byte aligned");
-  SD_CHECK_ARG(!(a->tee && a->tee_add), "sd_conv1d_cl_split16: the tee_add epilogue is not available on this kernel");
-  if (a->tee)
-    SD_CHECK_ARG(a->tee_lo >= 0 && a->tee_lo < a->tee_hi && a->tee_hi <= a->cout && a->tee_hi - a->tee_lo <= a->ldt,
-                 "sd_conv1d_cl_split16: bad tee range [%d,%d) ldt=%d", a->tee_lo, a->tee_hi, a->ldt);
+  int vec;      // (value columns in groups of 32: the operand is cin_pad values wide)
+  if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 32, 32, 8, false, false, 128}, &vec)) return e;
   const long tiles = (long)((a->M + TBM - 1) / TBM) * ((a->cout + TBN - 1) / TBN);
   SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_split16: grid too large");
-  int vec = a->cout % 8 == 0 && a->ldo % 8 == 0 && a->o_col0 % 8 == 0 && sd_aligned16(a->y);
-  vec = vec && sd_aligned16(a->bias) && sd_aligned16(a->scale) && sd_aligned16(a->shift);
-  if (a->tee) vec = vec && a->tee_lo % 8 == 0 && a->tee_hi % 8 == 0 && a->ldt % 8 == 0 && sd_aligned16(a->tee);
-  if (a->colstat) {
-    const bool simple = (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg;
-    if (!(vec && simple && a->T >= 128 && a->cout % 256 == 0 && !a->tee))
-      return sd_set_error(SD_ERR_UNSUPPORTED, "sd_conv1d_cl_split16: colstat needs T >= 128, cout %% 256 == 0, relu/identity, per-channel bias, "
-                          "aligned slices and no tee (T=%d cout=%d act=%d/%d)", a->T, a->cout, a->act, a->act2);
-  }
   // the kernel sees rows of halfs: a value column is two halfs, a K step of 64 halfs is 32 values
   sd_conv_args k = *a;
   k.lda = 2 * a->lda; k.a_col0 = 2 * a->a_col0;

@@ -230,28 +230,33 @@ int run_wide(const sd_layer& l, sd_conv_args a, bool split, void* xs, long narro
     if (e_ != SD_OK) return e_; \
   } while (0)
 
-// rel_len (device f32 [B], NULL = all ones): speechbrain's relative lengths.  Every conv, BN, Res2Net add and the SE gate's application
-// run on the padded rows as without them; the SE squeezes, the global mean / std of the attentive pooling and its softmax and statistics
-// count each row's first sd_mask_frames(rel_len[b], T) frames only.  Those statistics then come from the row-masked reduction kernels
-// (no column statistics from the conv epilogues), and both pooling routes take the mask.
-// span (device int32 [B + 1], NULL = uniform): packed spans ("Packed spans", sd_hip.h) of span_rows rows in all, exact f32 only.  The
-// position-dependent layers (the k = 5 stem, the dilated Res2Net convs, the attention TDNN with its per-segment bias) run on the packed conv,
-// the position-free 1x1 layers on the uniform operator as ONE segment of M rows (T = M: the reflect is a no-op), every statistic and the SE
-// gate on the packed reductions; the per-segment layers (B rows) as always.
-int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb, void* ws_dev, size_t ws_bytes,
-            sd_stream_t stream, int dt, const float* rel_len = nullptr, const int* span = nullptr, int span_rows = 0) {
+// A position-dependent layer (the k = 5 stem, the dilated Res2Net convs, the attention TDNN with its per-segment bias): packed spans take the
+// packed conv (reflect and bias per span), a uniform map the given runner.
+template <typename F>
+int run_positional(const SdSegs& sg, const sd_conv_args& a, sd_stream_t stream, F&& uniform) {
+  return sg.packed ? sd_conv1d_cl_packed_f32(&a, sg.span, sg.B, stream) : uniform();
+}
+
+// sg: the segment map of the B segments (SdSegs, sd_common.h).
+// Relative lengths (sg.rel_len, speechbrain's wav_lens): every conv, BN, Res2Net add and the SE gate's application run on the padded rows as
+// without them; the SE squeezes, the global mean / std of the attentive pooling and its softmax and statistics count each row's first
+// sd_mask_frames(rel_len[b], T) frames only.  Those statistics then come from the reduction kernels (no column statistics from the conv
+// epilogues), and both pooling routes take the mask.
+// Packed spans ("Packed spans", sd_hip.h; exact f32 only): the position-dependent layers run on the packed conv, the position-free 1x1 layers
+// on the uniform operator as ONE segment of M rows (T = M: the reflect is a no-op), every statistic and the SE gate on the packed map; the
+// per-segment layers (B rows) as always.
+int forward(const sd_ecapa_weights* w, const float* feats, const SdSegs& sg, float* emb, void* ws_dev, size_t ws_bytes, sd_stream_t stream, int dt) {
+  const int B = sg.B, T = sg.T;
   SD_TRY(check_weights(w, dt));
-  SD_CHECK_ARG(B >= 0 && T > 0, "sd_ecapa_forward: B=%d T=%d", B, T);
+  SD_CHECK_ARG(B >= 0 && (sg.packed || T > 0), "sd_ecapa_forward: B=%d T=%d", B, T);
   if (B == 0) return SD_OK;
   SD_CHECK_ARG(feats && emb && ws_dev, "sd_ecapa_forward: null feats/emb/workspace");
-  SD_CHECK_ARG(span || (long)B * T < (1L << 31), "sd_ecapa_forward: B*T overflows int");
+  SD_CHECK_ARG(sg.packed || (long)B * T < (1L << 31), "sd_ecapa_forward: B*T overflows int");
   SD_CHECK_ARG(sd_aligned16(ws_dev), "sd_ecapa_forward: workspace must be 16-byte aligned");
-  const int M = span ? span_rows : B * T;
+  const int M = sg.packed ? sg.M : B * T;
   const Buffers b = carve(w, B, (size_t)M, ws_dev, dt);
   if (ws_bytes < b.bytes) return sd_set_error(SD_ERR_WORKSPACE, "sd_ecapa_forward: workspace %zu < %zu bytes", ws_bytes, b.bytes);
-  const int Tc = span ? M : T;          // the segment length the position-free layers see
-  // the position-dependent layers: uniform -> the given runner; packed spans -> the packed conv
-  auto by_span = [&](const sd_conv_args& a, auto&& uniform) -> int { return span ? sd_conv1d_cl_packed_f32(&a, span, B, stream) : uniform(); };
+  const int Tc = sg.packed ? M : T;          // the segment length the position-free layers see
 
   const int C = w->channels, Cm = w->mfa_channels, chunk = C / w->res2_scale;
   const int F32 = SD_DT_F32;
@@ -272,7 +277,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     const char* e = sd_experiment_env("SD_COLSTAT");
     return !(e && e[0] == '0');
   }();
-  const bool colstat_on = colstat_ok && rel_len == nullptr && span == nullptr;    // the epilogue's column statistics sum over all T rows of a segment
+  const bool colstat_on = colstat_ok && !sg.packed && !sg.rel_len;    // the epilogue's column statistics sum over all T rows of a segment
   bool x0_split = false;                                 // the stem's output exists as SD_DT_SPLIT16 only (b.x0s)
   // block 0: TDNNBlock(n_mels -> C, k=5) on the f32 features.  f16: the features are rounded to f16 once (the
   // operand precision of that path anyway; t2 is free here), which lets the stem run on the LDS-DMA kernel of the
@@ -291,7 +296,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     x0_split = wsplit && b.x0s && b.xcs && wide_packed(w->block0) && wide_packed(w->blocks[0].tdnn1) && !wide_goes_narrow(w->block0, M, nt) &&
                !wide_goes_narrow(w->blocks[0].tdnn1, M, nt);
     if (x0_split) { a.y = b.x0s; a.y_dtype = SD_DT_SPLIT16; }
-    SD_TRY(by_span(a, [&] { return run_wide(w->block0, a, wsplit, b.xs, nt, stream); }));
+    SD_TRY(run_positional(sg, a, stream, [&] { return run_wide(w->block0, a, wsplit, b.xs, nt, stream); }));
   }
   const void* xin = b.x0; int ldin = C, colin = 0;
   // where the current block input exists as SD_DT_SPLIT16 (null: it does not), and whether its f32 form was skipped
@@ -335,7 +340,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
           a.tee = dst; a.ldt = chunk; a.tee_lo = 0; a.tee_hi = chunk;
           a.tee_add = b.r; a.ld_ta = C; a.ta_col0 = (j + 1) * chunk;
         }
-        SD_TRY(by_span(a, [&] { return run_narrow(blk.res2[j - 1], a, split, stream); }));
+        SD_TRY(run_positional(sg, a, stream, [&] { return run_narrow(blk.res2[j - 1], a, split, stream); }));
       }
     }
     // tdnn2; the SE squeeze (mean over T) comes out of its epilogue as per-tile column sums where the
@@ -348,8 +353,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       int rows = 128;
       SD_TRY(run_wide(blk.tdnn2, a, wsplit, b.xs, nt, stream, r_split ? b.rs : nullptr, C, stat ? &rows : nullptr));
       if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.t2, dt, C, 0, B, T, C, 0, 0.f, b.semean, rows, stream));
-      else if (span) SD_TRY(sd_seg_mean_std_packed_dt(b.t2, dt, C, 0, span, B, M, C, 0, 0.f, b.semean, stream));
-      else SD_TRY(sd_seg_mean_std_lens_dt(b.t2, dt, C, 0, B, T, rel_len, C, 0, 0.f, b.semean, stream));
+      else SD_TRY(sd_seg_mean_std(b.t2, dt, C, 0, sg, C, 0, 0.f, b.semean, stream));
     }
     // squeeze-excitation gate (per-segment, f32)
     {
@@ -368,12 +372,8 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
       const bool skip_f32 = twin && wide_packed(w->mfa) && !wide_goes_narrow(w->mfa, M, nt) && !next_reads_f32 &&
                             (i + 1 >= w->n_blocks || wide_packed(w->blocks[i + 1].tdnn1));
       const bool res_twin = twin && in_sp != nullptr && res_is_twin;
-      if (span)      // (exact f32 only: no split copies)
-        SD_TRY(sd_se_scale_residual_packed_dt(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, span, B, M, C, dt, stream));
-      else
-        SD_TRY(sd_se_scale_residual_split(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, B, T, C, dt,
-                                          twin ? b.xcs : nullptr, Cm, i * C, stream,
-                                          res_twin ? in_sp : nullptr, in_sp_ld, in_sp_col, skip_f32 ? 0 : 1));
+      SD_TRY(sd_se_scale_residual(b.t2, C, b.gate, xin, ldin, colin, b.xcat, Cm, i * C, sg, C, dt, stream, twin ? b.xcs : nullptr, Cm, i * C,
+                                  res_twin ? in_sp : nullptr, in_sp_ld, in_sp_col, skip_f32 ? 0 : 1));
       res_is_twin = skip_f32;                            // the next block's shortcut exists only as the split copy
       in_sp = twin ? b.xcs : nullptr; in_sp_ld = Cm; in_sp_col = i * C;
     }
@@ -389,8 +389,7 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     int rows = 128;
     SD_TRY(run_wide(w->mfa, a, wsplit, b.xs, nt, stream, b.xcs, Cm, stat ? &rows : nullptr));
     if (stat) SD_TRY(sd_colstat_finish_rows(a.colstat, a.shift, b.h, dt, Cm, 0, B, T, Cm, 1, w->asp_eps, b.stats, rows, stream));
-    else if (span) SD_TRY(sd_seg_mean_std_packed_dt(b.h, dt, Cm, 0, span, B, M, Cm, 1, w->asp_eps, b.stats, stream));
-    else SD_TRY(sd_seg_mean_std_lens_dt(b.h, dt, Cm, 0, B, T, rel_len, Cm, 1, w->asp_eps, b.stats, stream));
+    else SD_TRY(sd_seg_mean_std(b.h, dt, Cm, 0, sg, Cm, 1, w->asp_eps, b.stats, stream));
   }
   // attentive statistics pooling with global context
   {
@@ -399,26 +398,25 @@ int forward(const sd_ecapa_weights* w, const float* feats, int B, int T, float* 
     SD_TRY(sd_seg_gemm_f32(&g, b.skp_bytes ? b.skp : nullptr, b.skp_bytes, stream));
     sd_conv_args a = conv_of(w->asp_tdnn_h, b.h, dt, Cm, 0, b.a1, dt, w->att_channels, 0, M, Tc, SD_ACT_RELU);
     a.bias = b.gbias; a.bias_per_seg = 1; a.act2 = SD_ACT_TANH;
-    SD_TRY(by_span(a, [&] { return run_narrow(w->asp_tdnn_h, a, split, stream); }));
+    SD_TRY(run_positional(sg, a, stream, [&] { return run_narrow(w->asp_tdnn_h, a, split, stream); }));
     // asp.conv + softmax over T + weighted statistics: one kernel where the geometry allows (the
     // [M][3C] logits are then never stored), else the conv followed by the pooling kernel
     static const bool fuse_ok = [] {     // SD_ASP_FUSED=0: A/B switch for measurements
       const char* e = sd_experiment_env("SD_ASP_FUSED");
       return !(e && e[0] == '0');
     }();
-    const bool fused = fuse_ok && !span && w->asp_conv.taps == 1 && w->asp_conv.cin_pad == w->att_channels &&
+    const bool fused = fuse_ok && !sg.packed && w->asp_conv.taps == 1 && w->asp_conv.cin_pad == w->att_channels &&
                        sd_asp_attend_pool_supported(dt, T, Cm, w->att_channels);
     if (fused) {
       // (split16 mode: the same f32 tensors, the logits product on the f16 matrix cores with split operands)
       // (the weights' 2^s: asp_conv.split_scale_inv = 2^-s from the host, data dependent like every other split weight's)
       const float ws = w->asp_conv.split_scale_inv > 0.f ? 1.f / w->asp_conv.split_scale_inv : 256.f;
       SD_TRY(sd_asp_attend_pool_scaled(b.a1, w->asp_conv.w, b.h, split ? SD_DT_SPLIT16 : dt, Cm, B, T, Cm, w->att_channels, w->asp_eps, ws, b.pooled, stream,
-                                            rel_len));
+                                            sg.rel_len));
     } else {
       sd_conv_args c = conv_of(w->asp_conv, b.a1, dt, w->att_channels, 0, b.e, dt, Cm, 0, M, Tc, SD_ACT_NONE);
       SD_TRY(run_conv(c, stream));
-      if (span) SD_TRY(sd_asp_pool_packed_dt(b.e, Cm, b.h, dt, Cm, span, B, M, Cm, w->asp_eps, b.pooled, stream));
-      else SD_TRY(sd_asp_pool_lens_dt(b.e, Cm, b.h, dt, Cm, B, T, rel_len, Cm, w->asp_eps, b.pooled, stream));
+      SD_TRY(sd_asp_pool(b.e, Cm, b.h, dt, Cm, sg, Cm, w->asp_eps, b.pooled, stream));
     }
   }
   // asp_bn (folded into the weights by the host) + fc
@@ -450,25 +448,25 @@ extern "C" int sd_ecapa_forward_packed_f32(const sd_ecapa_weights* w, const floa
   SD_CHECK_ARG(B >= 0, "sd_ecapa_forward_packed_f32: B=%d", B);
   if (B == 0) return SD_OK;
   SD_CHECK_ARG(M > 0 && frame_start_dev != nullptr, "sd_ecapa_forward_packed_f32: M=%d, frame_start %p", M, (const void*)frame_start_dev);
-  return forward(w, feats, B, 1, emb, ws_dev, ws_bytes, stream, SD_DT_F32, nullptr, frame_start_dev, M);
+  return forward(w, feats, sd_packed_segs(frame_start_dev, B, M), emb, ws_dev, ws_bytes, stream, SD_DT_F32);
 }
 
 extern "C" int sd_ecapa_forward_f32(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb,
                                     void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
-  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F32);
+  return forward(w, feats, sd_uniform_segs(B, T), emb, ws_dev, ws_bytes, stream, SD_DT_F32);
 }
 
 extern "C" int sd_ecapa_forward_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, float* emb,
                                     void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
-  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F16);
+  return forward(w, feats, sd_uniform_segs(B, T), emb, ws_dev, ws_bytes, stream, SD_DT_F16);
 }
 
 extern "C" int sd_ecapa_forward_lens_f32(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev, float* emb,
                                          void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
-  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F32, rel_len_dev);
+  return forward(w, feats, sd_uniform_segs(B, T, rel_len_dev), emb, ws_dev, ws_bytes, stream, SD_DT_F32);
 }
 
 extern "C" int sd_ecapa_forward_lens_f16(const sd_ecapa_weights* w, const float* feats, int B, int T, const float* rel_len_dev, float* emb,
                                          void* ws_dev, size_t ws_bytes, sd_stream_t stream) {
-  return forward(w, feats, B, T, emb, ws_dev, ws_bytes, stream, SD_DT_F16, rel_len_dev);
+  return forward(w, feats, sd_uniform_segs(B, T, rel_len_dev), emb, ws_dev, ws_bytes, stream, SD_DT_F16);
 }

@@ -8,6 +8,8 @@
 // owns 4 consecutive channels (one 16-byte load per row) and walks time; a
 // workgroup is 64 channel groups x 4 row phases, combined through LDS in a fixed
 // order (results are run-to-run identical).
+#include <type_traits>
+
 #include "sd_common.h"
 
 namespace {
@@ -59,19 +61,48 @@ __device__ __forceinline__ f32x4 combine_max(f32x4* part, int rp, int cg, f32x4 
   return s;
 }
 
+// Segment maps (SdSegs, sd_common.h) on the device: which rows of the [M][ld] activations are segment s.  One type per kind, a template
+// parameter of every kernel below, so that a kind costs nothing in the other's code.
+//   rows(s, r0, n): segment s is rows r0 .. r0 + n (the row offset 64-bit: the uniform _dt entries do not limit B * T)
+//   seg_of(m):      the segment that owns row m
+struct UniformRows {      // rows s T .. s T + T, of which the first sd_mask_frames(rel_len[s], T) count (rel_len null: all T)
+  static constexpr bool packed = false;
+  int T;
+  const float* rel_len;
+  __device__ void rows(int s, size_t& r0, int& n) const {
+    r0 = (size_t)s * T;
+    n = rel_len ? sd_mask_frames(rel_len[s], T) : T;
+  }
+  __device__ int seg_of(int m) const { return m / T; }
+};
+struct PackedRows {       // rows frame_start[s] .. frame_start[s + 1], clamped into [0, M) (a malformed table gives wrong numbers, never an
+  static constexpr bool packed = true;    // access outside the M rows)
+  const int* fs;
+  int B, M;
+  __device__ void rows(int s, size_t& r0, int& n) const {
+    int a = fs[s], e = fs[s + 1];
+    a = a < 0 ? 0 : (a > M ? M : a);
+    e = e < a ? a : (e > M ? M : e);
+    r0 = a;
+    n = e - a;
+  }
+  __device__ int seg_of(int m) const { return sd_span_of(fs, B, m); }
+};
+
 // CGv channel groups (of 4) x RPv row phases = 256 threads: 64 x 4 (a thread walks a quarter of the segment's rows) for launches that fill the
 // chip, 16 x 16 for the few segments of a small batch (16 segments x 1024 channels: 64 workgroups of 50 dependent steps each took 15-17 us)
-template <typename T, int CGv = CG, int RPv = RP>
-__global__ __launch_bounds__(256) void seg_mean_std_kernel(const T* x, int ld, int col0, int Tn, int C,
-                                                           int want_std, float eps, float* out, const float* rel_len) {
+template <typename T, typename Rows, int CGv = CG, int RPv = RP>
+__global__ __launch_bounds__(256) void seg_mean_std_kernel(const T* x, int ld, int col0, int C, int want_std, float eps, float* out, Rows sg) {
   static_assert(CGv * RPv == 256, "one workgroup");
   __shared__ f32x4 part[RPv * CGv];
   const int b = blockIdx.y;
   const int cg = threadIdx.x % CGv, rp = threadIdx.x / CGv;
   const int c = (blockIdx.x * CGv + cg) * 4;
   const bool ok = c < C;
-  const T* base = x + (size_t)b * Tn * ld + col0 + (ok ? c : 0);
-  const int nt = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;     // frames that count (relative lengths: speechbrain's mask)
+  size_t r0;
+  int nt;                                      // the segment's first row and the rows that count
+  sg.rows(b, r0, nt);
+  const T* base = x + r0 * ld + col0 + (ok ? c : 0);
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
   if (ok)
     for (int t = rp; t < nt; t += RPv) s += ld4(base + (size_t)t * ld);
@@ -98,17 +129,18 @@ __global__ __launch_bounds__(256) void seg_mean_std_kernel(const T* x, int ld, i
 
 // y = x * gate[segment] + res, 16 bytes per lane, no 64-bit index arithmetic: a workgroup walks whole
 // rows (grid-stride over row groups), a thread keeps its channel group for all of them, the
-// segment index costs one 32-bit division per row.
+// segment index costs one 32-bit division (packed: a search in frame_start) per row.
 // ys (f32 only, may be null): a second, SD_DT_SPLIT16 copy of the result (hi = f16(v), lo = f16(v - hi), interleaved per 32
 // channels) at value column s_col0 of rows of lds value columns: what the split16x3 wide convs read, written here so that
 // they need no separate pack pass over the MFA input.
-template <typename T>
+template <typename T, typename Rows>
 __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int ldx, const float* gate,
                                                                 const T* res, int ldr, int r_col0,
                                                                 T* y, int ldy, int y_col0,
-                                                                int M, int Tn, int C, _Float16* ys = nullptr, int lds = 0, int s_col0 = 0,
+                                                                int M, Rows sg, int C, _Float16* ys = nullptr, int lds = 0, int s_col0 = 0,
                                                                 const _Float16* rsp = nullptr, int ld_rsp = 0, int rsp_col0 = 0, int write_y = 1) {
   constexpr int VEC = 16 / sizeof(T);                 // 4 f32 or 8 f16 channels per lane
+  constexpr bool twins = sizeof(T) == 4 && !Rows::packed;   // the split copies (the f32-split16x3 schedule: never over packed spans)
   typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
   const int groups = C / VEC;                          // channel groups per row
   const int gpr = groups < 256 ? groups : 256;         // threads used per row
@@ -116,7 +148,7 @@ __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int 
   const int tr = threadIdx.x / gpr, tg = threadIdx.x % gpr;
   if (tr >= rows_per_pass) return;
   for (int m = blockIdx.x * rows_per_pass + tr; m < M; m += gridDim.x * rows_per_pass) {
-    const float* g = gate + (size_t)(m / Tn) * C;
+    const float* g = gate + (size_t)sg.seg_of(m) * C;
     const T* xr = x + (size_t)m * ldx;
     const T* rr = res + (size_t)m * ldr + r_col0;
     T* yr = y + (size_t)m * ldy + y_col0;
@@ -124,7 +156,7 @@ __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int 
       const int c = gq * VEC;
       const vec_t xv = *reinterpret_cast<const vec_t*>(xr + c);
       vec_t rv;
-      if constexpr (sizeof(T) == 4) {
+      if constexpr (twins) {
         if (rsp) {      // the shortcut as the SD_DT_SPLIT16 copy a previous call wrote: hi + lo (the value the split convs see)
           typedef _Float16 h4r __attribute__((ext_vector_type(4)));
           const int rc = rsp_col0 + c;
@@ -141,8 +173,8 @@ __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int 
       vec_t o;
 #pragma unroll
       for (int e = 0; e < VEC; ++e) o[e] = (T)((float)xv[e] * g[c + e] + (float)rv[e]);
-      if (write_y) *reinterpret_cast<vec_t*>(yr + c) = o;
-      if constexpr (sizeof(T) == 4) {
+      if (Rows::packed || write_y) *reinterpret_cast<vec_t*>(yr + c) = o;
+      if constexpr (twins) {
         if (ys) {
           typedef _Float16 h4v __attribute__((ext_vector_type(4)));
           h4v hi, lo;
@@ -162,17 +194,18 @@ __global__ __launch_bounds__(256) void se_scale_residual_kernel(const T* x, int 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, const T* h, int ldh,
-                                                       int Tn, int C, float eps, float* out, const float* rel_len) {
+template <typename T, typename Rows>
+__global__ __launch_bounds__(256) void asp_pool_kernel(const T* logit, int ldl, const T* h, int ldh, Rows sg, int C, float eps, float* out) {
   __shared__ f32x4 part[RP * CG];
   const int b = blockIdx.y;
   const int cg = threadIdx.x & (CG - 1), rp = threadIdx.x >> 6;
   const int c = (blockIdx.x * CG + cg) * 4;
   const bool ok = c < C;
-  const T* lb = logit + (size_t)b * Tn * ldl + (ok ? c : 0);
-  const T* hb = h + (size_t)b * Tn * ldh + (ok ? c : 0);
-  const int nt = rel_len ? sd_mask_frames(rel_len[b], Tn) : Tn;     // frames past the mask: logit -inf, out of every sum
+  size_t r0;
+  int nt;                                      // rows past the mask: logit -inf, out of every sum
+  sg.rows(b, r0, nt);
+  const T* lb = logit + r0 * ldl + (ok ? c : 0);
+  const T* hb = h + r0 * ldh + (ok ? c : 0);
   const float ninf = -INFINITY;
   f32x4 mx = {ninf, ninf, ninf, ninf};
   if (ok)
@@ -348,14 +381,40 @@ __global__ __launch_bounds__(256) void sim_argmax_kernel(const float* w, int ldw
   }
 }
 
-int check_cl_dt(const char* fn, const void* x, int dtype, int ld, int col0, int C) {
-  SD_CHECK_ARG(x != nullptr, "%s: null input", fn);
-  SD_CHECK_ARG(dtype == SD_DT_F32 || dtype == SD_DT_F16, "%s: bad dtype %d", fn, dtype);
+int check_cl_dt(const char* fn, const char* what, const void* x, int dtype, int ld, int col0, int C) {
+  SD_CHECK_ARG(x != nullptr, "%s%s: null input", fn, what);
+  SD_CHECK_ARG(dtype == SD_DT_F32 || dtype == SD_DT_F16, "%s%s: bad dtype %d", fn, what, dtype);
   SD_CHECK_ARG(C > 0 && C % 4 == 0 && ld % 4 == 0 && col0 % 4 == 0 && col0 >= 0 && col0 + C <= ld,
-               "%s: C=%d ld=%d col0=%d must be multiples of 4 with the slice inside the row", fn, C, ld, col0);
-  SD_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & (dtype == SD_DT_F16 ? 7u : 15u)) == 0, "%s: input is not aligned for 4-channel accesses", fn);
+               "%s%s: C=%d ld=%d col0=%d must be multiples of 4 with the slice inside the row", fn, what, C, ld, col0);
+  SD_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & (dtype == SD_DT_F16 ? 7u : 15u)) == 0, "%s%s: input is not aligned for 4-channel accesses", fn, what);
   return SD_OK;
 }
+
+// The map's own domain: uniform B >= 1 and T >= 1; packed 0 <= B < 65536 (grid.y; B == 0 is an empty call), M >= 1 and a table.
+// empty: nothing to launch.
+int check_segs(const char* fn, const SdSegs& sg, bool& empty) {
+  empty = false;
+  if (!sg.packed) {
+    SD_CHECK_ARG(sg.B > 0 && sg.T > 0, "%s: B=%d T=%d", fn, sg.B, sg.T);
+    return SD_OK;
+  }
+  SD_CHECK_ARG(sg.B >= 0 && sg.B < 65536, "%s: B=%d (0 .. 65535)", fn, sg.B);
+  empty = sg.B == 0;
+  if (!empty) SD_CHECK_ARG(sg.M > 0 && sg.span != nullptr, "%s: M=%d, frame_start %p", fn, sg.M, (const void*)sg.span);
+  return SD_OK;
+}
+
+// f((T*)nullptr, rows): the launch for the storage type (SD_DT_F32 / SD_DT_F16) and the device form of the map
+template <typename F>
+void launch_as(int dtype, const SdSegs& sg, F&& f) {
+  auto typed = [&](auto rows) {
+    if (dtype == SD_DT_F16) f(static_cast<_Float16*>(nullptr), rows);
+    else f(static_cast<float*>(nullptr), rows);
+  };
+  if (sg.packed) typed(PackedRows{sg.span, sg.B, sg.M});
+  else typed(UniformRows{sg.T, sg.rel_len});
+}
+
 // Column statistics left by the conv epilogue (sd_conv_args.colstat) -> per-segment mean (and std).
 // colstat [units][6][C]: sums of (y - pivot) and (y - pivot)^2 over each tile of U rows (128; 80 / 96 / 112 from the variable-height
 // conv kernel), split at the segment boundaries inside the tile (up to three segments: T >= U / 2) (a trailing partial tile counts its
@@ -383,139 +442,6 @@ __global__ __launch_bounds__(256) void colstat_finish_kernel(const float* __rest
   if (want_std) out[(size_t)b * 2 * C + C + c] = sqrtf(fmaxf(q * inv - m1 * m1, eps));
 }
 
-// ---- packed spans (sd_hip.h): span s is rows [frame_start[s], frame_start[s + 1]) of the activations, clamped into [0, M) (a malformed
-// table gives wrong numbers, never an access outside the M rows).  The arithmetic of the kernels above with (first row, count) in place of
-// (b T, n_mask), in ONE workgroup shape for every span and batch: a span's statistics depend on its own rows only.
-__device__ __forceinline__ void span_rows(const int* fs, int M, int s, int& r0, int& nt) {
-  int a = fs[s], e = fs[s + 1];
-  a = a < 0 ? 0 : (a > M ? M : a);
-  e = e < a ? a : (e > M ? M : e);
-  r0 = a;
-  nt = e - a;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void seg_mean_std_packed_kernel(const T* x, int ld, int col0, const int* fs, int M, int C, int want_std,
-                                                                  float eps, float* out) {
-  __shared__ f32x4 part[RP * CG];
-  const int b = blockIdx.y;
-  const int cg = threadIdx.x % CG, rp = threadIdx.x / CG;
-  const int c = (blockIdx.x * CG + cg) * 4;
-  const bool ok = c < C;
-  int r0, nt;
-  span_rows(fs, M, b, r0, nt);
-  const T* base = x + (size_t)r0 * ld + col0 + (ok ? c : 0);
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (ok)
-    for (int t = rp; t < nt; t += RP) s += ld4(base + (size_t)t * ld);
-  s = combine_sum(part, rp, cg, s);
-  const float invT = 1.0f / (float)nt;
-  const f32x4 mean = s * invT;
-  const int ostride = want_std ? 2 * C : C;
-  if (ok && rp == 0) st4(out + (size_t)b * ostride + c, mean);
-  if (!want_std) return;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (ok)
-    for (int t = rp; t < nt; t += RP) {
-      const f32x4 d = ld4(base + (size_t)t * ld) - mean;
-      v += d * d;
-    }
-  v = combine_sum(part, rp, cg, v);
-  if (ok && rp == 0) {
-    f32x4 sd;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sd[e] = sqrtf(fmaxf(v[e] * invT, eps));
-    st4(out + (size_t)b * ostride + C + c, sd);
-  }
-}
-
-// y = x * gate[span of the row] + res (se_scale_residual_kernel's arithmetic; the span by a search in frame_start per row)
-template <typename T>
-__global__ __launch_bounds__(256) void se_scale_residual_packed_kernel(const T* x, int ldx, const float* gate, const T* res, int ldr, int r_col0,
-                                                                       T* y, int ldy, int y_col0, const int* fs, int B, int M, int C) {
-  constexpr int VEC = 16 / sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
-  const int groups = C / VEC;
-  const int gpr = groups < 256 ? groups : 256;
-  const int rows_per_pass = 256 / gpr;
-  const int tr = threadIdx.x / gpr, tg = threadIdx.x % gpr;
-  if (tr >= rows_per_pass) return;
-  for (int m = blockIdx.x * rows_per_pass + tr; m < M; m += gridDim.x * rows_per_pass) {
-    const float* g = gate + (size_t)sd_span_of(fs, B, m) * C;
-    const T* xr = x + (size_t)m * ldx;
-    const T* rr = res + (size_t)m * ldr + r_col0;
-    T* yr = y + (size_t)m * ldy + y_col0;
-    for (int gq = tg; gq < groups; gq += gpr) {
-      const int c = gq * VEC;
-      const vec_t xv = *reinterpret_cast<const vec_t*>(xr + c);
-      const vec_t rv = *reinterpret_cast<const vec_t*>(rr + c);
-      vec_t o;
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) o[e] = (T)((float)xv[e] * g[c + e] + (float)rv[e]);
-      *reinterpret_cast<vec_t*>(yr + c) = o;
-    }
-  }
-}
-
-// attentive statistics pooling over each span's rows (asp_pool_kernel's arithmetic)
-template <typename T>
-__global__ __launch_bounds__(256) void asp_pool_packed_kernel(const T* logit, int ldl, const T* h, int ldh, const int* fs, int M, int C, float eps,
-                                                              float* out) {
-  __shared__ f32x4 part[RP * CG];
-  const int b = blockIdx.y;
-  const int cg = threadIdx.x & (CG - 1), rp = threadIdx.x >> 6;
-  const int c = (blockIdx.x * CG + cg) * 4;
-  const bool ok = c < C;
-  int r0, nt;
-  span_rows(fs, M, b, r0, nt);
-  const T* lb = logit + (size_t)r0 * ldl + (ok ? c : 0);
-  const T* hb = h + (size_t)r0 * ldh + (ok ? c : 0);
-  const float ninf = -INFINITY;
-  f32x4 mx = {ninf, ninf, ninf, ninf};
-  if (ok)
-    for (int t = rp; t < nt; t += RP) {
-      const f32x4 l = ld4(lb + (size_t)t * ldl);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], l[e]);
-    }
-  mx = combine_max(part, rp, cg, mx);
-  f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = {0.f, 0.f, 0.f, 0.f};
-  if (ok)
-    for (int t = rp; t < nt; t += RP) {
-      const f32x4 l = ld4(lb + (size_t)t * ldl);
-      const f32x4 hv = ld4(hb + (size_t)t * ldh);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float w = expf(l[e] - mx[e]);
-        den[e] += w;
-        num[e] += w * hv[e];
-      }
-    }
-  den = combine_sum(part, rp, cg, den);
-  num = combine_sum(part, rp, cg, num);
-  const f32x4 mu = num / den;
-  f32x4 var = {0.f, 0.f, 0.f, 0.f};
-  if (ok)
-    for (int t = rp; t < nt; t += RP) {
-      const f32x4 l = ld4(lb + (size_t)t * ldl);
-      const f32x4 hv = ld4(hb + (size_t)t * ldh);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float w = expf(l[e] - mx[e]);
-        const float d = hv[e] - mu[e];
-        var[e] += w * d * d;
-      }
-    }
-  var = combine_sum(part, rp, cg, var);
-  if (ok && rp == 0) {
-    f32x4 sd;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sd[e] = sqrtf(fmaxf(var[e] / den[e], eps));
-    st4(out + (size_t)b * 2 * C + c, mu);
-    st4(out + (size_t)b * 2 * C + C + c, sd);
-  }
-}
-
 }  // namespace
 
 // f32 -> f16 (round to nearest even), n % 8 == 0 elements, both 16-byte aligned: the features in front of the f16 stem
@@ -541,83 +467,156 @@ int sd_cast_f32_f16(const float* x, long n, void* y, sd_stream_t stream) {
   return SD_OK;
 }
 
-extern "C" int sd_seg_mean_std_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, int C, int want_std, float eps,
-                                  float* out, sd_stream_t stream) {
-  return sd_seg_mean_std_lens_dt(x, x_dtype, ld, col0, B, T, nullptr, C, want_std, eps, out, stream);
-}
-
-// rel_len (device f32 [B], may be NULL = all ones): each segment's statistics over its first sd_mask_frames(rel_len[b], T) rows
-extern "C" int sd_seg_mean_std_lens_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, const float* rel_len, int C, int want_std,
-                                       float eps, float* out, sd_stream_t stream) {
-  if (int e = check_cl_dt("sd_seg_mean_std_dt", x, x_dtype, ld, col0, C)) return e;
-  SD_CHECK_ARG(B > 0 && T > 0 && out && sd_aligned16(out), "sd_seg_mean_std_dt: B=%d T=%d / null or unaligned output", B, T);
-  dim3 grid((C / 4 + CG - 1) / CG, B);
+// ---- the per-segment operators: one launcher each, over a segment map (SdSegs, sd_common.h), behind every public entry.
+// Workgroup shapes: a PACKED map always takes 64 x 4 and the streaming pooling kernel, whatever B and the spans are -- the contract of
+// sd_hip.h ("Packed spans": nothing about span s depends on another span), so a span's result depends neither on B nor on its neighbours.
+// A UNIFORM map keeps the faster choices: 16 x 16 when the 64 x 4 grid is small (grid.x * B < 256), and the LDS pooling kernel when
+// C % APC == 0 and a segment's tile fits in 64 KB.
+int sd_seg_mean_std(const void* x, int dtype, int ld, int col0, const SdSegs& sg, int C, int want_std, float eps, float* out, sd_stream_t stream) {
+  const char* fn = sg.packed ? "sd_seg_mean_std_packed_dt" : "sd_seg_mean_std_dt";
+  bool empty;
+  if (int e = check_segs(fn, sg, empty)) return e;
+  if (empty) return SD_OK;
+  if (int e = check_cl_dt(fn, "", x, dtype, ld, col0, C)) return e;
+  SD_CHECK_ARG(out && sd_aligned16(out), "%s: null or unaligned output", fn);
+  const dim3 grid((C / 4 + CG - 1) / CG, sg.B);
+  const bool small = !sg.packed && (long)grid.x * sg.B < 256;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((long)grid.x * B < 256) {           // a small batch: 16 channel groups x 16 row phases per workgroup
-    dim3 g16((C / 4 + 15) / 16, B);
-    if (x_dtype == SD_DT_F16)
-      hipLaunchKernelGGL((seg_mean_std_kernel<_Float16, 16, 16>), g16, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
-    else
-      hipLaunchKernelGGL((seg_mean_std_kernel<float, 16, 16>), g16, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
-  } else if (x_dtype == SD_DT_F16)
-    hipLaunchKernelGGL(seg_mean_std_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
-  else
-    hipLaunchKernelGGL(seg_mean_std_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, T, C, want_std, eps, out, rel_len);
+  launch_as(dtype, sg, [&](auto* tp, auto rows) {
+    using T = std::remove_pointer_t<decltype(tp)>;
+    using Rows = decltype(rows);
+    const T* xt = static_cast<const T*>(x);
+    if constexpr (!Rows::packed)
+      if (small) {      // a small batch: 16 channel groups x 16 row phases per workgroup
+        hipLaunchKernelGGL((seg_mean_std_kernel<T, Rows, 16, 16>), dim3((C / 4 + 15) / 16, sg.B), dim3(256), 0, s, xt, ld, col0, C, want_std, eps, out, rows);
+        return;
+      }
+    hipLaunchKernelGGL((seg_mean_std_kernel<T, Rows>), grid, dim3(256), 0, s, xt, ld, col0, C, want_std, eps, out, rows);
+  });
   SD_CHECK_LAUNCH("seg_mean_std_kernel");
   return SD_OK;
 }
 
-extern "C" int sd_seg_mean_f32(const float* x, int ld, int col0, int B, int T, int C, float* mean, sd_stream_t stream) {
-  return sd_seg_mean_std_dt(x, SD_DT_F32, ld, col0, B, T, C, 0, 0.f, mean, stream);
-}
-
-extern "C" int sd_seg_mean_std_f32(const float* x, int ld, int col0, int B, int T, int C, float eps, float* stats,
-                                   sd_stream_t stream) {
-  return sd_seg_mean_std_dt(x, SD_DT_F32, ld, col0, B, T, C, 1, eps, stats, stream);
-}
-
-extern "C" int sd_se_scale_residual_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0,
-                                       void* y, int ldy, int y_col0, int B, int T, int C, int dtype, sd_stream_t stream) {
-  return sd_se_scale_residual_split(x, ldx, gate, res, ldr, r_col0, y, ldy, y_col0, B, T, C, dtype, nullptr, 0, 0, stream, nullptr, 0, 0, 1);
-}
-
-// library-internal: the same, plus (f32 only) an SD_DT_SPLIT16 copy of the result at value column s_col0 of ys [B*T][lds]
-int sd_se_scale_residual_split(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0,
-                               void* y, int ldy, int y_col0, int B, int T, int C, int dtype, void* ys, int lds, int s_col0,
-                               sd_stream_t stream, const void* res_split, int ld_rs, int rs_col0, int write_y) {
-  if (res_split || !write_y)      // (f32-split16x3 schedule: the shortcut read from the split copy, the f32 result not written)
-    SD_CHECK_ARG(dtype == SD_DT_F32 && ys && (!res_split || (ld_rs % 32 == 0 && rs_col0 % 4 == 0 && rs_col0 + C <= ld_rs && sd_aligned16(res_split))),
-                 "sd_se_scale_residual: a split shortcut / no f32 result need f32 activations and the split copy of the result");
-  if (ys) SD_CHECK_ARG(dtype == SD_DT_F32 && lds % 32 == 0 && s_col0 % 4 == 0 && s_col0 + C <= lds && sd_aligned16(ys),
-                       "sd_se_scale_residual: the split copy needs f32 activations, lds %% 32 == 0, an aligned slice inside the row");
-  if (int e = check_cl_dt("sd_se_scale_residual(x)", x, dtype, ldx, 0, C)) return e;
-  if (int e = check_cl_dt("sd_se_scale_residual(res)", res, dtype, ldr, r_col0, C)) return e;
-  if (int e = check_cl_dt("sd_se_scale_residual(y)", y, dtype, ldy, y_col0, C)) return e;
-  SD_CHECK_ARG(gate && sd_aligned16(gate) && B > 0 && T > 0, "sd_se_scale_residual: bad gate / B / T");
-  const int M = B * T;
+// (f32 only) ys: an SD_DT_SPLIT16 copy of the result at value column s_col0 of rows of lds value columns; res_split: the shortcut read from
+// such a copy (ld_rs, rs_col0); write_y = 0: the f32 result not written (the f32-split16x3 schedule)
+int sd_se_scale_residual(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy, int y_col0,
+                         const SdSegs& sg, int C, int dtype, sd_stream_t stream, void* ys, int lds, int s_col0, const void* res_split, int ld_rs,
+                         int rs_col0, int write_y) {
+  const char* fn = sg.packed ? "sd_se_scale_residual_packed_dt" : "sd_se_scale_residual";
+  bool empty;
+  if (int e = check_segs(fn, sg, empty)) return e;
+  if (empty) return SD_OK;
+  if (res_split || !write_y)
+    SD_CHECK_ARG(dtype == SD_DT_F32 && !sg.packed && ys && (!res_split || (ld_rs % 32 == 0 && rs_col0 % 4 == 0 && rs_col0 + C <= ld_rs && sd_aligned16(res_split))),
+                 "%s: a split shortcut / no f32 result need uniform f32 activations and the split copy of the result", fn);
+  if (ys) SD_CHECK_ARG(dtype == SD_DT_F32 && !sg.packed && lds % 32 == 0 && s_col0 % 4 == 0 && s_col0 + C <= lds && sd_aligned16(ys),
+                       "%s: the split copy needs uniform f32 activations, lds %% 32 == 0, an aligned slice inside the row", fn);
+  if (int e = check_cl_dt(fn, "(x)", x, dtype, ldx, 0, C)) return e;
+  if (int e = check_cl_dt(fn, "(res)", res, dtype, ldr, r_col0, C)) return e;
+  if (int e = check_cl_dt(fn, "(y)", y, dtype, ldy, y_col0, C)) return e;
+  SD_CHECK_ARG(gate && sd_aligned16(gate), "%s: null or unaligned gate", fn);
   const int vec = dtype == SD_DT_F16 ? 8 : 4;
   SD_CHECK_ARG(C % vec == 0 && ldx % vec == 0 && ldr % vec == 0 && ldy % vec == 0 && r_col0 % vec == 0 && y_col0 % vec == 0,
-               "sd_se_scale_residual: C / strides / column offsets must be multiples of %d", vec);
-  SD_CHECK_ARG(sd_aligned16(x) && sd_aligned16(res) && sd_aligned16(y), "sd_se_scale_residual: x / res / y must be 16-byte aligned");
+               "%s: C / strides / column offsets must be multiples of %d", fn, vec);
+  SD_CHECK_ARG(sd_aligned16(x) && sd_aligned16(res) && sd_aligned16(y), "%s: x / res / y must be 16-byte aligned", fn);
+  const int M = sg.packed ? sg.M : sg.B * sg.T;
   const int groups = C / vec;
   const int rpp = 256 / (groups < 256 ? groups : 256);
   long blocks = ((long)M + rpp - 1) / rpp;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == SD_DT_F16)
-    hipLaunchKernelGGL(se_scale_residual_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(x), ldx, gate,
-                       static_cast<const _Float16*>(res), ldr, r_col0, static_cast<_Float16*>(y), ldy, y_col0, M, T, C);
-  else
-    hipLaunchKernelGGL(se_scale_residual_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(x), ldx, gate,
-                       static_cast<const float*>(res), ldr, r_col0, static_cast<float*>(y), ldy, y_col0, M, T, C,
-                       static_cast<_Float16*>(ys), lds, s_col0, static_cast<const _Float16*>(res_split), ld_rs, rs_col0, write_y);
+  launch_as(dtype, sg, [&](auto* tp, auto rows) {
+    using T = std::remove_pointer_t<decltype(tp)>;
+    hipLaunchKernelGGL((se_scale_residual_kernel<T, decltype(rows)>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const T*>(x), ldx, gate,
+                       static_cast<const T*>(res), ldr, r_col0, static_cast<T*>(y), ldy, y_col0, M, rows, C, static_cast<_Float16*>(ys), lds, s_col0,
+                       static_cast<const _Float16*>(res_split), ld_rs, rs_col0, write_y);
+  });
   SD_CHECK_LAUNCH("se_scale_residual_kernel");
   return SD_OK;
 }
 
+int sd_asp_pool(const void* logit, int ldl, const void* h, int dtype, int ldh, const SdSegs& sg, int C, float eps, float* out, sd_stream_t stream) {
+  const char* fn = sg.packed ? "sd_asp_pool_packed_dt" : "sd_asp_pool";
+  bool empty;
+  if (int e = check_segs(fn, sg, empty)) return e;
+  if (empty) return SD_OK;
+  if (int e = check_cl_dt(fn, "(logit)", logit, dtype, ldl, 0, C)) return e;
+  if (int e = check_cl_dt(fn, "(h)", h, dtype, ldh, 0, C)) return e;
+  SD_CHECK_ARG(out && sd_aligned16(out), "%s: null or unaligned output", fn);
+  const int apc = dtype == SD_DT_F16 ? AspTile<_Float16>::APC : AspTile<float>::APC;
+  const size_t lds = (((size_t)2 * sg.T * 128 + 15) & ~(size_t)15) + (size_t)2 * 256 * sizeof(float);   // 128-byte tile rows
+  const bool staged = !sg.packed && C % apc == 0 && lds <= 64 * 1024;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_as(dtype, sg, [&](auto* tp, auto rows) {
+    using T = std::remove_pointer_t<decltype(tp)>;
+    using Rows = decltype(rows);
+    const T* lt = static_cast<const T*>(logit);
+    const T* ht = static_cast<const T*>(h);
+    if constexpr (!Rows::packed)
+      if (staged) {
+        hipLaunchKernelGGL(asp_pool_lds_kernel<T>, dim3(C / apc, sg.B), dim3(256), lds, s, lt, ldl, ht, ldh, sg.T, C, eps, out, sg.rel_len);
+        return;
+      }
+    hipLaunchKernelGGL((asp_pool_kernel<T, Rows>), dim3((C / 4 + CG - 1) / CG, sg.B), dim3(256), 0, s, lt, ldl, ht, ldh, rows, C, eps, out);
+  });
+  SD_CHECK_LAUNCH(staged ? "asp_pool_lds_kernel" : "asp_pool_kernel");
+  return SD_OK;
+}
+
+extern "C" int sd_seg_mean_std_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, int C, int want_std, float eps,
+                                  float* out, sd_stream_t stream) {
+  return sd_seg_mean_std(x, x_dtype, ld, col0, sd_uniform_segs(B, T), C, want_std, eps, out, stream);
+}
+
+// rel_len (device f32 [B], may be NULL = all ones): each segment's statistics over its first sd_mask_frames(rel_len[b], T) rows
+extern "C" int sd_seg_mean_std_lens_dt(const void* x, int x_dtype, int ld, int col0, int B, int T, const float* rel_len, int C, int want_std,
+                                       float eps, float* out, sd_stream_t stream) {
+  return sd_seg_mean_std(x, x_dtype, ld, col0, sd_uniform_segs(B, T, rel_len), C, want_std, eps, out, stream);
+}
+
+extern "C" int sd_seg_mean_std_packed_dt(const void* x, int x_dtype, int ld, int col0, const int* frame_start_dev, int B, int M, int C,
+                                         int want_std, float eps, float* out, sd_stream_t stream) {
+  return sd_seg_mean_std(x, x_dtype, ld, col0, sd_packed_segs(frame_start_dev, B, M), C, want_std, eps, out, stream);
+}
+
+extern "C" int sd_seg_mean_f32(const float* x, int ld, int col0, int B, int T, int C, float* mean, sd_stream_t stream) {
+  return sd_seg_mean_std(x, SD_DT_F32, ld, col0, sd_uniform_segs(B, T), C, 0, 0.f, mean, stream);
+}
+
+extern "C" int sd_seg_mean_std_f32(const float* x, int ld, int col0, int B, int T, int C, float eps, float* stats,
+                                   sd_stream_t stream) {
+  return sd_seg_mean_std(x, SD_DT_F32, ld, col0, sd_uniform_segs(B, T), C, 1, eps, stats, stream);
+}
+
+extern "C" int sd_se_scale_residual_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0,
+                                       void* y, int ldy, int y_col0, int B, int T, int C, int dtype, sd_stream_t stream) {
+  return sd_se_scale_residual(x, ldx, gate, res, ldr, r_col0, y, ldy, y_col0, sd_uniform_segs(B, T), C, dtype, stream);
+}
+
+extern "C" int sd_se_scale_residual_packed_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy,
+                                              int y_col0, const int* frame_start_dev, int B, int M, int C, int dtype, sd_stream_t stream) {
+  return sd_se_scale_residual(x, ldx, gate, res, ldr, r_col0, y, ldy, y_col0, sd_packed_segs(frame_start_dev, B, M), C, dtype, stream);
+}
+
 extern "C" int sd_se_scale_residual_f32(const float* x, int ldx, const float* gate, const float* res, int ldr, int r_col0,
                                         float* y, int ldy, int y_col0, int B, int T, int C, sd_stream_t stream) {
-  return sd_se_scale_residual_dt(x, ldx, gate, res, ldr, r_col0, y, ldy, y_col0, B, T, C, SD_DT_F32, stream);
+  return sd_se_scale_residual(x, ldx, gate, res, ldr, r_col0, y, ldy, y_col0, sd_uniform_segs(B, T), C, SD_DT_F32, stream);
+}
+
+extern "C" int sd_asp_pool_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, int C, float eps,
+                              float* out, sd_stream_t stream) {
+  return sd_asp_pool(logit, ldl, h, dtype, ldh, sd_uniform_segs(B, T), C, eps, out, stream);
+}
+
+// rel_len (device f32 [B], may be NULL = all ones): softmax and statistics over the first sd_mask_frames(rel_len[b], T) frames
+extern "C" int sd_asp_pool_lens_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, const float* rel_len, int C,
+                                   float eps, float* out, sd_stream_t stream) {
+  return sd_asp_pool(logit, ldl, h, dtype, ldh, sd_uniform_segs(B, T, rel_len), C, eps, out, stream);
+}
+
+extern "C" int sd_asp_pool_packed_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, const int* frame_start_dev, int B, int M, int C,
+                                     float eps, float* out, sd_stream_t stream) {
+  return sd_asp_pool(logit, ldl, h, dtype, ldh, sd_packed_segs(frame_start_dev, B, M), C, eps, out, stream);
 }
 
 extern "C" size_t sd_colstat_floats(int M, int cout) {
@@ -652,104 +651,6 @@ int sd_colstat_finish_rows(const float* colstat, const float* pivot, const void*
   return SD_OK;
 }
 
-extern "C" int sd_asp_pool_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, int C, float eps,
-                              float* out, sd_stream_t stream) {
-  return sd_asp_pool_lens_dt(logit, ldl, h, dtype, ldh, B, T, nullptr, C, eps, out, stream);
-}
-
-// rel_len (device f32 [B], may be NULL = all ones): softmax and statistics over the first sd_mask_frames(rel_len[b], T) frames
-extern "C" int sd_asp_pool_lens_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, int B, int T, const float* rel_len, int C,
-                                   float eps, float* out, sd_stream_t stream) {
-  if (int e = check_cl_dt("sd_asp_pool(logit)", logit, dtype, ldl, 0, C)) return e;
-  if (int e = check_cl_dt("sd_asp_pool(h)", h, dtype, ldh, 0, C)) return e;
-  SD_CHECK_ARG(B > 0 && T > 0 && out && sd_aligned16(out), "sd_asp_pool: B=%d T=%d / null or unaligned output", B, T);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool half = dtype == SD_DT_F16;
-  const int apc = half ? AspTile<_Float16>::APC : AspTile<float>::APC;
-  const size_t lds = (((size_t)2 * T * 128 + 15) & ~(size_t)15) + (size_t)2 * 256 * sizeof(float);   // 128-byte tile rows
-  const _Float16* lh = static_cast<const _Float16*>(logit); const _Float16* hh = static_cast<const _Float16*>(h);
-  const float* lf = static_cast<const float*>(logit); const float* hf = static_cast<const float*>(h);
-  if (C % apc == 0 && lds <= 64 * 1024) {
-    dim3 g2(C / apc, B);
-    if (half) hipLaunchKernelGGL(asp_pool_lds_kernel<_Float16>, g2, dim3(256), lds, s, lh, ldl, hh, ldh, T, C, eps, out, rel_len);
-    else hipLaunchKernelGGL(asp_pool_lds_kernel<float>, g2, dim3(256), lds, s, lf, ldl, hf, ldh, T, C, eps, out, rel_len);
-    SD_CHECK_LAUNCH("asp_pool_lds_kernel");
-    return SD_OK;
-  }
-  dim3 grid((C / 4 + CG - 1) / CG, B);
-  if (half) hipLaunchKernelGGL(asp_pool_kernel<_Float16>, grid, dim3(256), 0, s, lh, ldl, hh, ldh, T, C, eps, out, rel_len);
-  else hipLaunchKernelGGL(asp_pool_kernel<float>, grid, dim3(256), 0, s, lf, ldl, hf, ldh, T, C, eps, out, rel_len);
-  SD_CHECK_LAUNCH("asp_pool_kernel");
-  return SD_OK;
-}
-
-// ---- packed spans: the three statistics / gating operators over spans [frame_start[s], frame_start[s + 1]) of M rows
-#define SD_PACKED_SPANS(fn)                                                                                                  \
-  SD_CHECK_ARG(B >= 0 && B < 65536, fn ": B=%d (0 .. 65535)", B);                                                           \
-  if (B == 0) return SD_OK;                                                                                                 \
-  SD_CHECK_ARG(M > 0 && frame_start_dev != nullptr, fn ": M=%d, frame_start %p", M, (const void*)frame_start_dev)
-
-extern "C" int sd_seg_mean_std_packed_dt(const void* x, int x_dtype, int ld, int col0, const int* frame_start_dev, int B, int M, int C,
-                                         int want_std, float eps, float* out, sd_stream_t stream) {
-  SD_PACKED_SPANS("sd_seg_mean_std_packed_dt");
-  if (int e = check_cl_dt("sd_seg_mean_std_packed_dt", x, x_dtype, ld, col0, C)) return e;
-  SD_CHECK_ARG(out && sd_aligned16(out), "sd_seg_mean_std_packed_dt: null or unaligned output");
-  const dim3 grid((C / 4 + CG - 1) / CG, B);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (x_dtype == SD_DT_F16)
-    hipLaunchKernelGGL(seg_mean_std_packed_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(x), ld, col0, frame_start_dev, M, C,
-                       want_std, eps, out);
-  else
-    hipLaunchKernelGGL(seg_mean_std_packed_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), ld, col0, frame_start_dev, M, C,
-                       want_std, eps, out);
-  SD_CHECK_LAUNCH("seg_mean_std_packed_kernel");
-  return SD_OK;
-}
-
-extern "C" int sd_se_scale_residual_packed_dt(const void* x, int ldx, const float* gate, const void* res, int ldr, int r_col0, void* y, int ldy,
-                                              int y_col0, const int* frame_start_dev, int B, int M, int C, int dtype, sd_stream_t stream) {
-  SD_PACKED_SPANS("sd_se_scale_residual_packed_dt");
-  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(x)", x, dtype, ldx, 0, C)) return e;
-  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(res)", res, dtype, ldr, r_col0, C)) return e;
-  if (int e = check_cl_dt("sd_se_scale_residual_packed_dt(y)", y, dtype, ldy, y_col0, C)) return e;
-  SD_CHECK_ARG(gate && sd_aligned16(gate), "sd_se_scale_residual_packed_dt: null or unaligned gate");
-  const int vec = dtype == SD_DT_F16 ? 8 : 4;
-  SD_CHECK_ARG(C % vec == 0 && ldx % vec == 0 && ldr % vec == 0 && ldy % vec == 0 && r_col0 % vec == 0 && y_col0 % vec == 0,
-               "sd_se_scale_residual_packed_dt: C / strides / column offsets must be multiples of %d", vec);
-  SD_CHECK_ARG(sd_aligned16(x) && sd_aligned16(res) && sd_aligned16(y), "sd_se_scale_residual_packed_dt: x / res / y must be 16-byte aligned");
-  const int groups = C / vec;
-  const int rpp = 256 / (groups < 256 ? groups : 256);
-  long blocks = ((long)M + rpp - 1) / rpp;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == SD_DT_F16)
-    hipLaunchKernelGGL(se_scale_residual_packed_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(x), ldx, gate,
-                       static_cast<const _Float16*>(res), ldr, r_col0, static_cast<_Float16*>(y), ldy, y_col0, frame_start_dev, B, M, C);
-  else
-    hipLaunchKernelGGL(se_scale_residual_packed_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(x), ldx, gate,
-                       static_cast<const float*>(res), ldr, r_col0, static_cast<float*>(y), ldy, y_col0, frame_start_dev, B, M, C);
-  SD_CHECK_LAUNCH("se_scale_residual_packed_kernel");
-  return SD_OK;
-}
-
-extern "C" int sd_asp_pool_packed_dt(const void* logit, int ldl, const void* h, int dtype, int ldh, const int* frame_start_dev, int B, int M, int C,
-                                     float eps, float* out, sd_stream_t stream) {
-  SD_PACKED_SPANS("sd_asp_pool_packed_dt");
-  if (int e = check_cl_dt("sd_asp_pool_packed_dt(logit)", logit, dtype, ldl, 0, C)) return e;
-  if (int e = check_cl_dt("sd_asp_pool_packed_dt(h)", h, dtype, ldh, 0, C)) return e;
-  SD_CHECK_ARG(out && sd_aligned16(out), "sd_asp_pool_packed_dt: null or unaligned output");
-  const dim3 grid((C / 4 + CG - 1) / CG, B);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == SD_DT_F16)
-    hipLaunchKernelGGL(asp_pool_packed_kernel<_Float16>, grid, dim3(256), 0, s, static_cast<const _Float16*>(logit), ldl,
-                       static_cast<const _Float16*>(h), ldh, frame_start_dev, M, C, eps, out);
-  else
-    hipLaunchKernelGGL(asp_pool_packed_kernel<float>, grid, dim3(256), 0, s, static_cast<const float*>(logit), ldl, static_cast<const float*>(h), ldh,
-                       frame_start_dev, M, C, eps, out);
-  SD_CHECK_LAUNCH("asp_pool_packed_kernel");
-  return SD_OK;
-}
-#undef SD_PACKED_SPANS
 
 __global__ __launch_bounds__(256) void wav_lens_frames_kernel(const float* rel_len, int B, int T, int* n_norm, int* n_mask) {
   const int b = blockIdx.x * 256 + threadIdx.x;
@@ -771,7 +672,7 @@ extern "C" int sd_wav_lens_frames(const float* rel_len_dev, int B, int T, int* n
 
 extern "C" int sd_asp_pool_f32(const float* logit, int ldl, const float* h, int ldh, int B, int T, int C, float eps,
                                float* out, sd_stream_t stream) {
-  return sd_asp_pool_dt(logit, ldl, h, SD_DT_F32, ldh, B, T, C, eps, out, stream);
+  return sd_asp_pool(logit, ldl, h, SD_DT_F32, ldh, sd_uniform_segs(B, T), C, eps, out, stream);
 }
 
 extern "C" int sd_l2norm_rows_f32(const float* x, int ldx, int N, int D, float eps_add, int sklearn_zero_guard,

@@ -47,6 +47,28 @@ def _dt(t: torch.dtype) -> int:
     raise TypeError(f"unsupported dtype {t}")
 
 
+def _conv_args(x: int, lda: int, a_col0: int, x_dtype: int, w: int, w_dtype: int, y: int, ldo: int, o_col0: int, y_dtype: int, M: int, T: int,
+               cin: int, cin_pad: int, cout: int, taps: int, dil: int, *, bias=None, bias_per_seg=False, act=None, act2=None, scale=None, shift=None,
+               tee=None, tee_lo: int = 0, tee_hi: int = 0, tee_add=None, ta_col0: int = 0, colstat=None) -> N.sd_conv_args:
+    """One `sd_conv_args` (x / w / y: device pointers; the optional vectors and buffers: tensors or None)."""
+    a = N.sd_conv_args()
+    a.x, a.lda, a.a_col0, a.x_dtype = x, lda, a_col0, x_dtype
+    a.w, a.w_dtype = w, w_dtype
+    a.y, a.ldo, a.o_col0, a.y_dtype = y, ldo, o_col0, y_dtype
+    a.M, a.T = M, T
+    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cin_pad, cout, taps, dil
+    a.bias, a.bias_per_seg = _ptr(bias), int(bool(bias_per_seg))
+    a.act, a.act2 = _ACT[act], _ACT[act2]
+    a.scale, a.shift = _ptr(scale), _ptr(shift)
+    if tee is not None:
+        a.tee, a.ldt, a.tee_lo, a.tee_hi = tee.data_ptr(), tee.stride(0), tee_lo, tee_hi
+        if tee_add is not None:
+            a.tee_add, a.ld_ta, a.ta_col0 = tee_add.data_ptr(), tee_add.stride(0), ta_col0
+    if colstat is not None:
+        a.colstat = colstat.data_ptr()
+    return a
+
+
 def conv1d_cl(x: torch.Tensor, w_packed: torch.Tensor, T: int, *, cin: int, dil: int = 1, bias=None, bias_per_seg=False,
               act=None, scale=None, shift=None, act2=None, a_col0: int = 0, out: torch.Tensor | None = None,
               o_col0: int = 0, tee: torch.Tensor | None = None, tee_lo: int = 0, tee_hi: int = 0,
@@ -63,27 +85,14 @@ def conv1d_cl(x: torch.Tensor, w_packed: torch.Tensor, T: int, *, cin: int, dil:
     half = w_packed.dtype == torch.float16
     if out is None:
         out = torch.empty((M, cout), dtype=out_dtype or (torch.float16 if half else torch.float32), device=x.device)
-    a = N.sd_conv_args()
-    a.x, a.lda, a.a_col0 = x.data_ptr(), x.stride(0), a_col0
-    a.w, a.w_dtype = w_packed.data_ptr(), _dt(w_packed.dtype)
-    a.x_dtype, a.y_dtype = _dt(x.dtype), _dt(out.dtype)
     for extra in (tee, tee_add):
         if extra is not None and extra.dtype != out.dtype:
             raise TypeError("tee / tee_add must have the output dtype")
-    a.y, a.ldo, a.o_col0 = out.data_ptr(), out.stride(0), o_col0
-    a.M, a.T = M, T
-    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cin_pad, cout, taps, dil
-    a.bias, a.bias_per_seg = _ptr(bias), int(bool(bias_per_seg))
-    a.act, a.act2 = _ACT[act], _ACT[act2]
-    a.scale, a.shift = _ptr(scale), _ptr(shift)
-    if tee is not None:
-        a.tee, a.ldt, a.tee_lo, a.tee_hi = tee.data_ptr(), tee.stride(0), tee_lo, tee_hi
-        if tee_add is not None:
-            a.tee_add, a.ld_ta, a.ta_col0 = tee_add.data_ptr(), tee_add.stride(0), ta_col0
-    if colstat is not None:
-        if colstat.dtype != torch.float32 or colstat.numel() < colstat_floats(M, cout):
-            raise ValueError("colstat must be f32 with colstat_floats(M, cout) elements")
-        a.colstat = colstat.data_ptr()
+    if colstat is not None and (colstat.dtype != torch.float32 or colstat.numel() < colstat_floats(M, cout)):
+        raise ValueError("colstat must be f32 with colstat_floats(M, cout) elements")
+    a = _conv_args(x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype), w_packed.data_ptr(), _dt(w_packed.dtype), out.data_ptr(), out.stride(0), o_col0,
+                   _dt(out.dtype), M, T, cin, cin_pad, cout, taps, dil, bias=bias, bias_per_seg=bias_per_seg, act=act, act2=act2, scale=scale,
+                   shift=shift, tee=tee, tee_lo=tee_lo, tee_hi=tee_hi, tee_add=tee_add, ta_col0=ta_col0, colstat=colstat)
     with torch.cuda.device(x.device):
         fn, name = (lib.sd_conv1d_cl_f16, "sd_conv1d_cl_f16") if half else (lib.sd_conv1d_cl_f32, "sd_conv1d_cl_f32")
         N.check(fn(C.byref(a), _stream(x)), name)
@@ -108,19 +117,9 @@ def conv1d_cl_packed(x: torch.Tensor, w_packed: torch.Tensor, frame_start, *, ci
     fs, B = _span_table(frame_start, x.device)
     if out is None:
         out = torch.empty((M, cout), dtype=torch.float32, device=x.device)
-    a = N.sd_conv_args()
-    a.x, a.lda, a.a_col0, a.x_dtype = x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype)
-    a.w, a.w_dtype = w_packed.data_ptr(), _dt(w_packed.dtype)
-    a.y, a.ldo, a.o_col0, a.y_dtype = out.data_ptr(), out.stride(0), o_col0, _dt(out.dtype)
-    a.M, a.T = M, M
-    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cin_pad, cout, taps, dil
-    a.bias, a.bias_per_seg = _ptr(bias), int(bool(bias_per_seg))
-    a.act, a.act2 = _ACT[act], _ACT[act2]
-    a.scale, a.shift = _ptr(scale), _ptr(shift)
-    if tee is not None:
-        a.tee, a.ldt, a.tee_lo, a.tee_hi = tee.data_ptr(), tee.stride(0), tee_lo, tee_hi
-        if tee_add is not None:
-            a.tee_add, a.ld_ta, a.ta_col0 = tee_add.data_ptr(), tee_add.stride(0), ta_col0
+    a = _conv_args(x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype), w_packed.data_ptr(), _dt(w_packed.dtype), out.data_ptr(), out.stride(0), o_col0,
+                   _dt(out.dtype), M, M, cin, cin_pad, cout, taps, dil, bias=bias, bias_per_seg=bias_per_seg, act=act, act2=act2, scale=scale,
+                   shift=shift, tee=tee, tee_lo=tee_lo, tee_hi=tee_hi, tee_add=tee_add, ta_col0=ta_col0)
     with torch.cuda.device(x.device):
         N.check(N.load().sd_conv1d_cl_packed_f32(C.byref(a), fs.data_ptr(), B, _stream(x)), "sd_conv1d_cl_packed_f32")
     return out
@@ -177,16 +176,8 @@ def seg_gemm(x: torch.Tensor, w_packed: torch.Tensor, *, cin: int, bias=None, ac
     need = int(lib.sd_seg_gemm_scratch_bytes(M, cin_pad, cout))
     if scratch is None and need:
         scratch = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    a = N.sd_conv_args()
-    a.x, a.lda, a.a_col0 = x.data_ptr(), x.stride(0), 0
-    a.w, a.w_dtype = w_packed.data_ptr(), N.SD_DT_F32
-    a.x_dtype, a.y_dtype = N.SD_DT_F32, N.SD_DT_F32
-    a.y, a.ldo, a.o_col0 = out.data_ptr(), out.stride(0), 0
-    a.M, a.T = M, 1
-    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cin_pad, cout, 1, 1
-    a.bias, a.bias_per_seg = _ptr(bias), 0
-    a.act, a.act2 = _ACT[act], _ACT[act2]
-    a.scale, a.shift = _ptr(scale), _ptr(shift)
+    a = _conv_args(x.data_ptr(), x.stride(0), 0, N.SD_DT_F32, w_packed.data_ptr(), N.SD_DT_F32, out.data_ptr(), out.stride(0), 0, N.SD_DT_F32,
+                   M, 1, cin, cin_pad, cout, 1, 1, bias=bias, act=act, act2=act2, scale=scale, shift=shift)
     with torch.cuda.device(x.device):
         N.check(lib.sd_seg_gemm_f32(C.byref(a), scratch.data_ptr() if scratch is not None else None,
                                     scratch.numel() * 4 if scratch is not None else 0, _stream(x)), "sd_seg_gemm_f32")
@@ -234,45 +225,32 @@ def conv1d_cl_split16(x: torch.Tensor, w_split: torch.Tensor, w_shift: int, T: i
     if out is None:
         out = torch.empty((M, cout), dtype=torch.float32, device=x.device)
     f = float(2.0 ** w_shift)
-    a = N.sd_conv_args()
     if narrow:
         if x.dtype != torch.float32 or x.stride(1) != 1:
             raise TypeError("x must be f32 with contiguous channels")
         keep = (x,)
-        a.x, a.lda, a.a_col0, a.x_dtype = x.data_ptr(), x.stride(0), a_col0, N.SD_DT_F32
-        a.bias, a.scale = _ptr(bias), _ptr(scale)
-        a.w_scale_inv = 1.0 / f
+        xp, lda, xcol, xdt, bias_k, scale_k = x.data_ptr(), x.stride(0), a_col0, N.SD_DT_F32, bias, scale
     else:
         if bias_per_seg or act2 is not None or tee_add is not None:
             raise ValueError("per-segment bias / act2 / tee_add belong to the narrow kernel (narrow=True)")
         xs = split16_pack(x, a_col0, cin)
-        bias_s = None if bias is None else bias * f
-        scale_s = (torch.full((cout,), 1.0 / f, dtype=torch.float32, device=x.device) if scale is None else scale / f)
-        keep = (xs, bias_s, scale_s)
-        a.x, a.lda, a.a_col0, a.x_dtype = xs.data_ptr(), cp, 0, N.SD_DT_SPLIT16
-        a.bias, a.scale = _ptr(bias_s), _ptr(scale_s)
-    a.w, a.w_dtype = w_split.data_ptr(), N.SD_DT_SPLIT16
-    a.y_dtype = N.SD_DT_F32
-    a.y, a.ldo, a.o_col0 = out.data_ptr(), out.stride(0), o_col0
+        bias_k = None if bias is None else bias * f
+        scale_k = (torch.full((cout,), 1.0 / f, dtype=torch.float32, device=x.device) if scale is None else scale / f)
+        keep = (xs, bias_k, scale_k)
+        xp, lda, xcol, xdt = xs.data_ptr(), cp, 0, N.SD_DT_SPLIT16
+    yp, ldo, ydt = out.data_ptr(), out.stride(0), N.SD_DT_F32
     if out_split is not None:
         # y leaves as SD_DT_SPLIT16 rows (f16 [M, 2 * ld], ld VALUE columns, a multiple of 32) instead of f32 --
         # bit for bit what split16_pack would make of the f32 result; `out` is then not written
         if out_split.dtype != torch.float16 or out_split.stride(1) != 1 or out_split.shape[1] % 64 or colstat is not None:
             raise TypeError("out_split: f16 [M, 2 * ld] with ld % 32 == 0, no colstat")
         _need_cuda(out_split)
-        a.y_dtype = N.SD_DT_SPLIT16
-        a.y, a.ldo = out_split.data_ptr(), out_split.shape[1] // 2
-    a.M, a.T = M, T
-    a.cin, a.cin_pad, a.cout, a.taps, a.dil = cin, cp, cout, taps, dil
-    a.bias_per_seg = int(bool(bias_per_seg))
-    a.act, a.act2 = _ACT[act], _ACT[act2]
-    a.shift = _ptr(shift)
-    if tee is not None:
-        a.tee, a.ldt, a.tee_lo, a.tee_hi = tee.data_ptr(), tee.stride(0), tee_lo, tee_hi
-        if tee_add is not None:
-            a.tee_add, a.ld_ta, a.ta_col0 = tee_add.data_ptr(), tee_add.stride(0), ta_col0
-    if colstat is not None:
-        a.colstat = colstat.data_ptr()
+        yp, ldo, ydt = out_split.data_ptr(), out_split.shape[1] // 2, N.SD_DT_SPLIT16
+    a = _conv_args(xp, lda, xcol, xdt, w_split.data_ptr(), N.SD_DT_SPLIT16, yp, ldo, o_col0, ydt, M, T, cin, cp, cout, taps, dil, bias=bias_k,
+                   bias_per_seg=bias_per_seg, act=act, act2=act2, scale=scale_k, shift=shift, tee=tee, tee_lo=tee_lo, tee_hi=tee_hi, tee_add=tee_add,
+                   ta_col0=ta_col0, colstat=colstat)
+    if narrow:
+        a.w_scale_inv = 1.0 / f
     with torch.cuda.device(x.device):
         N.check(lib.sd_conv1d_cl_split16(C.byref(a), _stream(x)), "sd_conv1d_cl_split16")
     del keep

@@ -156,6 +156,37 @@ def test_packed_reductions_match_f64(dev, conv_kernel):
         assert (y[fs[s]:fs[s + 1]] - (xs * gate[s] + res[fs[s]:fs[s + 1]])).abs().max() < 1e-5
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_equal_spans_are_bitwise_the_uniform_reductions(dev, dtype):
+    """One kernel per operator, two segment maps: spans of one length, in a pack big enough for the uniform operators' 64 x 4 shape
+    (C = 1024, B = 64: grid.x * B = 256) and, at T = 300, their streaming pooling kernel (a segment's tile above the LDS kernel's 64 KB),
+    give bitwise the uniform operator's result."""
+    from speech_diarization_amd import _native as N, ops
+    lib = N.load()
+    B, Cc, dt = 64, 1024, ops._dt(dtype)
+    g = torch.Generator().manual_seed(21)
+    for T in (37, 300):
+        M = B * T
+        fs = np.arange(B + 1, dtype=np.int32) * T
+        x = torch.randn(M, Cc, generator=g).to(dev, dtype)
+        s = ops._stream(x)
+        if T == 37:
+            st = torch.empty(B, 2 * Cc, device=dev)
+            N.check(lib.sd_seg_mean_std_dt(x.data_ptr(), dt, Cc, 0, B, T, Cc, 1, C.c_float(1e-12), st.data_ptr(), s), "sd_seg_mean_std_dt")
+            assert torch.equal(ops.seg_mean_std_packed(x, fs), st)
+            gate = torch.rand(B, Cc, generator=g).to(dev)
+            res = torch.randn(M, Cc, generator=g).to(dev, dtype)
+            y = torch.empty_like(x)
+            N.check(lib.sd_se_scale_residual_dt(x.data_ptr(), Cc, gate.data_ptr(), res.data_ptr(), Cc, 0, y.data_ptr(), Cc, 0, B, T, Cc, dt, s),
+                    "sd_se_scale_residual_dt")
+            assert torch.equal(ops.se_scale_residual_packed(x, gate, res, fs), y)
+        else:
+            lg = torch.randn(M, Cc, generator=g).to(dev, dtype)
+            pool = torch.empty(B, 2 * Cc, device=dev)
+            N.check(lib.sd_asp_pool_dt(lg.data_ptr(), Cc, x.data_ptr(), dt, Cc, B, T, Cc, C.c_float(1e-12), pool.data_ptr(), s), "sd_asp_pool_dt")
+            assert torch.equal(ops.asp_pool_packed(lg, x, fs), pool)
+
+
 # ------------------------------------------------------------------ 3 - 8. the whole path
 
 _CACHE = {}
