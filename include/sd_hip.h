@@ -371,6 +371,7 @@ int sd_res2net_chain_supported(int T, int chunk, int n, int taps, int dil);
 size_t sd_res2net_chain_workspace_bytes(int n);     /* the n convs' weights in MFMA-fragment order (re-made by every call) */
 int sd_res2net_chain_f16(void* r, int ld, int B, int T, const sd_layer* layers, int n, void* ws, size_t ws_bytes, sd_stream_t stream);
 
+/* bytes of workspace of a forward; never shrinks as B or T grow, so a workspace sized for the largest call serves every smaller one */
 size_t sd_ecapa_workspace_bytes(const sd_ecapa_weights* w, int B, int T);
 
 /* feats: device f32 [B][T][n_mels] (mean-normalised fbank); emb: device f32 [B][emb_dim] */

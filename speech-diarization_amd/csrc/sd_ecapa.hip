@@ -67,14 +67,17 @@ Buffers carve(const sd_ecapa_weights* w, int B, size_t M, void* ws, int act_dtyp
   b.stats = static_cast<float*>(c.take((size_t)B * 2 * Cm, 4));
   b.gbias = static_cast<float*>(c.take((size_t)B * w->att_channels, 4));
   b.pooled = static_cast<float*>(c.take((size_t)B * 2 * Cm, 4));
-  // scratch of the grid split-K (M <= 256 rows): the largest of the three per-segment layers that use it (final FC at B = 256: 4.7 MB)
-  b.skp_bytes = 0;
-  if (B <= 256) {
-    size_t need = sd_seg_gemm_scratch_bytes(B, w->fc.cin_pad, w->fc.cout);
-    const size_t g = sd_seg_gemm_scratch_bytes(B, w->asp_tdnn_g.cin_pad, w->asp_tdnn_g.cout);
+  // scratch of the grid split-K (M <= 256 rows): the largest of the three per-segment layers that use it (final FC at B = 256: 4.7 MB).
+  // Above 256 rows the layers take the plain operator and the scratch is idle, but its 256-row share stays reserved: a caller sizes one
+  // workspace for its largest micro-batch and runs a shorter last one in it, so the size must never shrink as B grows (it dropped by
+  // this share from B = 256 to 257, and a workspace sized for 257 .. 286 rows refused the <= 256-row remainder with SD_ERR_WORKSPACE)
+  {
+    const int Bs = B < 256 ? B : 256;
+    size_t need = sd_seg_gemm_scratch_bytes(Bs, w->fc.cin_pad, w->fc.cout);
+    const size_t g = sd_seg_gemm_scratch_bytes(Bs, w->asp_tdnn_g.cin_pad, w->asp_tdnn_g.cout);
     need = g > need ? g : need;
     for (int i = 0; i < w->n_blocks; ++i) {
-      const size_t s1 = sd_seg_gemm_scratch_bytes(B, w->blocks[i].se1.cin_pad, w->blocks[i].se1.cout);
+      const size_t s1 = sd_seg_gemm_scratch_bytes(Bs, w->blocks[i].se1.cin_pad, w->blocks[i].se1.cout);
       need = s1 > need ? s1 : need;
     }
     b.skp_bytes = (need + 255) & ~(size_t)255;

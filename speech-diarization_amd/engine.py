@@ -273,6 +273,8 @@ class EmbeddingEngine:
     # -- workspace: feats + fbank scratch + ECAPA activations, three flat buffers that only ever grow (keyed by
     # capacity, not by the exact (B, n): the reference's callers send batches whose padded length changes every call
     # [REF anti_stick_diarize.py:163-166], and re-allocating ~10 MB per segment per call was a measurable part of it)
+    # Sized once per call for the largest micro-batch; the shorter last one runs in the same buffers: the sizing functions never shrink
+    # as B grows (tests/test_buffer_rules.py)
     def _workspace(self, B: int, n: int):
         T = FbankPlan.num_frames(n)
         n_mels = self.weights.cfg.input_size

@@ -4,10 +4,16 @@ All calls go through the C ABI (ctypes -> libsd_hip.so).  Tolerances are stated 
 the operators are exact-f32 (fma chains on the f32 matrix cores), the references are
 float64, so the bound is f32 rounding of a K-term sum.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from kernel_selection import conv_kernel  # noqa: E402,F401  (the eight selections of the exact-f32 conv, shared fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,29 +28,6 @@ def _ref_conv_cl(x, w, b, T, dil):
         xt = F.pad(xt, (pad, pad), mode="reflect")
     y = F.conv1d(xt, w, b, dilation=dil)
     return y.transpose(1, 2).reshape(M, -1)
-
-
-@pytest.fixture(params=["auto", "split32", "tiles128", "tiles64", "rows80", "rows96", "rows112", "wide256"])
-def conv_kernel(request):
-    """Small launches pick the 32x32 split-K kernel by themselves; "tiles128" pins the 128x128 kernel so that
-    both implementations of the operator see every case."""
-    from speech_diarization_amd import _native as N
-    lib = N.load()
-    # "auto": small launches take the 64x64 ring kernel (time-axis convs) or the 32x32 split-K kernel (per-segment layers);
-    # "split32": the 32x32 split-K kernel for both
-    N.check(lib.sd_set_tuning(N.SD_TUNE_S64_TILES, 0 if request.param != "auto" else -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_SKINNY_TILES, 0 if request.param not in ("auto", "split32") else -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_WIDE_TILES, 0 if request.param == "wide256" else -1), "sd_set_tuning")   # cout >= 1024 layers: the 256x256 ring kernel
-    # 128x64 tiles: by the rule ("auto"), always ("tiles64"), never (the pinned kernels)
-    N.check(lib.sd_set_tuning(N.SD_TUNE_HALF_TILES, {"auto": -1, "split32": -1, "tiles64": 1}.get(request.param, 0)), "sd_set_tuning")
-    # tiles of 80 / 96 / 112 rows: by the rule ("auto"), that height wherever the layer allows ("rowsNN"), never (the pinned kernels)
-    N.check(lib.sd_set_tuning(N.SD_TUNE_TILE_ROWS, int(request.param[4:]) if request.param.startswith("rows") else (-1 if request.param in ("auto", "split32") else 0)), "sd_set_tuning")
-    yield request.param
-    N.check(lib.sd_set_tuning(N.SD_TUNE_HALF_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_TILE_ROWS, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_S64_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_SKINNY_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_WIDE_TILES, -1), "sd_set_tuning")
 
 
 @pytest.mark.parametrize("B,T,cin,cout,k,dil", [

@@ -5,11 +5,16 @@ At short T one 64 .. 256-row tile spans tens of segments and the reflect padding
 every segment: each operator is compared here with a float64 torch reference that pads with `F.pad(mode="reflect")` (so the reference
 itself refuses what speechbrain refuses), then the whole forward with `pipeline_ref.encode_batch_ref(..., float64)` at every precision."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from kernel_selection import conv_kernel  # noqa: E402,F401  (the eight selections of the exact-f32 conv, shared fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -69,25 +74,6 @@ def _conv_case(seed, B, T, cin, cout, k):
 
 
 # ------------------------------------------------------------------ 1. the exact-f32 conv, all eight kernel selections
-
-@pytest.fixture(params=["auto", "split32", "tiles128", "tiles64", "rows80", "rows96", "rows112", "wide256"])
-def conv_kernel(request):
-    """The selections of test_gpu_ops.py: "auto" (64x64 ring / 32x32 split-K for small launches), "split32", the 128x128 kernel,
-    128x64 tiles, tiles of 80 / 96 / 112 rows, and the 256x256 ring kernel for every cout >= 1024 layer; tuning restored afterwards."""
-    from speech_diarization_amd import _native as N
-    lib = N.load()
-    N.check(lib.sd_set_tuning(N.SD_TUNE_S64_TILES, 0 if request.param != "auto" else -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_SKINNY_TILES, 0 if request.param not in ("auto", "split32") else -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_WIDE_TILES, 0 if request.param == "wide256" else -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_HALF_TILES, {"auto": -1, "split32": -1, "tiles64": 1}.get(request.param, 0)), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_TILE_ROWS, int(request.param[4:]) if request.param.startswith("rows") else (-1 if request.param in ("auto", "split32") else 0)), "sd_set_tuning")
-    yield request.param
-    N.check(lib.sd_set_tuning(N.SD_TUNE_HALF_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_TILE_ROWS, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_S64_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_SKINNY_TILES, -1), "sd_set_tuning")
-    N.check(lib.sd_set_tuning(N.SD_TUNE_WIDE_TILES, -1), "sd_set_tuning")
-
 
 @pytest.mark.parametrize("B,T,cin,cout,k,dil", SHORT_SHAPES)
 def test_short_conv1d_cl_f32_matches_f64(dev, conv_kernel, B, T, cin, cout, k, dil):
