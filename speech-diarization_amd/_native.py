@@ -169,6 +169,15 @@ PROTOTYPES = {
     "sd_ecapa_forward_packed_f32": (_I, [C.POINTER(sd_ecapa_weights), _P, _P, _I, _I, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_spectral.h: the spectral-clustering entries, same shared object, a table and a version of their own
+SD_SPECTRAL_ABI_VERSION = 1
+SPECTRAL_PROTOTYPES = {
+    "sd_spectral_abi_version": (_I, []),
+    "sd_affinity_degree_f32": (_I, [_P, _I, C.c_long, _I, _P, _P]),
+    "sd_affinity_apply_workspace_bytes": (_Z, [_I, _I]),
+    "sd_affinity_apply_f32": (_I, [_P, _I, C.c_long, _I, _P, _P, _I, _I, _P, _I, _P, _Z, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -203,6 +212,15 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.sd_abi_version() != SD_ABI_VERSION:
             raise RuntimeError(f"libsd_hip.so ABI {lib.sd_abi_version()} != binding ABI {SD_ABI_VERSION}; rebuild")
+        missing = [name for name in SPECTRAL_PROTOTYPES if not hasattr(lib, name)]
+        if missing:
+            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_spectral.h: {missing}")
+        for name, (res, args) in SPECTRAL_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sd_spectral_abi_version() != SD_SPECTRAL_ABI_VERSION:
+            raise RuntimeError(f"libsd_hip.so spectral ABI {lib.sd_spectral_abi_version()} != binding ABI {SD_SPECTRAL_ABI_VERSION}; rebuild")
         for which, st in enumerate((sd_conv_args, sd_layer, sd_se_res2_block, sd_ecapa_weights)):
             if lib.sd_sizeof(which) != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__}: binding layout is {C.sizeof(st)} bytes, the library's {lib.sd_sizeof(which)}; rebuild")

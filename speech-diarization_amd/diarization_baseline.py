@@ -157,7 +157,10 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
     `world="dist"` (under torchrun, after `dist.init_from_env()`): BASELINE.json configs[2].  Every rank runs the
     host glue on the same audio, embeds only the windows `i mod W == rank` (`dist.shard_indices`), ONE
     `all_gather_into_tensor` returns the full [N, 192] in window order to every rank, every rank clusters
-    (deterministic, N x 192 is tiny), rank 0 writes the RTTM.  The result is identical to `world=None`."""
+    (deterministic, N x 192 is tiny), rank 0 writes the RTTM.  The result is identical to `world=None`.
+
+    `clustering`: "spectral" (default; eigengap + scikit-learn SpectralClustering on the host), "ahc", or "spectral_gpu": the two
+    spectral steps on the device (`cluster_gpu`), HIP path only."""
     y, sr, uri = _load(audio_filepath)
     use_gpu = encoder is None
     if encoder is None:
@@ -182,10 +185,17 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
             raise ValueError(f"world must be None or 'dist', got {world!r}")
         # recording-level mean removal (first step of the reference's whiten_l2, [REF diar_diag.py:187-188]):
         # untrained / mismatched encoders put a large common component into every embedding
-        K = cosine_affinity(cluster.center(embs) if center_embeddings else embs, use_gpu)
+        X = cluster.center(embs) if center_embeddings else embs
+        K = _spectral_gpu_affinity(X, use_gpu) if clustering == "spectral_gpu" else cosine_affinity(X, use_gpu)
         if clustering == "spectral":
             k = cluster.estimate_num_speakers(K, min_speakers, max_speakers)
             labels = cluster.spectral(K, k)
+        elif clustering == "spectral_gpu":
+            # the same two steps without the N x N matrix leaving the device (cluster_gpu.py); it is copied out for the details only
+            from . import cluster_gpu
+            k = cluster_gpu.estimate_num_speakers(K, min_speakers, max_speakers, assume_symmetric=True)
+            labels = cluster_gpu.spectral(K, k, assume_symmetric=True)
+            K = K.cpu().numpy() if return_details else None
         elif clustering == "ahc":
             labels = cluster.ahc_cosine(K, clustering_threshold)
         else:
@@ -197,6 +207,15 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
         with open(rttm_filepath, "w") as f:
             rttm.write_rttm(segments, uri, f)
     return (segments, details) if return_details else segments
+
+
+def _spectral_gpu_affinity(X: np.ndarray, use_gpu: bool):
+    """`ops.cosine_affinity` of the rows, left on the device for `clustering="spectral_gpu"`."""
+    import torch
+    if not use_gpu or not torch.cuda.is_available():
+        raise RuntimeError("clustering='spectral_gpu' runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+    from . import ops
+    return ops.cosine_affinity(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda())
 
 
 def _rank() -> int:

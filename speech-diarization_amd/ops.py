@@ -482,3 +482,48 @@ def viterbi(scores: torch.Tensor, alpha: float = 0.995) -> torch.Tensor:
         N.check(lib.sd_viterbi_f32(scores.data_ptr(), scores.stride(0), T, K, C.c_float(log_stay), C.c_float(log_move), ws.data_ptr(), nbytes,
                                    path.data_ptr(), _stream(scores)), "sd_viterbi_f32")
     return path
+
+
+# ----------------------------------------------------------------------------- spectral operator (include/sd_hip_spectral.h)
+
+def affinity_degree(K: torch.Tensor, zero_diag: bool = False) -> torch.Tensor:
+    """deg[i] = sum_j max(K[i][j], 0) (without j == i when `zero_diag`) of a square f32 affinity on the GPU -> f32 [N].
+    K is read in place (any row stride); bitwise reproducible."""
+    _need_cuda(K)
+    if K.dtype != torch.float32 or K.dim() != 2 or K.shape[0] != K.shape[1] or K.stride(1) != 1 and K.shape[0] > 1:
+        raise ValueError(f"affinity must be a square f32 matrix with contiguous rows, got {tuple(K.shape)} {K.dtype} strides {K.stride()}")
+    n = K.shape[0]
+    deg = torch.empty((n,), dtype=torch.float32, device=K.device)
+    if n == 0:
+        return deg
+    with torch.cuda.device(K.device):
+        N.check(N.load().sd_affinity_degree_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), deg.data_ptr(), _stream(K)),
+                "sd_affinity_degree_f32")
+    return deg
+
+
+def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_diag: bool = False,
+                   ws: torch.Tensor | None = None) -> torch.Tensor:
+    """Y = diag(scale) max(K, 0) diag(scale) V on the GPU, the diagonal of K taken as 0 when `zero_diag`.  K f32 [N, N] read in
+    place, scale f32 [N], V f32 [N, b] with b in {8, 16, 24, 32} -> f32 [N, b].  `ws`: a uint8 workspace of at least
+    sd_affinity_apply_workspace_bytes(N, b) to reuse across calls (allocated when None)."""
+    _need_cuda(K, scale, V)
+    if K.dtype != torch.float32 or K.dim() != 2 or K.shape[0] != K.shape[1] or K.stride(1) != 1 and K.shape[0] > 1:
+        raise ValueError(f"affinity must be a square f32 matrix with contiguous rows, got {tuple(K.shape)} {K.dtype} strides {K.stride()}")
+    n = K.shape[0]
+    scale = scale.contiguous().float()
+    V = V.contiguous().float()
+    if scale.shape != (n,) or V.dim() != 2 or V.shape[0] != n:
+        raise ValueError(f"scale {tuple(scale.shape)} / V {tuple(V.shape)} do not match the {n} x {n} affinity")
+    b = V.shape[1]
+    Y = torch.empty((n, b), dtype=torch.float32, device=K.device)
+    if n == 0:
+        return Y
+    lib = N.load()
+    with torch.cuda.device(K.device):
+        need = int(lib.sd_affinity_apply_workspace_bytes(n, b))
+        if ws is None or ws.numel() * ws.element_size() < need:
+            ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=K.device)
+        N.check(lib.sd_affinity_apply_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), scale.data_ptr(), V.data_ptr(), b, b,
+                                          Y.data_ptr(), b, ws.data_ptr(), ws.numel() * ws.element_size(), _stream(K)), "sd_affinity_apply_f32")
+    return Y
