@@ -178,6 +178,15 @@ SPECTRAL_PROTOTYPES = {
     "sd_affinity_apply_f32": (_I, [_P, _I, C.c_long, _I, _P, _P, _I, _I, _P, _I, _P, _Z, _P]),
 }
 
+# include/sd_hip_ahc.h: the agglomerative-clustering entries, same shared object, a table and a version of their own
+SD_AHC_ABI_VERSION = 1
+AHC_PROTOTYPES = {
+    "sd_ahc_abi_version": (_I, []),
+    "sd_ahc_nearest_workspace_bytes": (_Z, [_I, _I]),
+    "sd_ahc_nearest_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "sd_ahc_merge_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -221,6 +230,15 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.sd_spectral_abi_version() != SD_SPECTRAL_ABI_VERSION:
             raise RuntimeError(f"libsd_hip.so spectral ABI {lib.sd_spectral_abi_version()} != binding ABI {SD_SPECTRAL_ABI_VERSION}; rebuild")
+        missing = [name for name in AHC_PROTOTYPES if not hasattr(lib, name)]
+        if missing:
+            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_ahc.h: {missing}")
+        for name, (res, args) in AHC_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sd_ahc_abi_version() != SD_AHC_ABI_VERSION:
+            raise RuntimeError(f"libsd_hip.so AHC ABI {lib.sd_ahc_abi_version()} != binding ABI {SD_AHC_ABI_VERSION}; rebuild")
         for which, st in enumerate((sd_conv_args, sd_layer, sd_se_res2_block, sd_ecapa_weights)):
             if lib.sd_sizeof(which) != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__}: binding layout is {C.sizeof(st)} bytes, the library's {lib.sd_sizeof(which)}; rebuild")

@@ -1,0 +1,144 @@
+"""Device route for the reference's clustering: average-linkage AHC on cosine distance without the N x N matrix.
+
+`cluster.ahc_cosine` [REF diar_diag.py:218-226] copies the N x N affinity off the GPU, turns it into an f64 distance matrix and hands
+it to scikit-learn.  The matrix is not needed: the average linkage between clusters A and B of unit rows is
+
+    1 - (1 / (|A| |B|)) . sum_{a in A, b in B} <x_a, x_b>  =  1 - <s_A, s_B> / (|A| |B|),      s_A = sum of the rows of A,
+
+so a cluster is the sum of its unit rows and its size, and a merge is one vector add.  Average linkage is reducible: merging a pair of
+mutually nearest clusters never brings a third cluster closer to the merged one than it was to the nearer of the two, so EVERY pair of
+mutually nearest clusters can be merged in the same round and the dendrogram is the greedy one.  The cut at cosine `cos_thr` is the set
+of merges whose score is above it.  Opt-in: `diarize_audio(..., clustering="ahc_gpu")`; `cluster.py` and `clustering="ahc"` are
+unchanged.
+
+A round
+* `nearest`: the best other cluster of every active cluster (`ops.ahc_nearest`, `sd_ahc_nearest_f32`, include/sd_hip_ahc.h): one
+  Gram-with-argmax pass over the n_active x D sums on the f32 matrix cores, nothing n x n is stored;
+* `merge`: every reciprocal pair above the threshold, into the lower index (`ops.ahc_merge`, `sd_ahc_merge_f32`);
+* the number of merges is read back (the one host synchronisation of a round; 0 ends the loop);
+* the sums, counts and the row-to-cluster table are compacted with torch indexing on the operator's device (plumbing, no kernel).
+Merging goes into the lower index and compaction keeps order, so the final cluster ids are numbered by first appearance.
+
+The operator is injectable (`operator=`): an object with `device`, `normalise(X)`, `nearest(sums, inv_count)` and
+`merge(sums, count, inv_count, nn, best, cos_thr)` over torch tensors.  `DeviceSums` is the product one; the tests run the same driver
+on the CPU against a numpy operator.  There is no implicit CPU route: without an operator a host tensor raises the product path's
+RuntimeError.
+
+Two differences from the host route
+* the host clips 1 - K at 0 and symmetrises an f32 K; here there is no K: a score is an f32 dot product of f32 sums, and differs from
+  the host's f64 mean of f32 cosines by f32 rounding, about 1e-7;
+* equal partitions are therefore a property of inputs without near-ties (no merge height within that rounding of the cut or of a
+  competing merge; the caveat of DESIGN section 8), not a guarantee.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+class DeviceSums:
+    """The two kernels of include/sd_hip_ahc.h over cluster sums that live on the GPU."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("the device AHC route takes its rows as a GPU tensor; there is no CPU fallback")
+        self._ws = None
+
+    def normalise(self, X: torch.Tensor) -> torch.Tensor:
+        """Unit rows, a zero row left zero (sklearn `normalize`), f32 [N, D padded to a multiple of 4 with zero columns]."""
+        from . import ops
+        Xn = ops.l2norm_rows(X, sklearn_zero_guard=True)
+        pad = -Xn.shape[1] % 4
+        return torch.nn.functional.pad(Xn, (0, pad)) if pad else Xn
+
+    def nearest(self, sums: torch.Tensor, inv_count: torch.Tensor):
+        from . import _native, ops
+        need = int(_native.load().sd_ahc_nearest_workspace_bytes(sums.shape[0], sums.shape[1]))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        return ops.ahc_nearest(sums, inv_count, ws=self._ws)
+
+    def merge(self, sums, count, inv_count, nn, best, cos_thr: float):
+        from . import ops
+        return ops.ahc_merge(sums, count, inv_count, nn, best, cos_thr)
+
+
+def ahc_cosine_rows(X, cos_thr: float = 0.70, *, operator=None, return_info: bool = False):
+    """`cluster.ahc_cosine(cosine_similarity(X), cos_thr)` from the rows X [N, D] themselves -> labels int [N], numbered by first
+    appearance (info = {"rounds": rounds that merged something, "clusters", "gram_rows": sum of n_active^2 over every nearest pass,
+    the last one that found nothing to merge included, "last_best": the largest score of that last pass, i.e. how far the closest
+    remaining pair is from the cut; -inf when one cluster is left}).
+
+    Early returns as in `cluster.ahc_cosine`: N = 0 and N = 1.  A non-finite row raises ValueError before anything is launched."""
+    from . import cluster
+    info = {"rounds": 0, "clusters": 0, "gram_rows": 0, "last_best": float("-inf")}
+    if operator is None:
+        if not isinstance(X, torch.Tensor) or X.device.type != "cuda":
+            raise RuntimeError("the device AHC route takes its rows as a GPU tensor; there is no CPU fallback")
+        operator = DeviceSums(X.device)
+    X = torch.as_tensor(X)
+    if X.dim() != 2:
+        raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
+    N = X.shape[0]
+    if N <= 1:
+        info["clusters"] = N
+        labels = np.zeros(N, dtype=int)
+        return (labels, info) if return_info else labels
+    if X.shape[1] == 0 or not bool(torch.isfinite(X).all()):
+        raise ValueError("rows must be finite and have at least one column")
+    dev = operator.device
+    sums = operator.normalise(X.to(dev).float())
+    count = torch.ones((N,), dtype=torch.float32, device=dev)
+    inv_count = torch.ones((N,), dtype=torch.float32, device=dev)
+    cluster_of = torch.arange(N, device=dev)                        # row -> index of its cluster among the active ones
+    n = N
+    while True:
+        nn, best = operator.nearest(sums, inv_count)
+        info["gram_rows"] += n * n
+        target, n_merged = operator.merge(sums, count, inv_count, nn, best, float(cos_thr))
+        m = int(n_merged)                                           # the host synchronisation of the round
+        if m == 0:
+            info["last_best"] = float(best.max())
+            break
+        info["rounds"] += 1
+        # compaction without a data-dependent shape (m is known): kept rows in order, the others dumped into one slot past the end
+        target = target.long()
+        ids = torch.arange(n, device=dev)
+        keep = target == ids
+        new_id = torch.cumsum(keep, 0) - 1
+        cluster_of = new_id[target[cluster_of]]
+        src = torch.empty((n - m + 1,), dtype=torch.long, device=dev)
+        src.scatter_(0, torch.where(keep, new_id, torch.full_like(new_id, n - m)), ids)
+        src = src[: n - m]
+        sums, count, inv_count = sums[src], count[src], inv_count[src]
+        n -= m
+    labels = cluster_of.cpu().numpy().astype(int)
+    assert np.array_equal(labels, cluster.relabel_by_first_appearance(labels)), "cluster ids are not numbered by first appearance"
+    info["clusters"] = n
+    return (labels, info) if return_info else labels
+
+
+class AhcGpuClusterer:
+    """`cluster.AhcClusterer` on the device route, for the `clusterer_factory=` argument of `cluster.cluster_hdbscan_two_stage` and
+    `diar_diag.cluster_embeddings`: `fit_predict` takes L2-normalised rows (metric "euclidean") and cuts at cosine `cos_thr`.  A
+    "precomputed" distance matrix raises ValueError: the route needs the rows, not a matrix."""
+
+    def __init__(self, cos_thr: float = 0.70, metric: str = "euclidean", operator=None, **_ignored):
+        if metric != "euclidean":
+            raise ValueError(f"AhcGpuClusterer clusters rows (metric='euclidean'); metric={metric!r} has no rows to work on")
+        self.cos_thr = float(cos_thr)
+        self.metric = metric
+        self.operator = operator
+
+    @classmethod
+    def factory(cls, cos_thr: float = 0.70, operator=None):
+        return lambda **kw: cls(cos_thr, metric=kw.get("metric", "euclidean"), operator=operator)
+
+    def fit_predict(self, X) -> np.ndarray:
+        X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+        if self.operator is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("AhcGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
+            X = X.cuda()
+        return ahc_cosine_rows(X, self.cos_thr, operator=self.operator)

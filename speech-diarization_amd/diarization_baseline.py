@@ -159,8 +159,9 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
     `all_gather_into_tensor` returns the full [N, 192] in window order to every rank, every rank clusters
     (deterministic, N x 192 is tiny), rank 0 writes the RTTM.  The result is identical to `world=None`.
 
-    `clustering`: "spectral" (default; eigengap + scikit-learn SpectralClustering on the host), "ahc", or "spectral_gpu": the two
-    spectral steps on the device (`cluster_gpu`), HIP path only."""
+    `clustering`: "spectral" (default; eigengap + scikit-learn SpectralClustering on the host), "ahc", "spectral_gpu": the two
+    spectral steps on the device (`cluster_gpu`), or "ahc_gpu": the AHC of "ahc" on the device from the rows themselves (`ahc_gpu`; no
+    affinity is formed, `details["affinity"]` is None).  The two device routes are HIP path only."""
     y, sr, uri = _load(audio_filepath)
     use_gpu = encoder is None
     if encoder is None:
@@ -186,7 +187,10 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
         # recording-level mean removal (first step of the reference's whiten_l2, [REF diar_diag.py:187-188]):
         # untrained / mismatched encoders put a large common component into every embedding
         X = cluster.center(embs) if center_embeddings else embs
-        K = _spectral_gpu_affinity(X, use_gpu) if clustering == "spectral_gpu" else cosine_affinity(X, use_gpu)
+        if clustering == "ahc_gpu":
+            K = None
+        else:
+            K = _spectral_gpu_affinity(X, use_gpu) if clustering == "spectral_gpu" else cosine_affinity(X, use_gpu)
         if clustering == "spectral":
             k = cluster.estimate_num_speakers(K, min_speakers, max_speakers)
             labels = cluster.spectral(K, k)
@@ -198,6 +202,9 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
             K = K.cpu().numpy() if return_details else None
         elif clustering == "ahc":
             labels = cluster.ahc_cosine(K, clustering_threshold)
+        elif clustering == "ahc_gpu":
+            from . import ahc_gpu
+            labels = ahc_gpu.ahc_cosine_rows(_device_rows(X, use_gpu, clustering), clustering_threshold)
         else:
             raise ValueError(f"unknown clustering {clustering!r}")
         labels = cluster.relabel_by_first_appearance(labels)
@@ -209,13 +216,18 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
     return (segments, details) if return_details else segments
 
 
-def _spectral_gpu_affinity(X: np.ndarray, use_gpu: bool):
-    """`ops.cosine_affinity` of the rows, left on the device for `clustering="spectral_gpu"`."""
+def _device_rows(X: np.ndarray, use_gpu: bool, clustering: str):
+    """The rows on the device, for the clustering routes that stay there."""
     import torch
     if not use_gpu or not torch.cuda.is_available():
-        raise RuntimeError("clustering='spectral_gpu' runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+        raise RuntimeError(f"clustering={clustering!r} runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+    return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+
+
+def _spectral_gpu_affinity(X: np.ndarray, use_gpu: bool):
+    """`ops.cosine_affinity` of the rows, left on the device for `clustering="spectral_gpu"`."""
     from . import ops
-    return ops.cosine_affinity(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda())
+    return ops.cosine_affinity(_device_rows(X, use_gpu, "spectral_gpu"))
 
 
 def _rank() -> int:

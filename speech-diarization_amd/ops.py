@@ -527,3 +527,52 @@ def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_d
         N.check(lib.sd_affinity_apply_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), scale.data_ptr(), V.data_ptr(), b, b,
                                           Y.data_ptr(), b, ws.data_ptr(), ws.numel() * ws.element_size(), _stream(K)), "sd_affinity_apply_f32")
     return Y
+
+
+# ----------------------------------------------------------------------------- average-linkage clustering (include/sd_hip_ahc.h)
+
+def _ahc_sums(sums: torch.Tensor) -> tuple[int, int, int]:
+    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[0] == 0 or sums.shape[1] == 0 or sums.stride(1) != 1 and sums.shape[1] > 1:
+        raise ValueError(f"cluster sums must be a non-empty f32 matrix with contiguous rows, got {tuple(sums.shape)} {sums.dtype} strides {sums.stride()}")
+    n, d = sums.shape
+    return n, d, max(sums.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
+
+
+def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: torch.Tensor | None = None):
+    """The nearest other cluster of every cluster under score(i, j) = <sums[i], sums[j]> (inv_count[i] inv_count[j]):
+    sums f32 [n, d] read in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine),
+    inv_count f32 [n] -> (nn int32 [n], best f32 [n]); exactly symmetric scores, lowest index among equal ones, bitwise reproducible.
+    `ws`: a uint8 workspace of at least sd_ahc_nearest_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    _need_cuda(sums, inv_count)
+    n, d, ld = _ahc_sums(sums)
+    inv_count = inv_count.contiguous().float()
+    if inv_count.shape != (n,):
+        raise ValueError(f"inv_count {tuple(inv_count.shape)} does not match the {n} cluster sums")
+    nn = torch.empty((n,), dtype=torch.int32, device=sums.device)
+    best = torch.empty((n,), dtype=torch.float32, device=sums.device)
+    lib = N.load()
+    with torch.cuda.device(sums.device):
+        need = int(lib.sd_ahc_nearest_workspace_bytes(n, d))
+        if ws is None or ws.numel() * ws.element_size() < need:
+            ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=sums.device)
+        N.check(lib.sd_ahc_nearest_f32(sums.data_ptr(), ld, n, d, inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(),
+                                       ws.numel() * ws.element_size(), _stream(sums)), "sd_ahc_nearest_f32")
+    return nn, best
+
+
+def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, nn: torch.Tensor, best: torch.Tensor, cos_thr: float):
+    """One round of merges IN PLACE: every reciprocal pair i < j (nn[i] == j, nn[j] == i) with best[i] > cos_thr adds row j of `sums`
+    and its count into row i and refreshes inv_count[i] -> (target int32 [n]: i for the upper row of a pair, the row itself otherwise;
+    n_merged int32 [1], still on the device)."""
+    _need_cuda(sums, count, inv_count, nn, best)
+    n, d, ld = _ahc_sums(sums)
+    for name, t, dt in (("count", count, torch.float32), ("inv_count", inv_count, torch.float32), ("nn", nn, torch.int32),
+                        ("best", best, torch.float32)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    target = torch.empty((n,), dtype=torch.int32, device=sums.device)
+    n_merged = torch.empty((1,), dtype=torch.int32, device=sums.device)
+    with torch.cuda.device(sums.device):
+        N.check(N.load().sd_ahc_merge_f32(sums.data_ptr(), ld, n, d, count.data_ptr(), inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
+                                          C.c_float(cos_thr), target.data_ptr(), n_merged.data_ptr(), _stream(sums)), "sd_ahc_merge_f32")
+    return target, n_merged

@@ -27,8 +27,9 @@ def main():
     ap.add_argument("--synthetic", type=float, default=0.0, help="generate this many seconds of an 8-speaker meeting at AUDIO (rank 0)")
     ap.add_argument("--min-speakers", type=int, default=2)
     ap.add_argument("--max-speakers", type=int, default=8)
-    ap.add_argument("--clustering", default="spectral", choices=("spectral", "ahc", "spectral_gpu"),
-                    help="spectral_gpu: speaker count and spectral embedding on the device (cluster_gpu.py)")
+    ap.add_argument("--clustering", default="spectral", choices=("spectral", "ahc", "spectral_gpu", "ahc_gpu"),
+                    help="spectral_gpu: speaker count and spectral embedding on the device (cluster_gpu.py); "
+                         "ahc_gpu: average-linkage AHC on the device from the embeddings themselves (ahc_gpu.py)")
     ap.add_argument("--gpus", type=int, default=1, help="ranks to start (one per GPU) when not already under torchrun")
     a = ap.parse_args()
     from speech_diarization_amd import launch
