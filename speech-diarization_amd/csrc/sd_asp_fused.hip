@@ -329,12 +329,14 @@ __global__ __launch_bounds__(512, 2) void asp_attend_pool_f32_kernel(const float
   if (wid < ngroups) load_w(wid, wf);
 #pragma unroll 1
   for (int g = wid; g < ngroups; g += 8) {
-    // h of this group in the accumulator layout (consumed after the MFMAs): frame 16 j + col, channels 16 g + 4 quad .. +3
+    // h of this group in the accumulator layout (consumed after the MFMAs): frame 16 j + col, channels 16 g + 4 quad .. +3.  Frames past
+    // the mask read as 0, like frames past T (as the f16 kernel does): their weight is 0, but 0 x (h - mu)^2 is NaN once the square
+    // overflows, and the fmaxf of the clamp would turn that NaN into sqrt(eps)
     f32x4 hv[NT];
     {
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int j = 0; j < NT; ++j) hv[j] = j * 16 + col < Tn ? *reinterpret_cast<const f32x4*>(hl + (size_t)j * 16 * ldh + g * 16) : z;
+      for (int j = 0; j < NT; ++j) hv[j] = j * 16 + col < nv ? *reinterpret_cast<const f32x4*>(hl + (size_t)j * 16 * ldh + g * 16) : z;
     }
     f32x4 acc[NT];
 #pragma unroll

@@ -1,0 +1,715 @@
+"""Known-answer cases for tests/test_exact_rules.py (CPU) and tests/test_gpu_exact.py: inputs on which every f32 product and sum
+a kernel can form is exact (small integers, powers of two, one-hot weights), so that an int64 / float64 numpy reference gives
+the BITS the kernel must produce, whatever its tile shape, K order, split-K order or MFMA form.
+
+Every generator checks its own bit budget on the host and raises `BudgetError` when a case leaves it:
+  * every value an f32 accumulator or an f32 epilogue can hold is below 2^24 in magnitude (bounded by sum |x| |w|, so the bound
+    holds for every summation order) and is a multiple of a power of two that keeps it inside 24 bits;
+  * every value stored as f16 survives the round trip through f16 and is at most 2048 in magnitude;
+  * a mean divides by a power of two (or the quotient is an integer), quotient and square inside 24 bits.
+A GPU mismatch on one of these cases is therefore never rounding.
+
+`EXACT_COVERAGE` maps a kernel to the cases meant to reach it, read off the dispatch rules of sd_conv_gemm.hip
+(`conv1d_cl_f32_impl`), sd_conv_gemm_f16.hip (`sd_conv1d_cl_f16`, `sd_conv1d_cl_split16`), sd_pool.hip and sd_ecapa.hip and
+stated as data: a case names its kernels, the table is their inverse."""
+import functools
+from dataclasses import dataclass
+
+import numpy as np
+
+F32_LIMIT = 1 << 24
+F16_LIMIT = 2048
+
+
+class BudgetError(ValueError):
+    """A case left the range in which its arithmetic is exact."""
+
+
+def need_f32(name, *arrays):
+    """Every value is an f32 below 2^24 in magnitude that survives the round trip (so: no rounding when it is formed)."""
+    for a in arrays:
+        a = np.asarray(a, dtype=np.float64)
+        if a.size and (np.abs(a).max() >= F32_LIMIT or not np.array_equal(a.astype(np.float32).astype(np.float64), a)):
+            raise BudgetError(f"{name}: a value leaves the exact f32 range (max |v| = {np.abs(a).max():g})")
+
+
+def need_f16(name, *arrays):
+    for a in arrays:
+        a = np.asarray(a, dtype=np.float64)
+        if a.size and (np.abs(a).max() > F16_LIMIT or not np.array_equal(a.astype(np.float16).astype(np.float64), a)):
+            raise BudgetError(f"{name}: a value is not an exact f16 of at most {F16_LIMIT} (max |v| = {np.abs(a).max():g})")
+
+
+def need_mean(name, total, divisor):
+    """total / divisor: the divisor a power of two (or the quotient an integer), quotient and its square inside 24 bits."""
+    total = np.asarray(total, dtype=np.float64)
+    q = total / divisor
+    pow2 = divisor > 0 and (int(divisor) & (int(divisor) - 1)) == 0 and int(divisor) == divisor
+    if not pow2 and not np.array_equal(q, np.round(q)):
+        raise BudgetError(f"{name}: divisor {divisor} is no power of two and the quotient no integer")
+    need_f32(name + " (mean)", q)
+    need_f32(name + " (mean^2)", q * q)
+
+
+# ------------------------------------------------------------------ kernels and coverage
+
+F32_CONV_KERNELS = ("conv_gemm_f32_kernel", "conv_gemm_f32_s64_kernel", "skinny_gemm_f32_kernel", "conv_gemm_f32_vh_kernel",
+                    "conv_gemm_f32_n64_kernel", "conv_gemm_f32_t256_kernel", "conv_gemm_f32_packed_kernel",
+                    "seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel")
+F16_CONV_KERNELS = ("conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel")
+SPLIT_CONV_KERNELS = ("conv_gemm_split16_n128_kernel", "conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")
+CONV_KERNELS = F32_CONV_KERNELS + F16_CONV_KERNELS + SPLIT_CONV_KERNELS + ("res2net_chain_f16_kernel",)
+REDUCTION_KERNELS = ("seg_mean_std_kernel", "se_scale_residual_kernel", "asp_pool_kernel", "asp_pool_lds_kernel",
+                     "asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel", "colstat_finish_kernel")
+PRODUCT_KERNELS = ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel", "sim_argmax_kernel", "ahc_nearest_kernel",
+                   "ahc_nearest_finish_kernel", "ahc_merge_kernel", "affinity_apply_kernel", "apply_finish_kernel",
+                   "affinity_degree_kernel", "topk_mean_std_kernel", "viterbi_kernel")
+ALL_KERNELS = CONV_KERNELS + REDUCTION_KERNELS + PRODUCT_KERNELS
+
+# which kernels a conv shape reaches under the eight selections of kernel_selection.CONV_KERNELS (sd_conv_gemm.hip conv1d_cl_f32_impl):
+# S1 / S2 / S3 are small time-axis launches ("auto": the 64x64 ring kernel, "split32": the 32x32 split-K kernel, then the pinned
+# 128x128, 128x64 and 80 / 96 / 112-row kernels); S2 has cout >= 1024 ("wide256": the 256x256 ring kernel); S4 is T = 1 ("auto": the
+# split-K 32x32 kernel; through sd_seg_gemm_f32 the grid split-K pair; the other selections the 128x128 / 128x64 kernels)
+_TIME = ("conv_gemm_f32_s64_kernel", "skinny_gemm_f32_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "conv_gemm_f32_vh_kernel")
+_WIDE = _TIME + ("conv_gemm_f32_t256_kernel",)
+_SEG = ("skinny_gemm_f32_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel")
+_PACKED = ("conv_gemm_f32_packed_kernel",)
+# sd_conv1d_cl_f16: the 128x128 kernel unless x is f16, cout >= 1024 and the launch is not "small" (pinned by SD_TUNE_F16_NARROW_TILES)
+_H128 = ("conv_gemm_f16_kernel",)
+_H256 = ("conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel")
+# sd_conv1d_cl_split16: f32 x -> the 128x128 kernel that splits while staging; packed x (sd_split16_pack_f32) -> the 256x256 kernel
+_SN = ("conv_gemm_split16_n128_kernel",)
+_SW = ("conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")
+_CS = ("conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel",
+       "conv_gemm_f16_t256_kernel<split>", "colstat_finish_kernel")
+_POOL = ("asp_pool_kernel", "asp_pool_lds_kernel")
+_FUSED = ("asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel")
+
+# case name -> (kind, kernels it is meant to reach); kind: "gather" (one-hot weights, one-hot logits, planted ties: the answer names the
+# element that was read) or "dense" (integer arithmetic over every element)
+CASE_TABLE = {
+    **{f"{s}-{w}": ("gather", r) for s, r in (("S1", _TIME), ("S2", _WIDE), ("S3", _TIME), ("S4", _SEG), ("P", _PACKED)) for w in ("rows", "chan")},
+    "S1-dense": ("dense", _TIME), "S2-dense": ("dense", _WIDE), "S2-dense-tee": ("dense", _WIDE), "S3-dense": ("dense", _TIME),
+    "S4-dense": ("dense", _SEG), "P-dense": ("dense", _PACKED),
+    **{f"{s}-{w}": ("gather", r) for s, r in (("H1", _H128), ("H2", _H256), ("H3", _H128)) for w in ("rows", "chan")},
+    "H1-dense": ("dense", _H128), "H2-dense": ("dense", _H256), "H2-dense-tee": ("dense", _H256), "H2w-dense-tee": ("dense", _H256),
+    "H3-dense": ("dense", _H128), "H2L-rows": ("gather", _H256), "H2L-dense": ("dense", _H256),
+    "N128-rows": ("gather", _SN), "N128-chan": ("gather", _SN), "N128-split_x": ("dense", _SN), "N128-split_w": ("dense", _SN),
+    "W1032-rows": ("gather", _SW), "W1032-split_x": ("dense", _SW), "W1032-split_w": ("dense", _SW),
+    "W256-chan": ("gather", _SW), "W256-split_x": ("dense", _SW), "W256-split_w": ("dense", _SW),
+    "C3x128-256": ("dense", _CS), "C5x64-256": ("dense", _CS), "C11x64-1024": ("dense", _CS), "C3x128-1024": ("dense", _CS),
+    "chain-onehot": ("gather", ("res2net_chain_f16_kernel", "conv_gemm_f16_kernel")),
+    "chain-sums": ("dense", ("res2net_chain_f16_kernel", "conv_gemm_f16_kernel")),
+    "reduce-int": ("dense", ("seg_mean_std_kernel", "se_scale_residual_kernel")),
+    "reduce-poison": ("gather", ("seg_mean_std_kernel", "se_scale_residual_kernel")),
+    "pool-onehot": ("gather", _POOL), "pool-uniform": ("dense", _POOL),
+    "fused-onehot": ("gather", _FUSED), "fused-uniform": ("dense", _FUSED),
+    "affinity-k16": ("dense", ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel", "conv_gemm_f32_kernel",
+                               "conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")),
+    "affinity-duplicates": ("gather", ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel")),
+    "ahc-ties": ("gather", ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel")),
+    "ahc-int": ("dense", ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel")),
+    "spectral-dyadic": ("dense", ("affinity_apply_kernel", "apply_finish_kernel", "affinity_degree_kernel")),
+    "spectral-onehot": ("gather", ("affinity_apply_kernel", "apply_finish_kernel", "affinity_degree_kernel")),
+    "argmax-duplicates": ("gather", ("sim_argmax_kernel",)), "argmax-int": ("dense", ("sim_argmax_kernel",)),
+    "topk-ties": ("gather", ("topk_mean_std_kernel",)), "topk-int": ("dense", ("topk_mean_std_kernel",)),
+    "viterbi-ties": ("gather", ("viterbi_kernel",)), "viterbi-int": ("dense", ("viterbi_kernel",)),
+}
+assert all(kind in ("gather", "dense") and set(ks) <= set(ALL_KERNELS) for kind, ks in CASE_TABLE.values())
+
+
+def register(name, kind=None):
+    """The kernels of a case; a generator may only build what the table names."""
+    if name not in CASE_TABLE:
+        raise KeyError(f"{name} is not in CASE_TABLE")
+    if kind is not None and CASE_TABLE[name][0] != kind:
+        raise ValueError(f"{name} is a {CASE_TABLE[name][0]} case, built as {kind}")
+    return CASE_TABLE[name][1]
+
+
+def coverage(table=None):
+    """kernel -> case names, the inverse of CASE_TABLE."""
+    out = {}
+    for name, (_, kernels) in (CASE_TABLE if table is None else table).items():
+        for k in kernels:
+            out.setdefault(k, []).append(name)
+    return out
+
+
+EXACT_COVERAGE = coverage()
+
+
+# ------------------------------------------------------------------ convs
+
+# the shapes of the issue (what each crosses: the docstring of tests/test_gpu_exact.py).  H*: the same shapes for sd_conv1d_cl_f16, whose
+# activations come in groups of 8 channels (S1's 36 channels are refused there: 40).  N128 / W*: the narrow and wide split16 forms.
+SHAPES = {
+    "S1": dict(B=3, T=57, cin=36, cout=72, k=3, dil=2),
+    "S2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "S3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
+    "S4": dict(B=70, T=1, cin=544, cout=40, k=1, dil=1),
+    "P": dict(spans=(5, 7, 5, 9, 131), cin=36, cout=72, k=3, dil=2),
+    "H1": dict(B=3, T=57, cin=40, cout=72, k=3, dil=2),
+    "H2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "H2w": dict(B=2, T=131, cin=80, cout=1100, k=5, dil=1),
+    "H2L": dict(B=2, T=131, cin=80, cout=1024, k=5, dil=1),      # four column tiles of 256: the lockstep walk of the 256x256 kernel
+    "H3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
+    "N128": dict(B=3, T=57, cin=36, cout=128, k=3, dil=2),
+    "W1032": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "W256": dict(B=2, T=131, cin=80, cout=256, k=5, dil=1),
+}
+# the epilogue of each dense case: (per-segment bias, act, (tee_lo, tee_hi) or None, tee_add)
+DENSE = {
+    "S1-dense": (True, "relu", (8, 40), True), "S2-dense": (False, "relu", None, False), "S2-dense-tee": (True, None, (128, 256), False),
+    "S3-dense": (True, "relu", (4, 52), True), "S4-dense": (False, "relu", None, False), "P-dense": (True, "relu", (8, 40), True),
+    "H1-dense": (True, "relu", (8, 40), True), "H2-dense": (False, "relu", None, False), "H2-dense-tee": (True, None, (128, 256), False),
+    "H2w-dense-tee": (True, "relu", (128, 256), False), "H3-dense": (True, "relu", (8, 56), True), "H2L-dense": (False, "relu", None, False),
+    "N128-split_x": (True, "relu", (0, 128), True), "N128-split_w": (True, None, (0, 128), True),
+    "W1032-split_x": (False, "relu", None, False), "W1032-split_w": (False, "relu", (128, 256), False),
+    "W256-split_x": (False, "relu", None, False), "W256-split_w": (False, None, None, False),
+}
+GATHER_TEE = {"N128-rows": (0, 128), "H1-rows": (8, 40), "S1-rows": (8, 40), "W1032-rows": (128, 256)}
+
+
+def source_rows(lengths, k, dil):
+    """[M, k] int64: the row tap j of output row m reads, reflected inside m's segment (segments given by their lengths)."""
+    src = []
+    start = 0
+    for L in lengths:
+        if (k // 2) * dil >= L:
+            raise ValueError(f"reflect padding {(k // 2) * dil} needs a longer segment than {L}")
+        t = np.arange(L)[:, None] + (np.arange(k)[None, :] - k // 2) * dil
+        t = np.where(t < 0, -t, t)
+        t = np.where(t >= L, 2 * (L - 1) - t, t)
+        src.append(start + t)
+        start += L
+    return np.concatenate(src).astype(np.int64)
+
+
+def conv_sum(x, w, src):
+    """sum_j x[src[:, j]] @ w[:, :, j].T in float64 (exact: every partial sum is an integer multiple of a power of two far below 2^53)."""
+    acc = np.zeros((x.shape[0], w.shape[0]), dtype=np.float64)
+    for j in range(w.shape[2]):
+        acc += x[src[:, j]].astype(np.float64) @ w[:, :, j].astype(np.float64).T
+    return acc
+
+
+@dataclass
+class ConvCase:
+    name: str
+    kind: str                   # "rows" / "chan" (gather), "dense", "split_x" / "split_w" (the 2049 s operand on that side)
+    lengths: tuple              # segment lengths: (T,) * B, or the packed spans
+    packed: bool
+    cin: int
+    cout: int
+    k: int
+    dil: int
+    x: np.ndarray               # [M, cin] float64 (integers)
+    w: np.ndarray               # [cout, cin, k] float64
+    bias: np.ndarray = None     # [cout] or [B, cout]
+    bias_per_seg: bool = False
+    act: str = None
+    scale: np.ndarray = None
+    shift: np.ndarray = None
+    tee_lo: int = 0
+    tee_hi: int = 0             # 0: no tee
+    tee_add: np.ndarray = None  # [M, tee_hi - tee_lo]
+    y: np.ndarray = None        # expected [M, cout] float64
+    tee: np.ndarray = None      # expected [M, tee_hi - tee_lo]
+    kernels: tuple = ()
+    bound: float = 0.0          # sum |x| |w| of the largest output: no partial sum, in any order, passes it
+    f16: bool = False           # the case is also run with f16 storage
+
+    @property
+    def M(self):
+        return int(sum(self.lengths))
+
+    @property
+    def B(self):
+        return len(self.lengths)
+
+    @property
+    def T(self):
+        return self.lengths[0]
+
+    @property
+    def frame_start(self):
+        return np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int32)
+
+
+def finish_conv(c: ConvCase) -> ConvCase:
+    """Fill in the expected outputs and check the budget for every storage type the case is run with."""
+    src = source_rows(c.lengths, c.k, c.dil)
+    acc = conv_sum(c.x, c.w, src)
+    c.bound = float(conv_sum(np.abs(c.x), np.abs(c.w), src).max())
+    if c.bound >= F32_LIMIT:
+        raise BudgetError(f"{c.name}: sum |x| |w| = {c.bound:g} reaches 2^24")
+    r = acc
+    steps = [acc]
+    if c.bias is not None:
+        r = r + (np.repeat(c.bias, c.lengths, axis=0) if c.bias_per_seg else c.bias[None, :])
+        steps.append(r)
+    if c.act == "relu":
+        r = np.maximum(r, 0.0)
+    if c.scale is not None:
+        r = r * c.scale[None, :]
+        steps.append(r)
+    if c.shift is not None:
+        r = r + c.shift[None, :]
+        steps.append(r)
+    c.y = r
+    if c.tee_hi:
+        c.tee = r[:, c.tee_lo:c.tee_hi] + (c.tee_add if c.tee_add is not None else 0.0)
+        steps.append(c.tee)
+    need_f32(c.name, *steps, c.x, c.w)
+    if c.f16:
+        need_f16(c.name, c.x, c.w, c.y, *([c.tee] if c.tee_hi else []), *([c.tee_add] if c.tee_add is not None else []))
+    return c
+
+
+def _lengths(s):
+    return tuple(s["spans"]) if "spans" in s else (s["T"],) * s["B"]
+
+
+def gather_case(name, s, which, *, f16=False, seed=0, tee=None):
+    """One-hot weights: w[n][jmap(n)][cmap(n)] = 1.  x[m, c] = m ("rows") makes y[m, n] the reflected source row of tap jmap(n),
+    x[m, c] = c ("chan") makes it the source channel cmap(n); both maps are seeded and use every tap and the channels 0 and cin - 1
+    (the last real one before the cin_pad zero fill)."""
+    cin, cout, k = s["cin"], s["cout"], s["k"]
+    rng = np.random.default_rng(seed + 17 * cout + cin)
+    lengths = _lengths(s)
+    M = sum(lengths)
+    cmap = np.concatenate([rng.permutation(cin) for _ in range(-(-cout // cin))])[:cout]
+    cmap[:2] = (cin - 1, 0)
+    jmap = rng.permutation(cout) % k
+    w = np.zeros((cout, cin, k))
+    w[np.arange(cout), cmap, jmap] = 1.0
+    x = np.repeat(np.arange(M, dtype=np.float64)[:, None], cin, 1) if which == "rows" else np.repeat(np.arange(cin, dtype=np.float64)[None, :], M, 0)
+    c = ConvCase(name, which, lengths, "spans" in s, cin, cout, k, s["dil"], x, w, kernels=register(name, "gather"), f16=f16)
+    if tee:
+        c.tee_lo, c.tee_hi = tee
+    c = finish_conv(c)
+    want = source_rows(lengths, k, s["dil"])[:, jmap] if which == "rows" else np.repeat(cmap[None, :], M, 0)
+    assert np.array_equal(c.y, want.astype(np.float64)), name          # the conv IS the gather
+    return c
+
+
+def dense_case(name, s, *, f16=False, seed=0, bias_per_seg=False, act="relu", tee=None, tee_add=False, kind="dense", kernels=None):
+    """x, w in {-2 .. 2}; integer bias (per channel or per segment); scale in {0.5, 1, 2, 4}; integer shift; relu or identity; a partial
+    tee [tee_lo, tee_hi) with an integer tee_add.  kind "split_x" / "split_w": that operand is 2049 s, s in {-1, 0, 1}
+    (f16(2049) = 2048, remainder 1: hi and lo both carry weight; the other operand has no low half, so lo.lo is zero)."""
+    cin, cout, k = s["cin"], s["cout"], s["k"]
+    rng = np.random.default_rng(seed + 31 * cout + cin)
+    lengths = _lengths(s)
+    M, B = sum(lengths), len(lengths)
+    x = rng.integers(-2, 3, (M, cin)).astype(np.float64)
+    w = rng.integers(-2, 3, (cout, cin, k)).astype(np.float64)
+    if kind == "split_x":
+        x = 2049.0 * rng.integers(-1, 2, (M, cin))
+    if kind == "split_w":
+        w = 2049.0 * rng.integers(-1, 2, (cout, cin, k))
+    big = 1 if kind == "dense" else 2049
+    bias = big * rng.integers(-8, 9, (B, cout) if bias_per_seg else (cout,)).astype(np.float64)
+    c = ConvCase(name, kind, lengths, "spans" in s, cin, cout, k, s["dil"], x, w, bias=bias, bias_per_seg=bias_per_seg, act=act,
+                 scale=rng.choice(np.array([0.5, 1.0, 2.0, 4.0]), cout), shift=rng.integers(-9, 10, cout).astype(np.float64),
+                 kernels=register(name, "dense") if kernels is None else kernels, f16=f16)
+    if tee:
+        c.tee_lo, c.tee_hi = tee
+        if tee_add:
+            c.tee_add = rng.integers(-5, 6, (M, tee[1] - tee[0])).astype(np.float64)
+    return finish_conv(c)
+
+
+def oversized_case():
+    """A 2049 s case whose accumulator bound passes 2^24: the helper must refuse it (BudgetError)."""
+    return dense_case("oversized", dict(B=1, T=8, cin=32768, cout=8, k=1, dil=1), kind="split_x", kernels=())
+
+
+def colstat_case(name, B, T, cout, seed=0):
+    """1x1 conv, cin 64, relu + affine with y - shift in {0 .. 3} and T a power of two.  Columns n % 3 == 0: half the rows 0 and half 2
+    (variance exactly 1); n % 3 == 1: constant (variance 0 -> sqrt(eps)); n % 3 == 2: a pattern over {0 .. 3} that depends on the frame
+    and the segment (exact mean; the std only where the variance is a perfect square)."""
+    if T & (T - 1):
+        raise BudgetError(f"{name}: T = {T} is no power of two")
+    rng = np.random.default_rng(seed + cout + T)
+    cin, M = 64, B * T
+    t, b = np.arange(M) % T, np.arange(M) // T
+    x = rng.integers(-2, 3, (M, cin)).astype(np.float64)          # channels 10 .. 63 meet zero weights
+    x[:, :10] = 0.0
+    x[np.arange(M), (t * 5 + b) % 8] = 1.0
+    x[:, 8] = t % 2
+    x[:, 9] = 1.0
+    w = np.zeros((cout, cin, 1))
+    n = np.arange(cout)
+    w[n % 3 == 0, 8, 0] = 2.0
+    w[n % 3 == 1, 9, 0] = rng.integers(0, 4, (n % 3 == 1).sum())
+    w[n % 3 == 2, :8, 0] = rng.integers(0, 5, ((n % 3 == 2).sum(), 8))
+    c = ConvCase(name, "dense", (T,) * B, False, cin, cout, 1, 1, x, w, bias=np.where(n % 3 == 2, -1.0, 0.0), act="relu", scale=np.ones(cout),
+                 shift=rng.integers(-3, 4, cout).astype(np.float64), kernels=register(name, "dense"), f16=True)
+    c = finish_conv(c)
+    v = c.y - c.shift[None, :]
+    if v.min() < 0 or v.max() > 3:
+        raise BudgetError(f"{name}: y - shift leaves {{0 .. 3}}")
+    need_mean(name, v.reshape(B, T, cout).sum(1), T)
+    return c
+
+
+def colstat_units(c: ConvCase, unit=128):
+    """[units, 6, cout] float64: per tile of `unit` rows [sum part 0..2 | sum of squares part 0..2] of y - shift, a part being the
+    tile's first, second or third segment; NaN where a part has no rows (a kernel may leave such a slot alone)."""
+    v = c.y - c.shift[None, :]
+    M, T = c.M, c.T
+    units = -(-M // unit)
+    out = np.full((units, 6, c.cout), np.nan)
+    for u in range(units):
+        rows = np.arange(u * unit, min(M, (u + 1) * unit))
+        part = rows // T - (u * unit) // T
+        for p in range(3):
+            sel = rows[part == p]
+            if sel.size:
+                out[u, p] = v[sel].sum(0)
+                out[u, 3 + p] = (v[sel] ** 2).sum(0)
+    need_f32(c.name + " (colstat)", np.nan_to_num(out))
+    return out
+
+
+SQRT_EPS = float(np.sqrt(np.float32(1e-12)))      # what sqrtf(fmaxf(0, 1e-12f)) returns: 1e-6 to f32 rounding
+
+
+def exact_std(var):
+    """sqrt(var) where the variance is the square of a dyadic number, SQRT_EPS where it is 0, NaN (= not asserted) elsewhere."""
+    var = np.asarray(var, dtype=np.float64)
+    root = np.sqrt(var)
+    return np.where(var == 0, SQRT_EPS, np.where(root * 64 == np.round(root * 64), root, np.nan))
+
+
+def colstat_stats(c: ConvCase):
+    yr = c.y.reshape(c.B, c.T, c.cout)
+    return yr.mean(1), exact_std(yr.var(1))
+
+
+@functools.lru_cache(maxsize=None)
+def conv_case(name):
+    """Every conv case of CASE_TABLE by name (built once per process, never modified)."""
+    shape, _, what = name.partition("-")
+    if shape[0] == "C":
+        bt, cout = name[1:].split("-")
+        B, T = (int(v) for v in bt.split("x"))
+        return colstat_case(name, B, T, int(cout))
+    s = SHAPES[shape]
+    f16 = shape[0] == "H"
+    if what in ("rows", "chan"):
+        return gather_case(name, s, what, f16=f16, tee=GATHER_TEE.get(name))
+    per_seg, act, tee, add = DENSE[name]
+    kind = what if what.startswith("split") else "dense"
+    return dense_case(name, s, f16=f16, bias_per_seg=per_seg, act=act, tee=tee, tee_add=add, kind=kind)
+
+
+CONV_CASE_NAMES = tuple(n for n in CASE_TABLE if n.split("-")[0] in SHAPES or n[0] == "C" and n[1].isdigit())
+
+
+# ------------------------------------------------------------------ the Res2Net chain
+
+CHAIN_SHAPES = ((3, 61, 3), (2, 212, 4))        # (B, T, dil)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case(kind, B, T, dil, n=7, ld=1024 + 64):
+    """"onehot": one-hot weights [128][128][3], so the chain is a composition of gathers and adds; "sums": four +-1 weights per output
+    channel (taps and channels mixed), so every output is a signed sum.  Integer bias / shift, scale 1 (layer 3: 2), relu.
+    -> (r [B T, ld] small integers, layers, the expected r after the chain); every chain state y_j and c_{j+1} + y_j an exact f16."""
+    name = "chain-" + kind
+    register(name, "gather" if kind == "onehot" else "dense")
+    rng = np.random.default_rng(T + dil + (kind == "sums"))
+    M = B * T
+    r = rng.integers(0, 3, (M, ld)).astype(np.float64)
+    src = source_rows((T,) * B, 3, dil)
+    layers = []
+    out = r.copy()
+    u = r[:, 128:256].copy()
+    for j in range(1, n + 1):
+        w = np.zeros((128, 128, 3))
+        if kind == "onehot":
+            w[np.arange(128), rng.permutation(128), rng.permutation(128) % 3] = 1.0
+        else:
+            for q in range(4):
+                w[np.arange(128), rng.permutation(128), (rng.permutation(128) + q) % 3] += rng.choice(np.array([-1.0, 1.0]), 128)
+        L = dict(w=w, bias=rng.integers(-2, 2, 128).astype(np.float64), scale=np.full(128, 2.0 if j == 3 else 1.0),
+                 shift=rng.integers(-1, 3, 128).astype(np.float64), dil=dil)
+        acc = conv_sum(u, w, src)
+        y = np.maximum(acc + L["bias"][None, :], 0.0) * L["scale"][None, :] + L["shift"][None, :]
+        need_f32(name, conv_sum(np.abs(u), np.abs(w), src))
+        need_f16(name, y, u)
+        out[:, 128 * j:128 * j + 128] = y
+        if j < n:
+            u = y + r[:, 128 * (j + 1):128 * (j + 2)]
+        layers.append(L)
+    return r, layers, out
+
+
+# ------------------------------------------------------------------ reductions
+
+LENS = ((201, 128), (131, 64), (57, 32))        # (T, n): rel_len = f32(n / T) gives mask_frames = norm_frames = n
+POISON = 1e30
+POISON_F16 = 65504.0
+
+
+def rel_len(T, n):
+    return np.float32(n / T)
+
+
+def reduction_case(B, T, C, lens=None, f16=False, seed=0):
+    """Integer x [B, T, C] in {-3 .. 3} (columns 0 mod 5: 0 / 2 alternating, variance 1 over an even number of frames; 1 mod 5: constant),
+    gate in {0.25, 0.5, 1}, integer res.  `lens`: the live frames of each segment in turn; the frames past them hold POISON (f16: the
+    largest f16) in `x_poisoned`.  -> dict with the expected mean / std (NaN where the variance is no perfect square) over the live
+    frames and y = x gate + res over all rows."""
+    name = "reduce-poison" if lens else "reduce-int"
+    register(name)
+    rng = np.random.default_rng(seed + C + T)
+    n_live = np.array([lens[b % len(lens)] for b in range(B)]) if lens else np.full(B, T)
+    x = rng.integers(-3, 4, (B, T, C)).astype(np.float64)
+    x[:, :, 0::5] = np.where(np.arange(T)[None, :, None] % 2, 2.0, 0.0)
+    x[:, :, 1::5] = rng.integers(-3, 4, (B, 1, len(range(1, C, 5))))
+    gate = rng.choice(np.array([0.25, 0.5, 1.0]), (B, C))
+    res = rng.integers(-4, 5, (B, T, C)).astype(np.float64)
+    mean, std = np.zeros((B, C)), np.zeros((B, C))
+    for b in range(B):
+        live = x[b, :n_live[b]]
+        need_mean(name, live.sum(0), int(n_live[b]))
+        mean[b] = live.mean(0)
+        need_f32(name, ((live - mean[b]) ** 2).sum(0))
+        std[b] = exact_std(live.var(0))
+    y = x * gate[:, None, :] + res
+    need_f32(name, y)
+    if f16:
+        need_f16(name, x, res, y)
+    xp = x.copy()
+    for b in range(B):
+        xp[b, n_live[b]:] = POISON_F16 if f16 else POISON
+    return dict(x=x, x_poisoned=xp, gate=gate, res=res, mean=mean, std=std, y=y, n_live=n_live)
+
+
+def pool_frames(T):
+    """Frames on both sides of every boundary of the pooling kernels: the 4 row phases of the streaming kernel, the 8 (f32) / 4 (f16) row
+    phases and the 32-row staging passes of the LDS kernel, the 16-frame MFMA tiles, the 64-frame wave slots and the 64 / 128 / 192 /
+    208-frame templates of the fused kernels; the first and the last frame."""
+    cand = [0, 1, 3, 4, 7, 8, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 192, 193, 207, 208, 209, 247, 248, T - 2, T - 1]
+    return sorted({t for t in cand if 0 <= t < T})
+
+
+@functools.lru_cache(maxsize=None)
+def pool_onehot_case(B, T, C, lens=None, fused=False, seed=0):
+    """logit 0 at frame t*(b, c) and -200 elsewhere (exp underflows to exactly 0; -200 is an f16 value), integer h: the mean is
+    h[b, t*, c] and the variance 0.  t* walks pool_frames() below the live frames.  Padded frames hold a +200 logit and POISON in h
+    (`h_f16`: the largest f16)."""
+    name = "fused-onehot" if fused else "pool-onehot"
+    register(name, "gather")
+    rng = np.random.default_rng(seed + T + C)
+    n_live = np.array([lens[b % len(lens)] for b in range(B)]) if lens else np.full(B, T)
+    h = rng.integers(-9, 10, (B, T, C)).astype(np.float64)
+    logit = np.full((B, T, C), -200.0)
+    tstar = np.zeros((B, C), dtype=np.int64)
+    for b in range(B):
+        fr = np.array(pool_frames(int(n_live[b])))
+        tstar[b] = fr[(np.arange(C) // (4 if fused else 1) + 3 * b) % len(fr)]
+        logit[b, tstar[b], np.arange(C)] = 0.0
+        logit[b, n_live[b]:] = 200.0
+    mean = np.take_along_axis(h, tstar[:, None, :], 1)[:, 0]
+    need_f16(name, h, logit)
+    hp, hp16 = h.copy(), h.copy()
+    for b in range(B):
+        hp[b, n_live[b]:] = POISON
+        hp16[b, n_live[b]:] = POISON_F16
+    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, tstar=tstar, n_live=n_live)
+
+
+@functools.lru_cache(maxsize=None)
+def pool_uniform_case(B, T, C, level=1.0, fused=False, n=None, seed=0):
+    """All logits of a channel equal (`level` times a per-channel integer) over the n live frames (all T when n is None), n a power of
+    two, integer h: the exact mean, and the exact std on the columns built for it (0 / 2 alternating: variance 1; constant: sqrt(eps)).
+    Padded frames hold a +200 logit and POISON in h (`h_f16`: the largest f16)."""
+    name = "fused-uniform" if fused else "pool-uniform"
+    register(name, "dense")
+    n = T if n is None else n
+    if n & (n - 1) or n > T:
+        raise BudgetError(f"{name}: {n} live frames of {T} are no power of two")
+    rng = np.random.default_rng(seed + T + C)
+    h = rng.integers(-9, 10, (B, T, C)).astype(np.float64)
+    h[:, :, 0::3] = np.where(np.arange(T)[None, :, None] % 2, 2.0, 0.0)
+    h[:, :, 1::3] = rng.integers(-9, 10, (B, 1, len(range(1, C, 3))))
+    logit = np.repeat(level * rng.integers(-3, 4, (B, 1, C)).astype(np.float64), T, 1) + 0.0
+    logit[:, n:] = 200.0
+    live = h[:, :n]
+    need_mean(name, live.sum(1), n)
+    mean = live.mean(1)
+    need_f32(name, ((live - mean[:, None]) ** 2).sum(1))
+    need_f16(name, h, logit)
+    hp, hp16 = h.copy(), h.copy()
+    hp[:, n:], hp16[:, n:] = POISON, POISON_F16
+    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, std=exact_std(live.var(1)), n_live=np.full(B, n))
+
+
+def attend_factors(logit, att=128):
+    """One-hot a1 [B, T, att] and integer wc [C, att] with a1 @ wc.T == logit: one attention channel per distinct logit row (the frames
+    that are nobody's t* share one, the padded frames another, every t* class has its own)."""
+    B, T, C = logit.shape
+    rows, inv = np.unique(logit.reshape(B * T, C), axis=0, return_inverse=True)
+    if len(rows) > att:
+        raise BudgetError(f"{len(rows)} distinct logit rows do not fit {att} attention channels")
+    a1 = np.zeros((B * T, att))
+    a1[np.arange(B * T), np.asarray(inv).reshape(-1)] = 1.0
+    wc = np.zeros((C, att))
+    wc[:, :len(rows)] = rows.T
+    assert np.array_equal((a1 @ wc.T).reshape(B, T, C), logit)
+    return a1.reshape(B, T, att), wc
+
+
+# ------------------------------------------------------------------ products outside the network
+
+def affinity_rows(n, d=192, seed=0):
+    """Rows in {0, +-1} with exactly 16 non-zeros (norm 4, cosine k / 16); row 2 zero; rows 1 and n - 1 copies of row 0 (cosine 1).
+    -> (X, K) with K[i][j] = k / 16."""
+    register("affinity-k16", "dense"), register("affinity-duplicates", "gather")
+    rng = np.random.default_rng(seed + n)
+    X = np.zeros((n, d))
+    for i in range(n):
+        X[i, rng.choice(d, 16, replace=False)] = rng.choice(np.array([-1.0, 1.0]), 16)
+    X[2] = 0.0
+    X[1] = X[0]
+    X[n - 1] = X[0]
+    K = (X @ X.T) / 16.0
+    need_f32("affinity", K * 16.0, K)
+    return X, K
+
+
+def ahc_case(n, d, ld, seed=0):
+    """Integer cluster sums in {-1, 0, 1} drawn from sixteen distinct rows (NaN in columns [d, ld)), inv_count in {1, 1/2, 1/4, 1/8}:
+    nearly every row has many equal best scores.  Planted: copies of one heavy row at indices 16, 64 and 128 apart, on both sides of the diagonal and in the last row,
+    with equal counts, so that their mutual score is each one's maximum and every step of the reduction (in-lane, the 16-lane row, the
+    two waves through LDS, the slot order of the finish kernel) breaks a tie; three adjacent copies of a second heavy row tie across
+    the lanes of a row.  -> (S, count, inv, nn, best), nn the LOWEST index attaining the integer maximum."""
+    register("ahc-ties", "gather"), register("ahc-int", "dense")
+    rng = np.random.default_rng(seed + n + d)
+    S = np.full((n, ld), np.nan)
+    S[:, :d] = rng.integers(-1, 2, (16, d))[rng.integers(0, 16, n)]          # sixteen distinct rows, each many times
+    count = rng.choice(np.array([1.0, 2.0, 4.0, 8.0]), n)
+    heavy = rng.choice(np.array([-3.0, 3.0]), d)
+    group = [i for i in (5, 21, 69, 133, 197, 261) if i < n - 1] + [n - 1]
+    for i in group:
+        S[i, :d] = heavy
+        count[i] = 1.0
+    second = rng.choice(np.array([-3.0, 3.0]), d)
+    second[: d // 2] = -heavy[: d // 2]                     # far from the first group
+    for i in (70, 71, 72):
+        S[i, :d] = second
+        count[i] = 2.0
+    inv = 1.0 / count
+    G = S[:, :d] @ S[:, :d].T
+    score = G * (inv[:, None] * inv[None, :])
+    need_f32("ahc", np.abs(S[:, :d]) @ np.abs(S[:, :d]).T, score)
+    np.fill_diagonal(score, -np.inf)
+    nn = score.argmax(1)                                     # numpy: the first maximum
+    best = score[np.arange(n), nn]
+    assert all(nn[i] == (group[0] if i != group[0] else group[1]) for i in group) and nn[71] == 70 and nn[70] == 71 and nn[72] == 70
+    return S, count, inv, nn.astype(np.int32), best
+
+
+def spectral_case(n, b, ld, onehot=False, seed=0):
+    """K [n, ld] (NaN past column n) with values in {-1, -0.5, 0, 0.25, 0.5, 1}, scale in {0.5, 1, 2}, integer V [n, b]; `onehot`: column c
+    of V is one-hot at a seeded row j_c (the first at row 0, the last at row n - 1), so Y[i][c] names the entry K[i][j_c] that was read."""
+    register("spectral-onehot" if onehot else "spectral-dyadic")
+    rng = np.random.default_rng(seed + n + b)
+    K = np.full((n, ld), np.nan)
+    K[:, :n] = rng.choice(np.array([-1.0, -0.5, 0.0, 0.25, 0.5, 1.0]), (n, n))
+    scale = rng.choice(np.array([0.5, 1.0, 2.0]), n)
+    V = rng.integers(-3, 4, (n, b)).astype(np.float64)
+    if onehot:
+        V[:] = 0.0
+        js = rng.integers(0, n, b)
+        js[0], js[-1] = 0, n - 1
+        V[js, np.arange(b)] = 1.0
+    A = np.clip(K[:, :n], 0.0, None)
+    need_f32("spectral", A.sum(1), (A * scale[None, :]) @ np.abs(V) * scale[:, None])
+    return K, scale, V
+
+
+def spectral_expected(K, scale, V, zero_diag):
+    n = K.shape[0]
+    A = np.clip(K[:, :n], 0.0, None)
+    if zero_diag:
+        A = A.copy()
+        np.fill_diagonal(A, 0.0)
+    return A.sum(1), scale[:, None] * (A @ (scale[:, None] * V))
+
+
+def argmax_case(N, K, D, seed=0):
+    """Integer rows and centres, the centres at (0, K - 1) and (3, 4) duplicated: np.argmax returns the first maximum."""
+    register("argmax-duplicates", "gather"), register("argmax-int", "dense")
+    rng = np.random.default_rng(seed + N + K + D)
+    w = rng.integers(-2, 3, (N, D)).astype(np.float64)
+    c = rng.integers(-2, 3, (K, D)).astype(np.float64)
+    if K > 4:
+        c[4] = c[3]
+    if K > 1:
+        c[K - 1] = c[0]
+    if K == 5:
+        c[3] = c[0]                                         # (K - 1 == 4: the two pairs share a centre)
+    sim = w @ c.T
+    need_f32("sim_argmax", np.abs(w) @ np.abs(c).T)
+    return w, c, sim.argmax(1).astype(np.int32), sim.max(1)
+
+
+def topk_reference(x, k):
+    """np.sort(...)[:, -k:].mean / .std, the statement of diar_diag.asnorm_scores, in float64."""
+    top = np.sort(np.asarray(x, dtype=np.float64), axis=1)[:, -min(k, np.shape(x)[1]):]
+    return top.mean(1), top.std(1)
+
+
+def topk_case(n, k, seed=0):
+    """Rows [7, n] of integers, signs mixed, +0.0 and -0.0 together -> (x, mean, std), NaN where the exact answer is not representable
+    (k no power of two and the quotient no integer; a variance that is no perfect square).
+      row 0: k / 2 copies of +3 above a long run of -3, the k-th value, of which k / 2 are taken: mean 0, std 3
+      row 1: k / 2 copies of 2 above +0.0 and -0.0 mixed, of which k / 2 are taken: mean 1, std 1
+      row 2: 1 and -3 in equal numbers (and one -1 when k is odd) above a run of -30: mean -1, std 2 when k is even
+      rows 3 ..: random integers in {-9 .. 9}: the k-th value tied many times."""
+    register("topk-ties", "gather"), register("topk-int", "dense")
+    rng = np.random.default_rng(seed + n + k)
+    kk = min(k, n)
+    x = rng.integers(-9, 10, (7, n)).astype(np.float64)
+    h = kk // 2
+    if 2 <= kk < n:
+        x[0] = -20.0
+        x[0, :h] = 3.0
+        x[0, h:h + min(n - h, kk + 30)] = -3.0
+        x[1] = -7.0
+        x[1, :h] = 2.0
+        zeros = min(n - h, kk - h + 9)
+        x[1, h:h + zeros] = np.where(np.arange(zeros) % 2, -0.0, 0.0)
+    x[2] = -30.0
+    x[2, :h] = 1.0
+    x[2, h:2 * h] = -3.0
+    if kk % 2:
+        x[2, 2 * h] = -1.0
+    for r in range(3):
+        x[r] = x[r, rng.permutation(n)]
+    mean, std = topk_reference(x, kk)
+    top = np.sort(x, axis=1)[:, -kk:]
+    pow2 = (kk & (kk - 1)) == 0
+    tot = top.sum(1)
+    ss = ((top - mean[:, None]) ** 2).sum(1)
+    mean_ok = np.array([pow2 or t % kk == 0 for t in tot])
+    need_f32("topk", np.abs(top).sum(1), mean[mean_ok], ((top - mean[:, None]) ** 2)[mean_ok], ss[mean_ok])
+    root = np.sqrt(ss / kk)
+    std_ok = mean_ok & np.array([(pow2 or s % kk == 0) for s in ss]) & (root * 64 == np.round(root * 64))
+    return x, np.where(mean_ok, mean, np.nan), np.where(std_ok, std, np.nan)
+
+
+def viterbi_scores(T, K, seed=0):
+    """Integer scores; every third row (and the first four) constant across the states, so that the dp entries, and with them the
+    candidates, tie exactly."""
+    register("viterbi-ties", "gather"), register("viterbi-int", "dense")
+    rng = np.random.default_rng(seed + T + K)
+    s = rng.integers(-3, 4, (T, K)).astype(np.float32)
+    s[::3] = rng.integers(-3, 4, (len(range(0, T, 3)), 1))
+    s[:4] = 1.0
+    return s

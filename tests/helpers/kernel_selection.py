@@ -1,4 +1,5 @@
-"""The kernel selections of the exact-f32 conv operator (`sd_set_tuning`), as one fixture shared by the GPU test modules.
+"""The kernel selections of the exact-f32 conv operator (`sd_set_tuning`), as one fixture shared by the GPU test modules, and the two
+tile choices of the f16 / split16 operators (`f16_tiles`).
 
 Imported, not a conftest: `from kernel_selection import conv_kernel` (with tests/helpers on sys.path) makes the fixture visible
 to the importing module only."""
@@ -37,3 +38,13 @@ def conv_kernel(request):
     select_conv_kernel(request.param)
     yield request.param
     restore_conv_kernel()
+
+
+@pytest.fixture(params=["wide256", "auto"])
+def f16_tiles(request):
+    """"wide256" pins the 256x256 kernel for every cout >= 1024 layer; "auto" is the shipped choice."""
+    from speech_diarization_amd import _native as N
+    lib = N.load()
+    N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, 0 if request.param == "wide256" else -1), "sd_set_tuning")
+    yield request.param
+    N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, -1), "sd_set_tuning")

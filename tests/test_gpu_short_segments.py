@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-from kernel_selection import conv_kernel  # noqa: E402,F401  (the eight selections of the exact-f32 conv, shared fixture)
+from kernel_selection import conv_kernel, f16_tiles  # noqa: E402,F401  (the selections of the f32 and the f16 / split16 convs, shared fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -119,16 +119,6 @@ def test_short_conv1d_cl_f32_epilogues(dev, conv_kernel, B, T, cin, cout, dil):
 
 
 # ------------------------------------------------------------------ 2. the f16 and split16 convs
-
-@pytest.fixture(params=["wide256", "auto"])
-def f16_tiles(request):
-    """"wide256" pins the 256x256 kernel for every cout >= 1024 layer; "auto" is the shipped choice."""
-    from speech_diarization_amd import _native as N
-    lib = N.load()
-    N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, 0 if request.param == "wide256" else -1), "sd_set_tuning")
-    yield request.param
-    N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, -1), "sd_set_tuning")
-
 
 @pytest.mark.parametrize("B,T,cin,cout,k,dil", SHORT_SHAPES)
 def test_short_conv1d_cl_f16_matches_f64(dev, f16_tiles, B, T, cin, cout, k, dil):
