@@ -187,6 +187,16 @@ AHC_PROTOTYPES = {
     "sd_ahc_merge_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
 }
 
+# include/sd_hip_hdbscan.h: the density-clustering entries, same shared object, a table and a version of their own
+SD_HDBSCAN_ABI_VERSION = 1
+HDBSCAN_PROTOTYPES = {
+    "sd_hdbscan_abi_version": (_I, []),
+    "sd_hdb_core_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sd_hdb_core_f32": (_I, [_P, C.c_long, _I, _I, _I, _P, _P, _Z, _P]),
+    "sd_hdb_outgoing_workspace_bytes": (_Z, [_I, _I]),
+    "sd_hdb_outgoing_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -239,6 +249,15 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.sd_ahc_abi_version() != SD_AHC_ABI_VERSION:
             raise RuntimeError(f"libsd_hip.so AHC ABI {lib.sd_ahc_abi_version()} != binding ABI {SD_AHC_ABI_VERSION}; rebuild")
+        missing = [name for name in HDBSCAN_PROTOTYPES if not hasattr(lib, name)]
+        if missing:
+            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_hdbscan.h: {missing}")
+        for name, (res, args) in HDBSCAN_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sd_hdbscan_abi_version() != SD_HDBSCAN_ABI_VERSION:
+            raise RuntimeError(f"libsd_hip.so HDBSCAN ABI {lib.sd_hdbscan_abi_version()} != binding ABI {SD_HDBSCAN_ABI_VERSION}; rebuild")
         for which, st in enumerate((sd_conv_args, sd_layer, sd_se_res2_block, sd_ecapa_weights)):
             if lib.sd_sizeof(which) != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__}: binding layout is {C.sizeof(st)} bytes, the library's {lib.sd_sizeof(which)}; rebuild")

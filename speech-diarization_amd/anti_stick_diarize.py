@@ -394,7 +394,8 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
 
     `clusterer` selects what sits inside the reference's `cluster_hdbscan_two_stage(embs, min_cluster_size=2)`
     [REF :536]: "hdbscan_two_stage" (default: the two-stage glue over `cluster.default_hdbscan_factory`),
-    "ahc" (the same glue with average-linkage AHC cut at `cluster_cos` injected as the clusterer), "ahc_affinity"
+    "ahc" (the same glue with average-linkage AHC cut at `cluster_cos` injected as the clusterer), "hdbscan_gpu" (the same glue
+    over `hdbscan_gpu.HdbscanGpuClusterer.factory()`: HDBSCAN from the rows on the device, no N x N matrix), "ahc_affinity"
     (single-stage AHC on the GPU cosine affinity), or a `clusterer_factory(**kwargs)` callable.
 
     `packed_embeddings=True` embeds every segment as if alone (`embed_segments(..., packed=True)`) instead of in the reference's
@@ -417,10 +418,14 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     if clusterer == "ahc_affinity":
         raw = cluster.ahc_cosine(cosine_affinity(embs, _on_gpu(encode)), cluster_cos)
     else:
-        factory = (None if clusterer == "hdbscan_two_stage" else
-                   cluster.AhcClusterer.factory(cluster_cos) if clusterer == "ahc" else clusterer)
+        if clusterer == "hdbscan_gpu":
+            from . import hdbscan_gpu
+            factory = hdbscan_gpu.HdbscanGpuClusterer.factory()
+        else:
+            factory = (None if clusterer == "hdbscan_two_stage" else
+                       cluster.AhcClusterer.factory(cluster_cos) if clusterer == "ahc" else clusterer)
         if factory is not None and not callable(factory):
-            raise ValueError(f"clusterer must be 'hdbscan_two_stage', 'ahc', 'ahc_affinity' or a factory, got {clusterer!r}")
+            raise ValueError(f"clusterer must be 'hdbscan_two_stage', 'ahc', 'hdbscan_gpu', 'ahc_affinity' or a factory, got {clusterer!r}")
         raw = cluster_hdbscan_two_stage(embs, min_cluster_size=2, clusterer_factory=factory)
     labels = cluster.relabel_by_first_appearance(raw)
     for s, lab in zip(speech2, labels):
@@ -449,9 +454,25 @@ def main(wav_path: str, sr: int = 16000, target_lufs: float = -18.0, vad_thr: fl
     return final
 
 
-def cluster_hdbscan(embs: np.ndarray, min_cluster_size: int = 2, clusterer_factory=None, use_gpu: bool = False) -> np.ndarray:
-    """[REF anti_stick_diarize.py:175-186]; the N x N cosine on the GPU when `use_gpu`."""
+def cluster_hdbscan(embs: np.ndarray, min_cluster_size: int = 2, clusterer_factory=None, use_gpu: bool | str = False) -> np.ndarray:
+    """[REF anti_stick_diarize.py:175-186]; the N x N cosine on the GPU when `use_gpu` is True.  `use_gpu="rows"`: the whole
+    clustering from the rows on the device (`hdbscan_gpu.hdbscan_rows`, metric "cosine"), no matrix and no `clusterer_factory`."""
     from . import cluster
+    if isinstance(use_gpu, str):
+        if use_gpu != "rows":
+            raise ValueError(f"use_gpu must be False, True or 'rows', got {use_gpu!r}")
+        if clusterer_factory is not None:
+            raise ValueError("use_gpu='rows' is a clusterer of its own; it takes no clusterer_factory")
+        import torch
+        from . import hdbscan_gpu
+        embs = np.asarray(embs)
+        if embs.shape[0] < 2:            # as cluster.cluster_hdbscan: one segment is one speaker
+            return np.zeros(embs.shape[0], dtype=int)
+        if not torch.cuda.is_available():
+            raise RuntimeError("use_gpu='rows' runs on the HIP path (a visible GPU); there is no CPU fallback")
+        embs_norm = embs / (np.linalg.norm(embs, axis=1, keepdims=True) + 1e-8)
+        rows = torch.from_numpy(np.ascontiguousarray(embs_norm, dtype=np.float32)).cuda()
+        return hdbscan_gpu.hdbscan_rows(rows, min_cluster_size, None, True, metric="cosine")
     aff = (lambda x: cosine_affinity(x, True)) if use_gpu else None
     return cluster.cluster_hdbscan(embs, min_cluster_size, clusterer_factory, affinity=aff)
 

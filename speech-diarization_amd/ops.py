@@ -576,3 +576,54 @@ def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, 
         N.check(N.load().sd_ahc_merge_f32(sums.data_ptr(), ld, n, d, count.data_ptr(), inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
                                           C.c_float(cos_thr), target.data_ptr(), n_merged.data_ptr(), _stream(sums)), "sd_ahc_merge_f32")
     return target, n_merged
+
+
+# ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)
+
+def _hdb_rows(rows: torch.Tensor) -> tuple[int, int, int]:
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] == 0 or rows.shape[1] == 0 or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise ValueError(f"rows must be a non-empty f32 matrix with contiguous rows, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
+    n, d = rows.shape
+    return n, d, max(rows.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
+
+
+def _hdb_ws(ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def hdb_core(rows: torch.Tensor, k: int, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """core[i] = the k-th largest <rows[i], rows[j]> over j != i, duplicates counted (1 <= k <= min(16, n - 1)): rows f32 [n, d] read
+    in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine) -> f32 [n].  The products are
+    those of `hdb_outgoing`, bit for bit.  `ws`: a uint8 workspace of at least sd_hdb_core_workspace_bytes(n, d, k) to reuse across
+    calls (allocated when None)."""
+    _need_cuda(rows)
+    n, d, ld = _hdb_rows(rows)
+    core = torch.empty((n,), dtype=torch.float32, device=rows.device)
+    lib = N.load()
+    with torch.cuda.device(rows.device):
+        ws = _hdb_ws(ws, int(lib.sd_hdb_core_workspace_bytes(n, d, int(k))), rows.device)
+        N.check(lib.sd_hdb_core_f32(rows.data_ptr(), ld, n, d, int(k), core.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                    _stream(rows)), "sd_hdb_core_f32")
+    return core
+
+
+def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws: torch.Tensor | None = None):
+    """The heaviest edge that leaves the component of every row under w(i, j) = min(core[i], core[j], <rows[i], rows[j]>):
+    rows f32 [n, d] as for `hdb_core`, core f32 [n] (+inf allowed), comp int32 [n] -> (nn int32 [n], best f32 [n]); nn = -1 and
+    best = -inf for a row whose component is everything.  Exactly symmetric w, lowest index among equal ones, bitwise reproducible.
+    `ws`: a uint8 workspace of at least sd_hdb_outgoing_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    _need_cuda(rows, core, comp)
+    n, d, ld = _hdb_rows(rows)
+    for name, t, dt in (("core", core, torch.float32), ("comp", comp, torch.int32)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    nn = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    best = torch.empty((n,), dtype=torch.float32, device=rows.device)
+    lib = N.load()
+    with torch.cuda.device(rows.device):
+        ws = _hdb_ws(ws, int(lib.sd_hdb_outgoing_workspace_bytes(n, d)), rows.device)
+        N.check(lib.sd_hdb_outgoing_f32(rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(),
+                                        ws.data_ptr(), ws.numel() * ws.element_size(), _stream(rows)), "sd_hdb_outgoing_f32")
+    return nn, best
