@@ -197,6 +197,14 @@ HDBSCAN_PROTOTYPES = {
     "sd_hdb_outgoing_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_trace.h: the launch log, same shared object, a table and a version of its own
+SD_TRACE_ABI_VERSION = 1
+TRACE_PROTOTYPES = {
+    "sd_trace_abi_version": (_I, []),
+    "sd_launch_log_enable": (_I, [_I]),
+    "sd_launch_log_read": (_Z, [C.c_char_p, _Z]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -258,11 +266,42 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.sd_hdbscan_abi_version() != SD_HDBSCAN_ABI_VERSION:
             raise RuntimeError(f"libsd_hip.so HDBSCAN ABI {lib.sd_hdbscan_abi_version()} != binding ABI {SD_HDBSCAN_ABI_VERSION}; rebuild")
+        missing = [name for name in TRACE_PROTOTYPES if not hasattr(lib, name)]
+        if missing:
+            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_trace.h: {missing}")
+        for name, (res, args) in TRACE_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sd_trace_abi_version() != SD_TRACE_ABI_VERSION:
+            raise RuntimeError(f"libsd_hip.so trace ABI {lib.sd_trace_abi_version()} != binding ABI {SD_TRACE_ABI_VERSION}; rebuild")
         for which, st in enumerate((sd_conv_args, sd_layer, sd_se_res2_block, sd_ecapa_weights)):
             if lib.sd_sizeof(which) != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__}: binding layout is {C.sizeof(st)} bytes, the library's {lib.sd_sizeof(which)}; rebuild")
         _lib = lib
     return _lib
+
+
+def launch_log_enable(on: bool) -> bool:
+    """Start (clearing the counts) or stop the launch log of include/sd_hip_trace.h; -> whether it was on."""
+    return bool(load().sd_launch_log_enable(int(on)))
+
+
+def launch_log_read() -> dict:
+    """{label: launches} since the last launch_log_enable(True)."""
+    lib = load()
+    need = lib.sd_launch_log_read(None, 0)
+    while True:
+        buf = C.create_string_buffer(need)
+        got = lib.sd_launch_log_read(buf, need)
+        if got <= need:
+            break
+        need = got
+    out = {}
+    for line in buf.value.decode().splitlines():
+        label, _, count = line.rpartition("\t")
+        out[label] = int(count)
+    return out
 
 
 def last_error() -> str:

@@ -2,7 +2,11 @@
 #include <cstdlib>
 
 #include "sd_common.h"
+#include "sd_hip_trace.h"
 #include <atomic>
+#include <cstring>
+#include <map>
+#include <string>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -110,6 +114,83 @@ extern "C" int sd_profile_read(int kind, double* ms, long long* launches, double
   }
   *ms = t; *launches = n; *work = w;
   return SD_OK;
+}
+
+// ---------------------------------------------------------------- launch log (sd_hip_trace.h)
+// Host side only: SD_CHECK_LAUNCH hands over the label of a launch that succeeded; nothing here touches the device or a stream.
+// A record per label POINTER (labels are literals), found by a linear scan under the mutex, so the launch path allocates only the first
+// time a pointer is seen; records of equal text (the same literal in two translation units) are merged when the log is read.
+std::atomic<int> sd_launch_log_state{0};
+namespace {
+struct LaunchRec { const char* label; long long scoped, total; };
+std::mutex g_log_mu;
+std::vector<LaunchRec> g_log;
+std::string g_log_path;            // SD_LAUNCH_LOG: where the whole-process census goes at exit
+
+std::string launch_log_text(bool total) {
+  std::map<std::string, long long> by_text;
+  {
+    std::lock_guard<std::mutex> lk(g_log_mu);
+    for (const LaunchRec& r : g_log)
+      if (total ? r.total : r.scoped) by_text[r.label] += total ? r.total : r.scoped;
+  }
+  std::string out;
+  for (const auto& kv : by_text) out += kv.first + "\t" + std::to_string(kv.second) + "\n";
+  return out;
+}
+
+void launch_log_dump() {
+  if (FILE* f = fopen(g_log_path.c_str(), "w")) {
+    const std::string text = launch_log_text(true);
+    fwrite(text.data(), 1, text.size(), f);
+    fclose(f);
+  }
+}
+
+// SD_LAUNCH_LOG=<path> (with SD_EXPERIMENT=1, as every experiment variable): count every launch of the process, write the lines at exit
+const bool g_log_env = [] {
+  const char* p = sd_experiment_env("SD_LAUNCH_LOG");
+  if (!p || !*p) return false;
+  g_log_path = p;
+  sd_launch_log_state.fetch_or(2);
+  atexit(launch_log_dump);
+  return true;
+}();
+}  // namespace
+
+void sd_launch_log_note(const char* label) {
+  const int state = sd_launch_log_state.load(std::memory_order_relaxed);
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  LaunchRec* rec = nullptr;
+  for (LaunchRec& r : g_log)
+    if (r.label == label) { rec = &r; break; }
+  if (!rec) { g_log.push_back({label, 0, 0}); rec = &g_log.back(); }
+  if (state & 1) ++rec->scoped;
+  if (state & 2) ++rec->total;
+}
+
+extern "C" int sd_trace_abi_version(void) { return SD_TRACE_ABI_VERSION; }
+
+extern "C" int sd_launch_log_enable(int on) {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  int prev;
+  if (on) {
+    for (LaunchRec& r : g_log) r.scoped = 0;
+    prev = sd_launch_log_state.fetch_or(1);
+  } else {
+    prev = sd_launch_log_state.fetch_and(~1);
+  }
+  return prev & 1;
+}
+
+extern "C" size_t sd_launch_log_read(char* buf, size_t cap) {
+  const std::string text = launch_log_text(false);
+  if (buf && cap) {
+    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+    memcpy(buf, text.data(), n);
+    buf[n] = 0;
+  }
+  return text.size() + 1;
 }
 
 static int pad32(int d) { return (int)(((long)d + 31) & ~31L); }     // (callers bound d: a row of more than 2^31 - 32 floats is refused)

@@ -253,7 +253,8 @@ int launch_f16(const void* a1, const void* wc, const void* h, int ldh, int B, in
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)B * (C / CPB))), dim3(256), lds, s, static_cast<const _Float16*>(a1),
                      static_cast<const _Float16*>(wc), static_cast<const _Float16*>(h), ldh, T, C, eps, out, rel_len);
-  SD_CHECK_LAUNCH("asp_attend_pool_f16_kernel");
+  SD_CHECK_LAUNCH(TPW == 1 ? "asp_attend_pool_f16_kernel<1>" : TPW == 2 ? "asp_attend_pool_f16_kernel<2>"
+                  : TPW == 3 ? "asp_attend_pool_f16_kernel<3>" : "asp_attend_pool_f16_kernel<4>");
   return SD_OK;
 }
 
@@ -480,7 +481,10 @@ int launch_f32(const void* a1, const void* wc, const void* h, int ldh, int B, in
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)B * (C / cpb))), dim3(512), lds, s, static_cast<const float*>(a1),
                      static_cast<const float*>(wc), static_cast<const float*>(h), ldh, T, C, cpb, eps, out, wscale, rel_len);
-  SD_CHECK_LAUNCH("asp_attend_pool_f32_kernel");
+  SD_CHECK_LAUNCH(SPLIT ? (NT == 4 ? "asp_attend_pool_f32_kernel<4,split>" : NT == 8 ? "asp_attend_pool_f32_kernel<8,split>"
+                           : NT == 13 ? "asp_attend_pool_f32_kernel<13,split>" : "asp_attend_pool_f32_kernel<16,split>")
+                        : (NT == 4 ? "asp_attend_pool_f32_kernel<4>" : NT == 8 ? "asp_attend_pool_f32_kernel<8>"
+                           : NT == 13 ? "asp_attend_pool_f32_kernel<13>" : "asp_attend_pool_f32_kernel<16>"));
   return SD_OK;
 }
 

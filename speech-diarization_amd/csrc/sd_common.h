@@ -73,12 +73,18 @@ int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec);
       return sd_set_error(SD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
   } while (0)
 
-// Kernel launches report configuration errors through hipGetLastError.
+// Kernel launches report configuration errors through hipGetLastError.  `name` is the launch LABEL: the kernel's own name, then
+// <...> for the instantiation and /... for the walk where the host chose one at run time ("conv_gemm_f32_s64_kernel<32>",
+// "conv_gemm_f16_t256_kernel<f16,direct>/lockstep").  It must be a string literal (or a choice between literals): the launch log
+// (sd_hip_trace.h) keeps the pointer.  With the log off a successful launch costs one relaxed atomic load.
+extern std::atomic<int> sd_launch_log_state;       // sd_api.hip: bit 0 the scoped log (sd_launch_log_enable), bit 1 the whole-process census
+void sd_launch_log_note(const char* label);        // sd_api.hip: host only; no device work, no synchronisation
 #define SD_CHECK_LAUNCH(name)                                                           \
   do {                                                                                  \
     hipError_t e_ = hipGetLastError();                                                  \
     if (e_ != hipSuccess)                                                               \
       return sd_set_error(SD_ERR_HIP, "launch of %s failed: %s", name, hipGetErrorString(e_)); \
+    if (sd_launch_log_state.load(std::memory_order_relaxed)) sd_launch_log_note(name);  \
   } while (0)
 
 // ---- optional per-kernel timing with HIP events on the launch stream (sd_profile_* in sd_hip.h)

@@ -1192,14 +1192,15 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
     const long g = (long)((a->M + S64_T - 1) / S64_T) * nt64;
     const size_t lds64 = (size_t)S64_ST * S64_STAGE * sizeof(float);
     static const int s32 = [] { const char* e = sd_experiment_env("SD_S64_HALF"); return e ? atoi(e) : -1; }();   // 0 | 1: never / always 32-row tiles
-    if (s32 != 0 && (s32 == 1 || g < 128)) {
+    const bool half = s32 != 0 && (s32 == 1 || g < 128);
+    if (half) {
       SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_s64_kernel<32>), (int)lds64));
       hipLaunchKernelGGL(conv_gemm_f32_s64_kernel<32>, dim3((unsigned)(((a->M + 31) / 32) * nt64)), dim3(256), lds64, static_cast<hipStream_t>(stream), *a, vec);
     } else {
       SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_s64_kernel<64>), (int)lds64));
       hipLaunchKernelGGL(conv_gemm_f32_s64_kernel<64>, dim3((unsigned)g), dim3(256), lds64, static_cast<hipStream_t>(stream), *a, vec);
     }
-    SD_CHECK_LAUNCH("conv_gemm_f32_s64_kernel");
+    SD_CHECK_LAUNCH(half ? "conv_gemm_f32_s64_kernel<32>" : "conv_gemm_f32_s64_kernel<64>");
     return SD_OK;
   }
   const long skinny_below = g_skinny_below.load(std::memory_order_relaxed);
@@ -1264,7 +1265,7 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
           else if (best == 6) hipLaunchKernelGGL(conv_gemm_f32_vh_kernel<6>, grid, block, ldsv, hs, *a, vec);
           else hipLaunchKernelGGL(conv_gemm_f32_vh_kernel<7>, grid, block, ldsv, hs, *a, vec);
         }
-        SD_CHECK_LAUNCH("conv_gemm_f32_vh_kernel");
+        SD_CHECK_LAUNCH(best == 5 ? "conv_gemm_f32_vh_kernel<5>" : best == 6 ? "conv_gemm_f32_vh_kernel<6>" : "conv_gemm_f32_vh_kernel<7>");
         if (stat_rows) *stat_rows = 16 * best;
         return SD_OK;
       }
@@ -1317,7 +1318,9 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
       hipLaunchKernelGGL(conv_gemm_f32_kernel<false>, dim3((unsigned)grid), dim3(256), lds,
                          static_cast<hipStream_t>(stream), *a, vec, ord, (int)ntiles);
   }
-  SD_CHECK_LAUNCH("conv_gemm_f32_kernel");
+  // (the register-staged form only under SD_F32_DMA=0, read through sd_experiment_env above)
+  SD_CHECK_LAUNCH(dma ? (symmetric ? "conv_gemm_f32_kernel<dma>/symmetric" : "conv_gemm_f32_kernel<dma>")
+                      : (symmetric ? "conv_gemm_f32_kernel<reg>/symmetric" : "conv_gemm_f32_kernel<reg>"));
   return SD_OK;
 }
 

@@ -1070,10 +1070,25 @@ int launch_w4(const sd_conv_args* a, int vec, hipStream_t stream) {
     SdProfScope prof(SD_PROF_CONV_WIDE, stream, 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), R3_LDS_BYTES, stream, *a, vec);
   }
-  SD_CHECK_LAUNCH("conv_gemm_f16_w4_kernel");
+  SD_CHECK_LAUNCH(sizeof(TO) == 2 ? "conv_gemm_f16_w4_kernel<f16>" : "conv_gemm_f16_w4_kernel<f32>");
   return SD_OK;
 }
 #endif  // SD_WITH_W4
+
+// the launch label of an instantiation and its walk (sd_common.h SD_CHECK_LAUNCH)
+template <typename TO, bool DIRECT, bool SPLIT>
+constexpr const char* t256_label(bool super) {
+  if constexpr (SPLIT) {
+    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<split,direct>/lockstep" : "conv_gemm_f16_t256_kernel<split,direct>/grid";
+    else return "conv_gemm_f16_t256_kernel<split,staged>/grid";
+  } else if constexpr (sizeof(TO) == 2) {
+    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<f16,direct>/lockstep" : "conv_gemm_f16_t256_kernel<f16,direct>/grid";
+    else return "conv_gemm_f16_t256_kernel<f16,staged>/grid";
+  } else {
+    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<f32,direct>/lockstep" : "conv_gemm_f16_t256_kernel<f32,direct>/grid";
+    else return "conv_gemm_f16_t256_kernel<f32,staged>/grid";
+  }
+}
 
 template <typename TO, bool DIRECT, bool SPLIT = false>
 int launch_t256(const sd_conv_args* a, int vec, hipStream_t stream) {
@@ -1094,7 +1109,7 @@ int launch_t256(const sd_conv_args* a, int vec, hipStream_t stream) {
     if (super) hipLaunchKernelGGL(kern, dim3(256), dim3(512), R3_LDS_BYTES, stream, *a, vec, 1);
     else hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(512), R3_LDS_BYTES, stream, *a, vec, 0);
   }
-  SD_CHECK_LAUNCH("conv_gemm_f16_t256_kernel");
+  SD_CHECK_LAUNCH((t256_label<TO, DIRECT, SPLIT>(super)));
   return SD_OK;
 }
 
@@ -1108,7 +1123,8 @@ int launch(const sd_conv_args* a, int vec, hipStream_t stream) {
     SdProfScope prof(SD_PROF_CONV_GEMM, stream, 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), STAGE_BYTES, stream, *a, vec);
   }
-  SD_CHECK_LAUNCH("conv_gemm_f16_kernel");
+  SD_CHECK_LAUNCH(sizeof(TA) == 2 ? (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f16,f16>" : "conv_gemm_f16_kernel<f16,f32>")
+                                  : (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f32,f16>" : "conv_gemm_f16_kernel<f32,f32>"));      // <x, y>
   return SD_OK;
 }
 

@@ -703,7 +703,7 @@ static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long lo
     SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
     hipLaunchKernelGGL(fbank_logmel_kernel<false>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
   }
-  SD_CHECK_LAUNCH("fbank_logmel_kernel");
+  SD_CHECK_LAUNCH("fbank_logmel_kernel<uniform>");
   const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
   {
     int R = 320 / plan->n_mels; if (R < 1) R = 1; if (R > T) R = T;
@@ -711,7 +711,7 @@ static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long lo
     hipLaunchKernelGGL(fbank_finalize_kernel<false>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float),
                        stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R, rel_len,
                        nullptr, nullptr, 0, 0, 0);
-    SD_CHECK_LAUNCH("fbank_finalize_kernel");
+    SD_CHECK_LAUNCH("fbank_finalize_kernel<uniform>");
   }
   return SD_OK;
 }
@@ -770,12 +770,12 @@ extern "C" int sd_fbank_packed_f32(const sd_fbank_plan* plan, const float* wav_d
   SD_CHECK_LAUNCH("fbank_packed_tiles_kernel");
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel<true>), V2_LDS_BYTES));
   hipLaunchKernelGGL(fbank_logmel_kernel<true>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
-  SD_CHECK_LAUNCH("fbank_logmel_kernel");
+  SD_CHECK_LAUNCH("fbank_logmel_kernel<packed>");
   const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
   int R = 320 / plan->n_mels; if (R < 1) R = 1;
   const int threads = ((R * plan->n_mels + 63) / 64) * 64;
   hipLaunchKernelGGL(fbank_finalize_kernel<true>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float), stream, out_dev,
                      ld_out, 1, plan->n_mels, a.maxbuf, use_floor, plan->top_db, 1, R, nullptr, lens_dev, frame_start_dev, a.n_lo, n_max, M);
-  SD_CHECK_LAUNCH("fbank_finalize_kernel");
+  SD_CHECK_LAUNCH("fbank_finalize_kernel<packed>");
   return SD_OK;
 }

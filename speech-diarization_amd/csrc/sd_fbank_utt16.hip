@@ -816,7 +816,7 @@ int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long 
     SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
     hipLaunchKernelGGL(fbank_utt16_kernel<false>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
   }
-  SD_CHECK_LAUNCH("fbank_utt16_kernel");
+  SD_CHECK_LAUNCH("fbank_utt16_kernel<uniform>");
   return SD_OK;
 }
 
@@ -851,6 +851,6 @@ int sd_fbank_utt16_packed_launch(const sd_fbank_plan* plan, const float* wav_dev
   const size_t lds = u16_lds_bytes(n_cap, T);      // (monotone in n: enough for every span the kernel takes, lens[b] <= n_cap)
   SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel<true>), LDS_LIMIT));
   hipLaunchKernelGGL(fbank_utt16_kernel<true>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
-  SD_CHECK_LAUNCH("fbank_utt16_kernel");
+  SD_CHECK_LAUNCH("fbank_utt16_kernel<packed>");
   return SD_OK;
 }

@@ -364,11 +364,15 @@ inline int hd_tiles(int n) { return (n + HD_T - 1) / HD_T; }
 inline int hd_chunks(int nt) { return (nt + HD_CHUNK - 1) / HD_CHUNK; }
 
 template <int KK>
-void hd_launch_core(const float* rows, long ld, int n, int d, int k, float* core, float* ws, int nt, hipStream_t stream) {
+int hd_launch_core(const float* rows, long ld, int n, int d, int k, float* core, float* ws, int nt, hipStream_t stream) {
   const int npad = nt * HD_T;
   const int chunks = hd_chunks(nt);
   hipLaunchKernelGGL(hdb_core_kernel<KK>, dim3((unsigned)chunks, (unsigned)nt), dim3(256), 0, stream, rows, ld, n, d, k, ws, npad, nt);
+  SD_CHECK_LAUNCH(KK == 1 ? "hdb_core_kernel<1>" : KK == 2 ? "hdb_core_kernel<2>" : KK == 4 ? "hdb_core_kernel<4>" : KK == 8 ? "hdb_core_kernel<8>" : "hdb_core_kernel<16>");
   hipLaunchKernelGGL(hdb_core_finish_kernel<KK>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, chunks, npad, n, k, core);
+  SD_CHECK_LAUNCH(KK == 1 ? "hdb_core_finish_kernel<1>" : KK == 2 ? "hdb_core_finish_kernel<2>" : KK == 4 ? "hdb_core_finish_kernel<4>"
+                  : KK == 8 ? "hdb_core_finish_kernel<8>" : "hdb_core_finish_kernel<16>");
+  return SD_OK;
 }
 
 }  // namespace
@@ -396,13 +400,11 @@ extern "C" int sd_hdb_core_f32(const float* rows, long ld, int n, int d, int k, 
   if (ws_bytes < need)
     return sd_set_error(SD_ERR_WORKSPACE, "sd_hdb_core_f32: workspace of %zu bytes, n=%d d=%d k=%d needs %zu", ws_bytes, n, d, k, need);
   float* w = static_cast<float*>(ws);
-  if (k == 1) hd_launch_core<1>(rows, ld, n, d, k, core, w, nt, stream);
-  else if (k == 2) hd_launch_core<2>(rows, ld, n, d, k, core, w, nt, stream);
-  else if (k <= 4) hd_launch_core<4>(rows, ld, n, d, k, core, w, nt, stream);
-  else if (k <= 8) hd_launch_core<8>(rows, ld, n, d, k, core, w, nt, stream);
-  else hd_launch_core<16>(rows, ld, n, d, k, core, w, nt, stream);
-  SD_CHECK_LAUNCH("hdb_core_kernel");
-  return SD_OK;
+  if (k == 1) return hd_launch_core<1>(rows, ld, n, d, k, core, w, nt, stream);
+  if (k == 2) return hd_launch_core<2>(rows, ld, n, d, k, core, w, nt, stream);
+  if (k <= 4) return hd_launch_core<4>(rows, ld, n, d, k, core, w, nt, stream);
+  if (k <= 8) return hd_launch_core<8>(rows, ld, n, d, k, core, w, nt, stream);
+  return hd_launch_core<16>(rows, ld, n, d, k, core, w, nt, stream);
 }
 
 extern "C" size_t sd_hdb_outgoing_workspace_bytes(int n, int d) {

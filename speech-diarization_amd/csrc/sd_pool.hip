@@ -415,6 +415,9 @@ void launch_as(int dtype, const SdSegs& sg, F&& f) {
   else typed(UniformRows{sg.T, sg.rel_len});
 }
 
+// The label of a launch_as launch, from the two decisions launch_as makes: t[storage is f16][map is packed]
+const char* as_label(int dtype, const SdSegs& sg, const char* const (&t)[2][2]) { return t[dtype == SD_DT_F16][sg.packed]; }
+
 // Column statistics left by the conv epilogue (sd_conv_args.colstat) -> per-segment mean (and std).
 // colstat [units][6][C]: sums of (y - pivot) and (y - pivot)^2 over each tile of U rows (128; 80 / 96 / 112 from the variable-height
 // conv kernel), split at the segment boundaries inside the tile (up to three segments: T >= U / 2) (a trailing partial tile counts its
@@ -493,7 +496,10 @@ int sd_seg_mean_std(const void* x, int dtype, int ld, int col0, const SdSegs& sg
       }
     hipLaunchKernelGGL((seg_mean_std_kernel<T, Rows>), grid, dim3(256), 0, s, xt, ld, col0, C, want_std, eps, out, rows);
   });
-  SD_CHECK_LAUNCH("seg_mean_std_kernel");
+  static const char* const wide[2][2] = {{"seg_mean_std_kernel<f32,uniform,64x4>", "seg_mean_std_kernel<f32,packed,64x4>"},
+                                         {"seg_mean_std_kernel<f16,uniform,64x4>", "seg_mean_std_kernel<f16,packed,64x4>"}};
+  SD_CHECK_LAUNCH(small ? (dtype == SD_DT_F16 ? "seg_mean_std_kernel<f16,uniform,16x16>" : "seg_mean_std_kernel<f32,uniform,16x16>")
+                        : as_label(dtype, sg, wide));
   return SD_OK;
 }
 
@@ -531,7 +537,9 @@ int sd_se_scale_residual(const void* x, int ldx, const float* gate, const void* 
                        static_cast<const T*>(res), ldr, r_col0, static_cast<T*>(y), ldy, y_col0, M, rows, C, static_cast<_Float16*>(ys), lds, s_col0,
                        static_cast<const _Float16*>(res_split), ld_rs, rs_col0, write_y);
   });
-  SD_CHECK_LAUNCH("se_scale_residual_kernel");
+  static const char* const label[2][2] = {{"se_scale_residual_kernel<f32,uniform>", "se_scale_residual_kernel<f32,packed>"},
+                                          {"se_scale_residual_kernel<f16,uniform>", "se_scale_residual_kernel<f16,packed>"}};
+  SD_CHECK_LAUNCH(as_label(dtype, sg, label));
   return SD_OK;
 }
 
@@ -559,7 +567,9 @@ int sd_asp_pool(const void* logit, int ldl, const void* h, int dtype, int ldh, c
       }
     hipLaunchKernelGGL((asp_pool_kernel<T, Rows>), dim3((C / 4 + CG - 1) / CG, sg.B), dim3(256), 0, s, lt, ldl, ht, ldh, rows, C, eps, out);
   });
-  SD_CHECK_LAUNCH(staged ? "asp_pool_lds_kernel" : "asp_pool_kernel");
+  static const char* const streaming[2][2] = {{"asp_pool_kernel<f32,uniform>", "asp_pool_kernel<f32,packed>"},
+                                              {"asp_pool_kernel<f16,uniform>", "asp_pool_kernel<f16,packed>"}};
+  SD_CHECK_LAUNCH(staged ? (dtype == SD_DT_F16 ? "asp_pool_lds_kernel<f16>" : "asp_pool_lds_kernel<f32>") : as_label(dtype, sg, streaming));
   return SD_OK;
 }
 
@@ -647,7 +657,7 @@ int sd_colstat_finish_rows(const float* colstat, const float* pivot, const void*
   else
     hipLaunchKernelGGL(colstat_finish_kernel<float>, grid, dim3(256), 0, s, colstat, pivot, static_cast<const float*>(y) + y_col0, ldy, T, C,
                        B * T, want_std, eps, out, unit_rows);
-  SD_CHECK_LAUNCH("colstat_finish_kernel");
+  SD_CHECK_LAUNCH(y_dtype == SD_DT_F16 ? "colstat_finish_kernel<f16>" : "colstat_finish_kernel<f32>");
   return SD_OK;
 }
 

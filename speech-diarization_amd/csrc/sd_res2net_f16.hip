@@ -405,7 +405,10 @@ extern "C" int sd_res2net_chain_f16(void* r, int ld, int B, int T, const sd_laye
       SdProfScope prof(SD_PROF_CONV_GEMM, stream, 2.0 * (double)B * T * RC_CH * 3 * RC_CH * n);
       hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(RC_THREADS), lds, stream, a);
     }
-    SD_CHECK_LAUNCH("res2net_chain_f16_kernel");
+    static const char* const label[7] = {"res2net_chain_f16_kernel<1>", "res2net_chain_f16_kernel<2>", "res2net_chain_f16_kernel<3>", "res2net_chain_f16_kernel<4>",
+                                         "res2net_chain_f16_kernel<5>", "res2net_chain_f16_kernel<6>", "res2net_chain_f16_kernel<7>"};
+    const int tiles = (T + 31) >> 5;
+    SD_CHECK_LAUNCH(label[tiles >= 1 && tiles <= 6 ? tiles - 1 : 6]);
     return SD_OK;
   }
 }

@@ -234,7 +234,9 @@ extern "C" int sd_affinity_apply_f32(const float* K, int N, long ld, int zero_di
     else SD_AP_LAUNCH(2, false);
   }
 #undef SD_AP_LAUNCH
-  SD_CHECK_LAUNCH("affinity_apply_kernel");
+  // <column blocks of 16 per thread, 16-byte or scalar loads of K>
+  SD_CHECK_LAUNCH(b <= 16 ? (vec ? "affinity_apply_kernel<1,vec>" : "affinity_apply_kernel<1,scalar>")
+                          : (vec ? "affinity_apply_kernel<2,vec>" : "affinity_apply_kernel<2,scalar>"));
   const long total = (long)N * b;
   hipLaunchKernelGGL(apply_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, part, sp.splits, N, b, scale, Y, ldy);
   SD_CHECK_LAUNCH("apply_finish_kernel");

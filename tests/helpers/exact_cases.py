@@ -9,9 +9,12 @@ Every generator checks its own bit budget on the host and raises `BudgetError` w
   * a mean divides by a power of two (or the quotient is an integer), quotient and square inside 24 bits.
 A GPU mismatch on one of these cases is therefore never rounding.
 
-`EXACT_COVERAGE` maps a kernel to the cases meant to reach it, read off the dispatch rules of sd_conv_gemm.hip
-(`conv1d_cl_f32_impl`), sd_conv_gemm_f16.hip (`sd_conv1d_cl_f16`, `sd_conv1d_cl_split16`), sd_pool.hip and sd_ecapa.hip and
-stated as data: a case names its kernels, the table is their inverse."""
+`CASE_TABLE` names, for every case, the launch LABELS (include/sd_hip_trace.h: kernel, instantiation, walk) its runs reach on the
+MI355X, and `F32_LABELS` / `f16_label` / `split_labels` the one label of each single run (case x selection x storage types x tuning);
+tests/test_gpu_exact.py holds every run to its label through the launch log, so these are checked facts, not intentions.  Each entry
+is derived from the dispatch rules of sd_conv_gemm.hip (`conv1d_cl_f32_impl`), sd_conv_gemm_f16.hip (`sd_conv1d_cl_f16`,
+`sd_conv1d_cl_split16`), sd_pool.hip and sd_asp_fused.hip; the derivation stands beside it.  `EXACT_COVERAGE` is the inverse:
+label -> cases."""
 import functools
 from dataclasses import dataclass
 
@@ -51,71 +54,199 @@ def need_mean(name, total, divisor):
     need_f32(name + " (mean^2)", q * q)
 
 
-# ------------------------------------------------------------------ kernels and coverage
+# ------------------------------------------------------------------ conv shapes
+
+# the shapes of the issue (what each crosses: the docstring of tests/test_gpu_exact.py).  H*: the same shapes for sd_conv1d_cl_f16, whose
+# activations come in groups of 8 channels (S1's 36 channels are refused there: 40).  N128 / W*: the narrow and wide split16 forms.
+SHAPES = {
+    "S1": dict(B=3, T=57, cin=36, cout=72, k=3, dil=2),
+    "S2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "S3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
+    "S4": dict(B=70, T=1, cin=544, cout=40, k=1, dil=1),
+    "S5": dict(B=8, T=128, cin=32, cout=512, k=3, dil=2),        # fewer than 128 tiles of 128x128 but 128 of 64x64: the 64-row ring kernel
+    "P": dict(spans=(5, 7, 5, 9, 131), cin=36, cout=72, k=3, dil=2),
+    "H1": dict(B=3, T=57, cin=40, cout=72, k=3, dil=2),
+    "H2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "H2w": dict(B=2, T=131, cin=80, cout=1100, k=5, dil=1),
+    "H2L": dict(B=2, T=131, cin=80, cout=1024, k=5, dil=1),      # four column tiles of 256: the lockstep walk of the 256x256 kernel
+    "H3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
+    "N128": dict(B=3, T=57, cin=36, cout=128, k=3, dil=2),
+    "W1032": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
+    "W256": dict(B=2, T=131, cin=80, cout=256, k=5, dil=1),
+    "W1024": dict(B=2, T=131, cin=80, cout=1024, k=5, dil=1),    # H2L for the wide split form: four column tiles, the lockstep walk
+}
+# the epilogue of each dense case: (per-segment bias, act, (tee_lo, tee_hi) or None, tee_add)
+DENSE = {
+    "S1-dense": (True, "relu", (8, 40), True), "S2-dense": (False, "relu", None, False), "S2-dense-tee": (True, None, (128, 256), False),
+    "S3-dense": (True, "relu", (4, 52), True), "S4-dense": (False, "relu", None, False),
+    "S5-dense": (True, "relu", (8, 40), True), "P-dense": (True, "relu", (8, 40), True),
+    "H1-dense": (True, "relu", (8, 40), True), "H2-dense": (False, "relu", None, False), "H2-dense-tee": (True, None, (128, 256), False),
+    "H2w-dense-tee": (True, "relu", (128, 256), False), "H3-dense": (True, "relu", (8, 56), True), "H2L-dense": (False, "relu", None, False),
+    "N128-split_x": (True, "relu", (0, 128), True), "N128-split_w": (True, None, (0, 128), True),
+    "W1032-split_x": (False, "relu", None, False), "W1032-split_w": (False, "relu", (128, 256), False),
+    "W256-split_x": (False, "relu", None, False), "W256-split_w": (False, None, None, False), "W1024-split_x": (False, "relu", None, False),
+}
+GATHER_TEE = {"N128-rows": (0, 128), "H1-rows": (8, 40), "S1-rows": (8, 40), "W1032-rows": (128, 256)}
+
+
+
+# ------------------------------------------------------------------ kernels, labels and coverage
 
 F32_CONV_KERNELS = ("conv_gemm_f32_kernel", "conv_gemm_f32_s64_kernel", "skinny_gemm_f32_kernel", "conv_gemm_f32_vh_kernel",
                     "conv_gemm_f32_n64_kernel", "conv_gemm_f32_t256_kernel", "conv_gemm_f32_packed_kernel",
                     "seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel")
 F16_CONV_KERNELS = ("conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel")
-SPLIT_CONV_KERNELS = ("conv_gemm_split16_n128_kernel", "conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")
-CONV_KERNELS = F32_CONV_KERNELS + F16_CONV_KERNELS + SPLIT_CONV_KERNELS + ("res2net_chain_f16_kernel",)
+SPLIT_CONV_KERNELS = ("conv_gemm_split16_n128_kernel", "split16_pack_kernel")
+CONV_KERNELS = F32_CONV_KERNELS + F16_CONV_KERNELS + SPLIT_CONV_KERNELS + ("res2net_chain_f16_kernel", "chain_pack_kernel")
 REDUCTION_KERNELS = ("seg_mean_std_kernel", "se_scale_residual_kernel", "asp_pool_kernel", "asp_pool_lds_kernel",
                      "asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel", "colstat_finish_kernel")
 PRODUCT_KERNELS = ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel", "sim_argmax_kernel", "ahc_nearest_kernel",
                    "ahc_nearest_finish_kernel", "ahc_merge_kernel", "affinity_apply_kernel", "apply_finish_kernel",
-                   "affinity_degree_kernel", "topk_mean_std_kernel", "viterbi_kernel")
+                   "affinity_degree_kernel", "topk_mean_std_kernel", "viterbi_kernel", "fill_f32_kernel")
 ALL_KERNELS = CONV_KERNELS + REDUCTION_KERNELS + PRODUCT_KERNELS
 
-# which kernels a conv shape reaches under the eight selections of kernel_selection.CONV_KERNELS (sd_conv_gemm.hip conv1d_cl_f32_impl):
-# S1 / S2 / S3 are small time-axis launches ("auto": the 64x64 ring kernel, "split32": the 32x32 split-K kernel, then the pinned
-# 128x128, 128x64 and 80 / 96 / 112-row kernels); S2 has cout >= 1024 ("wide256": the 256x256 ring kernel); S4 is T = 1 ("auto": the
-# split-K 32x32 kernel; through sd_seg_gemm_f32 the grid split-K pair; the other selections the 128x128 / 128x64 kernels)
-_TIME = ("conv_gemm_f32_s64_kernel", "skinny_gemm_f32_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "conv_gemm_f32_vh_kernel")
-_WIDE = _TIME + ("conv_gemm_f32_t256_kernel",)
-_SEG = ("skinny_gemm_f32_kernel", "conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel")
-_PACKED = ("conv_gemm_f32_packed_kernel",)
-# sd_conv1d_cl_f16: the 128x128 kernel unless x is f16, cout >= 1024 and the launch is not "small" (pinned by SD_TUNE_F16_NARROW_TILES)
-_H128 = ("conv_gemm_f16_kernel",)
-_H256 = ("conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel")
-# sd_conv1d_cl_split16: f32 x -> the 128x128 kernel that splits while staging; packed x (sd_split16_pack_f32) -> the 256x256 kernel
-_SN = ("conv_gemm_split16_n128_kernel",)
-_SW = ("conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")
-_CS = ("conv_gemm_f32_kernel", "conv_gemm_f32_n64_kernel", "conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel",
-       "conv_gemm_f16_t256_kernel<split>", "colstat_finish_kernel")
-_POOL = ("asp_pool_kernel", "asp_pool_lds_kernel")
-_FUSED = ("asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel")
 
-# case name -> (kind, kernels it is meant to reach); kind: "gather" (one-hot weights, one-hot logits, planted ties: the answer names the
+def kernel_of(label):
+    """The kernel a launch label names: the text before the first '<' or '/'."""
+    return label.replace("/", "<").split("<")[0]
+
+
+# ---- sd_conv1d_cl_f32: the label of every shape under the eight selections of kernel_selection.CONV_KERNELS.
+# conv1d_cl_f32_impl, with t128 = ceil(M / 128) ceil(cout / 128), in this order:
+#   1. no colstat, T > 1, M >= 64 and t128 < S64 (128; 0 unless "auto"): the 64x64 ring kernel; <32> when ceil(M / 64) ceil(cout / 64) < 128
+#   2. no colstat and t128 < SKINNY (128; 0 from "tiles128" on): the 32x32 split-K kernel
+#   3. cout >= 1024 and ceil(M / 256) ceil(cout / 256) >= WIDE (1024; 0 under "wide256"), no tee_add, no colstat at T < 128: the 256x256 kernel
+#   4. T > 1, and a colstat only for a caller that takes other units (the public entry does not): 80 / 96 / 112 rows when pinned
+#      ("auto" / "split32": when 1.02 J / 8 per round of 256 tiles beats 0.97 of the cheaper of 5. and 6.; never on these small shapes)
+#   5. 128x64 tiles when pinned ("tiles64"), or by the rule when 0.52 rounds of half tiles < 0.97 rounds of tiles; with a colstat only at
+#      T >= 128 and cout % 64 == 0
+#   6. the 128x128 kernel, staged by DMA in the shipped build
+_S32, _S64 = "conv_gemm_f32_s64_kernel<32>", "conv_gemm_f32_s64_kernel<64>"
+_SK, _DMA, _N64, _T256 = "skinny_gemm_f32_kernel", "conv_gemm_f32_kernel<dma>", "conv_gemm_f32_n64_kernel", "conv_gemm_f32_t256_kernel"
+
+
+def _selections(auto, split32=_SK, tiles64=_N64, rows=True, wide256=_DMA):
+    vh = {f"rows{16 * j}": f"conv_gemm_f32_vh_kernel<{j}>" if rows else _DMA for j in (5, 6, 7)}
+    return {"auto": auto, "split32": split32, "tiles128": _DMA, "tiles64": tiles64, **vh, "wide256": wide256}
+
+
+F32_LABELS = {
+    "S1": _selections(_S32),                        # t128 = 2; M = 171 >= 64, 3 x 2 tiles of 64x64
+    "S2": _selections(_S32, wide256=_T256),         # t128 = 27; 5 x 17 = 85 tiles of 64x64; cout >= 1024: 2 x 5 tiles of 256x256
+    "S3": _selections(_SK),                         # M = 45 < 64: rule 1 does not apply, rule 2 does (t128 = 1)
+    "S4": _selections(_SK, rows=False),             # T = 1: neither rule 1 nor rule 4
+    "S5": _selections(_S64),                        # t128 = 8 x 4 = 32 < 128, 16 x 8 = 128 tiles of 64x64: not < 128
+    # with a colstat rules 1, 2 and 4 are out.  (3, 128) x 256: t128 = 6, 12 half tiles, one round each, 0.52 < 0.97 -> rule 5 by itself
+    "C3x128-256": _selections(_N64, split32=_N64, rows=False),
+    "C5x64-256": _selections(_DMA, split32=_DMA, tiles64=_DMA, rows=False),       # T = 64 < 128: rule 5 is out as well
+}
+SEG_GEMM_LABELS = ("seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel")    # S4 through sd_seg_gemm_f32: M <= 256, cin_pad = 544 >= 512
+PACKED_LABEL = "conv_gemm_f32_packed_kernel"
+
+# ---- sd_conv1d_cl_f16: the 128x128 kernel <x, y> unless x is f16, cout >= 1024, the launch is not "small" (cout <= 1024 and at most
+# SD_TUNE_F16_NARROW_TILES tiles of 256x256: 128 shipped = "auto", 0 = "wide256"), there is no tee_add and no colstat at T < 128.  Then the
+# 256x256 kernel <y, epilogue>: "direct" (registers) for relu / identity with a per-channel bias, no tee and aligned slices, else "staged";
+# the direct form walks in lockstep when the column tiles come in fours and there are at least SD_TUNE_T256_LOCKSTEP_TILES tiles
+# (shipped: 1024, so never here; the tests pin 0), else one workgroup per tile ("grid").
+H_EPILOGUE = {"H2-rows": "direct", "H2-chan": "direct", "H2-dense": "direct", "H2-dense-tee": "staged", "H2w-dense-tee": "staged",
+              "H2L-rows": "direct", "H2L-dense": "direct", "C3x128-1024": "direct"}       # the cases with cout >= 1024 that may take it
+
+
+def _cout(name):
+    return SHAPES[name.split("-")[0]]["cout"] if name.split("-")[0] in SHAPES else int(name.split("-")[1])
+
+
+def f16_label(name, tiles, x16, y16, lockstep=False):
+    """The label of one sd_conv1d_cl_f16 run of case `name`: tiles "auto" / "wide256", f16 or f32 x and y, lockstep tuning 0 or shipped."""
+    x, y = ("f16" if x16 else "f32"), ("f16" if y16 else "f32")
+    cout = _cout(name)
+    if not (x16 and name in H_EPILOGUE and (cout > 1024 or tiles == "wide256")):
+        return f"conv_gemm_f16_kernel<{x},{y}>"
+    walk = "lockstep" if lockstep and H_EPILOGUE[name] == "direct" and -(-cout // 256) % 4 == 0 else "grid"
+    return f"conv_gemm_f16_t256_kernel<{y},{H_EPILOGUE[name]}>/{walk}"
+
+
+# ---- sd_conv1d_cl_split16: f32 x (the narrow form) -> the 128x128 kernel; x packed by sd_split16_pack_f32 -> the 256x256 kernel
+# <split, epilogue>, "staged" as well whenever y is written as split halves; walks as above
+W_EPILOGUE = {"W1032-rows": "staged", "W1032-split_x": "direct", "W1032-split_w": "staged", "W256-chan": "direct", "W256-split_x": "direct",
+              "W256-split_w": "direct", "W1024-chan": "direct", "W1024-split_x": "direct", "C3x128-256": "direct"}
+
+
+def split_labels(name, split_out=False, lockstep=False):
+    """The labels of one sd_conv1d_cl_split16 run (the wide form packs its activations first)."""
+    if name[0] == "N":
+        return ("conv_gemm_split16_n128_kernel",)
+    form = "staged" if split_out else W_EPILOGUE[name]
+    walk = "lockstep" if lockstep and form == "direct" and -(-_cout(name) // 256) % 4 == 0 else "grid"
+    return ("split16_pack_kernel", f"conv_gemm_f16_t256_kernel<split,{form}>/{walk}")
+
+
+def _f32(shape, seg=False):
+    return tuple(sorted(set(F32_LABELS[shape].values()) | set(SEG_GEMM_LABELS if seg else ())))
+
+
+def _f16(name, lockstep):
+    runs = {f16_label(name, t, x, y) for t in ("auto", "wide256") for x in (True, False) for y in (True, False)}
+    if lockstep:
+        runs |= {f16_label(name, t, True, y, True) for t in ("auto", "wide256") for y in (True, False)}
+    return tuple(sorted(runs))
+
+
+def _split(name):
+    return tuple(sorted(set(split_labels(name)) | set(split_labels(name, split_out=True) if _cout(name) % 32 == 0 else ())
+                        | set(split_labels(name, lockstep=True) if _cout(name) == 1024 else ())))
+
+
+_CS = ("colstat_finish_kernel<f16>", "colstat_finish_kernel<f32>")
+_REDUCE = tuple(f"seg_mean_std_kernel<{t},uniform,{f}>" for t in ("f32", "f16") for f in ("16x16", "64x4")) + \
+    tuple(f"se_scale_residual_kernel<{t},uniform>" for t in ("f32", "f16"))
+_REDUCE_PACKED = tuple(f"{k}<{t},packed{f}>" for k, f in (("seg_mean_std_kernel", ",64x4"), ("se_scale_residual_kernel", "")) for t in ("f32", "f16"))
+_POOL = ("asp_pool_lds_kernel<f32>", "asp_pool_lds_kernel<f16>", "asp_pool_kernel<f32,uniform>", "asp_pool_kernel<f16,uniform>")
+_POOL_PACKED = ("asp_pool_kernel<f32,packed>", "asp_pool_kernel<f16,packed>")
+_FUSED = tuple(f"asp_attend_pool_f32_kernel<{n}{s}>" for n in (4, 8, 13, 16) for s in ("", ",split")) + \
+    tuple(f"asp_attend_pool_f16_kernel<{n}>" for n in (1, 2, 3, 4))
+_CHAIN = tuple(f"res2net_chain_f16_kernel<{n}>" for n in range(1, 8)) + ("chain_pack_kernel", "conv_gemm_f16_kernel<f16,f16>")
+_AFFINITY = ("affinity_sym_kernel<exact f32>", "affinity_sym_kernel<split16x3>", "l2norm_rows_kernel", "adjacent_cosine_kernel")
+# the forms of ops.cosine_affinity that are not the triangle kernel: an odd ldo or N % 4 != 0 (f32: the symmetric conv launch, which the
+# 32x32 split-K kernel takes below 128 tiles of 128x128 and the 128x128 kernel's band walk from there on; split16: 2^-8 as a per-column
+# scale, filled, and every tile through the wide split conv, whose slices are unaligned here: the staged epilogue) and `rows=` blocks
+_AFFINITY_CONV = ("skinny_gemm_f32_kernel", "conv_gemm_f32_kernel<dma>/symmetric", "fill_f32_kernel", "split16_pack_kernel",
+                  "conv_gemm_f16_t256_kernel<split,staged>/grid")
+_AHC = ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel")
+# sd_affinity_apply_f32: one block of 16 columns per thread up to b = 16, two above; 16-byte loads of K when its rows are 16-byte aligned
+_SPECTRAL = tuple(f"affinity_apply_kernel<{nj},{ld}>" for nj in (1, 2) for ld in ("vec", "scalar")) + ("apply_finish_kernel", "affinity_degree_kernel")
+
+# case name -> (kind, labels its runs reach); kind: "gather" (one-hot weights, one-hot logits, planted ties: the answer names the
 # element that was read) or "dense" (integer arithmetic over every element)
 CASE_TABLE = {
-    **{f"{s}-{w}": ("gather", r) for s, r in (("S1", _TIME), ("S2", _WIDE), ("S3", _TIME), ("S4", _SEG), ("P", _PACKED)) for w in ("rows", "chan")},
-    "S1-dense": ("dense", _TIME), "S2-dense": ("dense", _WIDE), "S2-dense-tee": ("dense", _WIDE), "S3-dense": ("dense", _TIME),
-    "S4-dense": ("dense", _SEG), "P-dense": ("dense", _PACKED),
-    **{f"{s}-{w}": ("gather", r) for s, r in (("H1", _H128), ("H2", _H256), ("H3", _H128)) for w in ("rows", "chan")},
-    "H1-dense": ("dense", _H128), "H2-dense": ("dense", _H256), "H2-dense-tee": ("dense", _H256), "H2w-dense-tee": ("dense", _H256),
-    "H3-dense": ("dense", _H128), "H2L-rows": ("gather", _H256), "H2L-dense": ("dense", _H256),
-    "N128-rows": ("gather", _SN), "N128-chan": ("gather", _SN), "N128-split_x": ("dense", _SN), "N128-split_w": ("dense", _SN),
-    "W1032-rows": ("gather", _SW), "W1032-split_x": ("dense", _SW), "W1032-split_w": ("dense", _SW),
-    "W256-chan": ("gather", _SW), "W256-split_x": ("dense", _SW), "W256-split_w": ("dense", _SW),
-    "C3x128-256": ("dense", _CS), "C5x64-256": ("dense", _CS), "C11x64-1024": ("dense", _CS), "C3x128-1024": ("dense", _CS),
-    "chain-onehot": ("gather", ("res2net_chain_f16_kernel", "conv_gemm_f16_kernel")),
-    "chain-sums": ("dense", ("res2net_chain_f16_kernel", "conv_gemm_f16_kernel")),
-    "reduce-int": ("dense", ("seg_mean_std_kernel", "se_scale_residual_kernel")),
-    "reduce-poison": ("gather", ("seg_mean_std_kernel", "se_scale_residual_kernel")),
-    "pool-onehot": ("gather", _POOL), "pool-uniform": ("dense", _POOL),
+    **{f"{s}-{w}": ("gather", _f32(s, s == "S4")) for s in ("S1", "S2", "S3", "S4", "S5") for w in ("rows", "chan")},
+    "S1-dense": ("dense", _f32("S1")), "S2-dense": ("dense", _f32("S2")), "S2-dense-tee": ("dense", _f32("S2")), "S3-dense": ("dense", _f32("S3")),
+    "S4-dense": ("dense", _f32("S4", True)), "S5-dense": ("dense", _f32("S5")),
+    "P-rows": ("gather", (PACKED_LABEL,)), "P-chan": ("gather", (PACKED_LABEL,)), "P-dense": ("dense", (PACKED_LABEL,)),
+    **{f"{s}-{w}": ("gather", _f16(f"{s}-{w}", s == "H2")) for s in ("H1", "H2", "H3") for w in ("rows", "chan")},
+    "H1-dense": ("dense", _f16("H1-dense", False)), "H2-dense": ("dense", _f16("H2-dense", True)),
+    "H2-dense-tee": ("dense", _f16("H2-dense-tee", True)), "H2w-dense-tee": ("dense", _f16("H2w-dense-tee", True)),
+    "H3-dense": ("dense", _f16("H3-dense", False)), "H2L-rows": ("gather", _f16("H2L-rows", True)), "H2L-dense": ("dense", _f16("H2L-dense", True)),
+    "N128-rows": ("gather", _split("N128-rows")), "N128-chan": ("gather", _split("N128-chan")),
+    "N128-split_x": ("dense", _split("N128-split_x")), "N128-split_w": ("dense", _split("N128-split_w")),
+    "W1032-rows": ("gather", _split("W1032-rows")), "W1032-split_x": ("dense", _split("W1032-split_x")), "W1032-split_w": ("dense", _split("W1032-split_w")),
+    "W256-chan": ("gather", _split("W256-chan")), "W256-split_x": ("dense", _split("W256-split_x")), "W256-split_w": ("dense", _split("W256-split_w")),
+    "W1024-chan": ("gather", _split("W1024-chan")), "W1024-split_x": ("dense", _split("W1024-split_x")),
+    "C3x128-256": ("dense", tuple(sorted(set(_f32("C3x128-256")) | set(_f16("C3x128-256", False)) | set(split_labels("C3x128-256")))) + _CS),
+    "C5x64-256": ("dense", tuple(sorted(set(_f32("C5x64-256")) | set(_f16("C5x64-256", False)))) + _CS),
+    "C11x64-1024": ("dense", _f16("C11x64-1024", False) + _CS), "C3x128-1024": ("dense", _f16("C3x128-1024", False) + _CS),
+    "chain-onehot": ("gather", _CHAIN), "chain-sums": ("dense", _CHAIN),
+    "reduce-int": ("dense", _REDUCE + _REDUCE_PACKED), "reduce-poison": ("gather", ("seg_mean_std_kernel<f32,uniform,16x16>", "seg_mean_std_kernel<f16,uniform,16x16>")),
+    "pool-onehot": ("gather", _POOL + _POOL_PACKED), "pool-uniform": ("dense", _POOL),
     "fused-onehot": ("gather", _FUSED), "fused-uniform": ("dense", _FUSED),
-    "affinity-k16": ("dense", ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel", "conv_gemm_f32_kernel",
-                               "conv_gemm_f16_t256_kernel<split>", "split16_pack_kernel")),
-    "affinity-duplicates": ("gather", ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel")),
-    "ahc-ties": ("gather", ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel")),
-    "ahc-int": ("dense", ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel")),
-    "spectral-dyadic": ("dense", ("affinity_apply_kernel", "apply_finish_kernel", "affinity_degree_kernel")),
-    "spectral-onehot": ("gather", ("affinity_apply_kernel", "apply_finish_kernel", "affinity_degree_kernel")),
+    "affinity-k16": ("dense", _AFFINITY + _AFFINITY_CONV), "affinity-duplicates": ("gather", _AFFINITY),
+    "ahc-ties": ("gather", _AHC), "ahc-int": ("dense", _AHC),
+    "spectral-dyadic": ("dense", _SPECTRAL), "spectral-onehot": ("gather", _SPECTRAL),
     "argmax-duplicates": ("gather", ("sim_argmax_kernel",)), "argmax-int": ("dense", ("sim_argmax_kernel",)),
     "topk-ties": ("gather", ("topk_mean_std_kernel",)), "topk-int": ("dense", ("topk_mean_std_kernel",)),
     "viterbi-ties": ("gather", ("viterbi_kernel",)), "viterbi-int": ("dense", ("viterbi_kernel",)),
 }
-assert all(kind in ("gather", "dense") and set(ks) <= set(ALL_KERNELS) for kind, ks in CASE_TABLE.values())
+assert all(kind in ("gather", "dense") and {kernel_of(lb) for lb in ks} <= set(ALL_KERNELS) for kind, ks in CASE_TABLE.values())
 
 
 def register(name, kind=None):
@@ -128,7 +259,7 @@ def register(name, kind=None):
 
 
 def coverage(table=None):
-    """kernel -> case names, the inverse of CASE_TABLE."""
+    """label -> case names, the inverse of CASE_TABLE."""
     out = {}
     for name, (_, kernels) in (CASE_TABLE if table is None else table).items():
         for k in kernels:
@@ -140,36 +271,6 @@ EXACT_COVERAGE = coverage()
 
 
 # ------------------------------------------------------------------ convs
-
-# the shapes of the issue (what each crosses: the docstring of tests/test_gpu_exact.py).  H*: the same shapes for sd_conv1d_cl_f16, whose
-# activations come in groups of 8 channels (S1's 36 channels are refused there: 40).  N128 / W*: the narrow and wide split16 forms.
-SHAPES = {
-    "S1": dict(B=3, T=57, cin=36, cout=72, k=3, dil=2),
-    "S2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
-    "S3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
-    "S4": dict(B=70, T=1, cin=544, cout=40, k=1, dil=1),
-    "P": dict(spans=(5, 7, 5, 9, 131), cin=36, cout=72, k=3, dil=2),
-    "H1": dict(B=3, T=57, cin=40, cout=72, k=3, dil=2),
-    "H2": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
-    "H2w": dict(B=2, T=131, cin=80, cout=1100, k=5, dil=1),
-    "H2L": dict(B=2, T=131, cin=80, cout=1024, k=5, dil=1),      # four column tiles of 256: the lockstep walk of the 256x256 kernel
-    "H3": dict(B=5, T=9, cin=128, cout=100, k=3, dil=4),
-    "N128": dict(B=3, T=57, cin=36, cout=128, k=3, dil=2),
-    "W1032": dict(B=2, T=131, cin=80, cout=1032, k=5, dil=1),
-    "W256": dict(B=2, T=131, cin=80, cout=256, k=5, dil=1),
-}
-# the epilogue of each dense case: (per-segment bias, act, (tee_lo, tee_hi) or None, tee_add)
-DENSE = {
-    "S1-dense": (True, "relu", (8, 40), True), "S2-dense": (False, "relu", None, False), "S2-dense-tee": (True, None, (128, 256), False),
-    "S3-dense": (True, "relu", (4, 52), True), "S4-dense": (False, "relu", None, False), "P-dense": (True, "relu", (8, 40), True),
-    "H1-dense": (True, "relu", (8, 40), True), "H2-dense": (False, "relu", None, False), "H2-dense-tee": (True, None, (128, 256), False),
-    "H2w-dense-tee": (True, "relu", (128, 256), False), "H3-dense": (True, "relu", (8, 56), True), "H2L-dense": (False, "relu", None, False),
-    "N128-split_x": (True, "relu", (0, 128), True), "N128-split_w": (True, None, (0, 128), True),
-    "W1032-split_x": (False, "relu", None, False), "W1032-split_w": (False, "relu", (128, 256), False),
-    "W256-split_x": (False, "relu", None, False), "W256-split_w": (False, None, None, False),
-}
-GATHER_TEE = {"N128-rows": (0, 128), "H1-rows": (8, 40), "S1-rows": (8, 40), "W1032-rows": (128, 256)}
-
 
 def source_rows(lengths, k, dil):
     """[M, k] int64: the row tap j of output row m reads, reflected inside m's segment (segments given by their lengths)."""
@@ -410,7 +511,9 @@ CONV_CASE_NAMES = tuple(n for n in CASE_TABLE if n.split("-")[0] in SHAPES or n[
 
 # ------------------------------------------------------------------ the Res2Net chain
 
-CHAIN_SHAPES = ((3, 61, 3), (2, 212, 4))        # (B, T, dil)
+# (B, T, dil): one instantiation of the chain kernel per 32-row time tile, ceil(T / 32) = 1 .. 7 -- T = 32 the upper edge of the first,
+# 65 / 97 / 129 / 161 the first T of the third to sixth, 61 and 212 (the longest the kernel takes) the second and the seventh
+CHAIN_SHAPES = ((3, 61, 3), (2, 212, 4), (2, 32, 2), (2, 65, 3), (2, 97, 2), (2, 129, 3), (2, 161, 4))
 
 
 @functools.lru_cache(maxsize=None)

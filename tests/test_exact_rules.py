@@ -1,6 +1,6 @@
 """The known-answer cases of tests/helpers/exact_cases.py, checked without a GPU: every integer reference against independent arithmetic
 (torch conv1d with reflect padding in float64, sklearn, the numpy stand-ins of ahc_ref / spectral_ref, the numpy statements of
-diar_diag.py) -- EXACTLY equal, not close; every case inside its bit budget and an oversized one refused; `EXACT_COVERAGE` complete; and
+diar_diag.py) -- EXACTLY equal, not close; every case inside its bit budget and an oversized one refused; `EXACT_COVERAGE` complete over kernels and over launch labels; and
 the expected values reachable in the kernels' own arithmetic (torch f32, the split16 hi / lo decomposition and the three-product sum)."""
 import os
 import sys
@@ -13,6 +13,8 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import ahc_ref  # noqa: E402
 import exact_cases as E  # noqa: E402
+import kernel_census  # noqa: E402
+import kernel_selection  # noqa: E402
 import spectral_ref  # noqa: E402
 
 
@@ -101,7 +103,7 @@ def test_chain_reference_equals_seven_torch_convs(kind, B, T, dil):
     assert np.array_equal(want[:, :128], r[:, :128]) and np.array_equal(want[:, 1024:], r[:, 1024:])
 
 
-@pytest.mark.parametrize("n", [4, 132, 260, 1030])
+@pytest.mark.parametrize("n", [4, 132, 260, 1030, 1412])
 def test_affinity_reference_equals_sklearn(n):
     from sklearn.metrics.pairwise import cosine_similarity
     X, K = E.affinity_rows(n)
@@ -264,45 +266,80 @@ def test_every_conv_case_states_its_budget():
 # every kernel the exact tests are held to, stated here a second time: a name dropped from the helper's table fails below
 CONV_KERNELS = ("conv_gemm_f32_kernel", "conv_gemm_f32_s64_kernel", "skinny_gemm_f32_kernel", "conv_gemm_f32_vh_kernel", "conv_gemm_f32_n64_kernel",
                 "conv_gemm_f32_t256_kernel", "conv_gemm_f32_packed_kernel", "seg_gemm_partial_f32_kernel", "seg_gemm_reduce_f32_kernel",
-                "conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel", "conv_gemm_split16_n128_kernel", "conv_gemm_f16_t256_kernel<split>",
-                "split16_pack_kernel", "res2net_chain_f16_kernel")
+                "conv_gemm_f16_kernel", "conv_gemm_f16_t256_kernel", "conv_gemm_split16_n128_kernel",
+                "split16_pack_kernel", "res2net_chain_f16_kernel", "chain_pack_kernel")
 FAMILIES = {
     "segment statistics": ("seg_mean_std_kernel", "se_scale_residual_kernel", "colstat_finish_kernel"),
     "pooling": ("asp_pool_kernel", "asp_pool_lds_kernel"),
     "fused pooling": ("asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel"),
-    "affinity": ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel"),
+    "affinity": ("affinity_sym_kernel", "l2norm_rows_kernel", "adjacent_cosine_kernel", "fill_f32_kernel"),
     "ahc": ("ahc_nearest_kernel", "ahc_nearest_finish_kernel", "ahc_merge_kernel"),
     "spectral": ("affinity_apply_kernel", "apply_finish_kernel", "affinity_degree_kernel"),
     "sim_argmax": ("sim_argmax_kernel",), "topk": ("topk_mean_std_kernel",), "viterbi": ("viterbi_kernel",),
 }
+# every LABEL they are held to: what the census (kernel_census.KERNEL_TESTS) sends to tests/test_gpu_exact.py
+EXACT_LABELS = {lb for lb, t in kernel_census.KERNEL_TESTS.items() if t and t[0] == "test_gpu_exact"}
 
 
 def _coverage_gaps(table):
+    """Kernels without a gather and a dense case, families without both kinds, and labels without any case."""
     cov = E.coverage(table)
-    kinds = lambda k: {table[n][0] for n in cov.get(k, ())}  # noqa: E731
+    by_kernel = {}
+    for lb, names in cov.items():
+        by_kernel.setdefault(E.kernel_of(lb), set()).update(names)
+    kinds = lambda k: {table[n][0] for n in by_kernel.get(k, ())}  # noqa: E731
     gaps = [k for k in CONV_KERNELS if kinds(k) != {"gather", "dense"}]
+    # the wide split form shares its kernel with the f16 operator: its labels need a gather and a dense case of their own
+    split = {table[n][0] for lb, names in cov.items() if lb.startswith("conv_gemm_f16_t256_kernel<split,") for n in names}
+    gaps += ["conv_gemm_f16_t256_kernel<split>"] if split != {"gather", "dense"} else []
     for fam, kernels in FAMILIES.items():
-        gaps += [k for k in kernels if not cov.get(k)]
+        gaps += [k for k in kernels if not by_kernel.get(k)]
         if set().union(*(kinds(k) for k in kernels)) != {"gather", "dense"}:
             gaps.append(fam)
-    return gaps
+    return gaps + sorted(lb for lb in EXACT_LABELS if not cov.get(lb) and lb not in gaps)
 
 
 def test_exact_coverage_names_a_gather_and_a_dense_case_for_every_kernel():
+    """... and, since the launch log, a case for every launch label the census sends to tests/test_gpu_exact.py."""
     assert E.EXACT_COVERAGE == E.coverage() and _coverage_gaps(E.CASE_TABLE) == []
-    assert set(E.EXACT_COVERAGE) == set(CONV_KERNELS) | {k for ks in FAMILIES.values() for k in ks} == set(E.ALL_KERNELS)
+    assert set(E.EXACT_COVERAGE) == EXACT_LABELS
+    assert {E.kernel_of(lb) for lb in EXACT_LABELS} == set(CONV_KERNELS) | {k for ks in FAMILIES.values() for k in ks} == set(E.ALL_KERNELS)
     assert set(E.CONV_CASE_NAMES) == {n for n in E.CASE_TABLE if E.CASE_TABLE[n][1] and n.split("-")[0] in tuple(E.SHAPES) or n[0] == "C"}
     # the check bites: without its packed cases, or without the one-hot chain, the table has a gap
-    assert _coverage_gaps({n: v for n, v in E.CASE_TABLE.items() if not n.startswith("P-")}) == ["conv_gemm_f32_packed_kernel"]
-    assert _coverage_gaps({n: v for n, v in E.CASE_TABLE.items() if n != "chain-onehot"}) == ["res2net_chain_f16_kernel"]
-    assert "viterbi_kernel" in _coverage_gaps({n: v for n, v in E.CASE_TABLE.items() if not n.startswith("viterbi")})
+    without = lambda pred: _coverage_gaps({n: v for n, v in E.CASE_TABLE.items() if not pred(n)})  # noqa: E731
+    assert without(lambda n: n.startswith("P-")) == ["conv_gemm_f32_packed_kernel"]
+    assert without(lambda n: n == "chain-onehot") == ["res2net_chain_f16_kernel", "chain_pack_kernel"]
+    assert "viterbi_kernel" in without(lambda n: n.startswith("viterbi"))
+    # ... and over labels: the 64-row ring kernel is reached by S5 alone, the lockstep walk of the wide split form by W1024 alone, the
+    # symmetric band walk of the 128x128 kernel by the affinity of 1412 rows alone
+    assert without(lambda n: n.startswith("S5-")) == ["conv_gemm_f32_s64_kernel<64>"]
+    assert without(lambda n: n.startswith("W1024-")) == ["conv_gemm_f16_t256_kernel<split,direct>/lockstep"]
+    assert without(lambda n: n[0] == "W" and n.endswith(("-rows", "-chan"))) == ["split16_pack_kernel", "conv_gemm_f16_t256_kernel<split>"]
+    assert "conv_gemm_f32_kernel<dma>/symmetric" in without(lambda n: n == "affinity-k16")
+
+
+def test_the_f32_label_table_is_the_dispatch_rule_restated():
+    """F32_LABELS (data, derived by hand beside each entry) against kernel_selection.f32_conv_label (conv1d_cl_f32_impl restated as
+    code): two statements of the same rules must agree on every shape and selection."""
+    for shape, by_sel in E.F32_LABELS.items():
+        assert list(by_sel) == kernel_selection.CONV_KERNELS
+        if shape[0] == "C":
+            (B, T), cout = (int(v) for v in shape[1:].split("-")[0].split("x")), int(shape.split("-")[1])
+        else:
+            B, T, cout = (E.SHAPES[shape][k] for k in ("B", "T", "cout"))
+        for sel, label in by_sel.items():
+            assert kernel_selection.f32_conv_label(sel, B * T, T, cout, colstat=shape[0] == "C") == label, (shape, sel)
+    # the pins fall through exactly where a side condition fails
+    assert kernel_selection.f32_conv_label("rows96", 70, 1, 40) == "conv_gemm_f32_kernel<dma>"                  # T == 1
+    assert kernel_selection.f32_conv_label("wide256", 262, 131, 1016) == "conv_gemm_f32_kernel<dma>"            # cout < 1024
+    assert kernel_selection.f32_conv_label("wide256", 704, 64, 1024, colstat=True) == "conv_gemm_f32_kernel<dma>"     # colstat at T < 128
 
 
 def test_every_kernel_of_the_table_exists_in_the_sources():
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "speech-diarization_amd", "csrc")
     text = "".join(open(os.path.join(root, f)).read() for f in sorted(os.listdir(root)) if f.endswith(".hip"))
     for k in E.ALL_KERNELS:
-        assert f" {k.split('<')[0]}(" in text, k
+        assert f" {k}(" in text, k
 
 
 # ------------------------------------------------------------------ 4. the expected values are reachable in the kernels' arithmetic

@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(HERE, "helpers"))
 import ahc_ref as A  # noqa: E402
 import guarded as G  # noqa: E402
 import spectral_ref as R  # noqa: E402
+from launch_log import expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -87,14 +88,16 @@ def test_merge_equals_the_numpy_statement_bit_for_bit(dev, n):
     for d, ld in ((192, 192), (190, 196), (7, 8)):
         S, count, inv = A.grid_case(n, d, ld, seed=77 * n + d)
         Sd, Sv, _, invd = _on(dev, S, d, count, inv)
-        nn, best = ops.ahc_nearest(Sv, invd)
+        with expect_launches(exactly=["ahc_nearest_kernel", "ahc_nearest_finish_kernel"]):
+            nn, best = ops.ahc_nearest(Sv, invd)
         nn_h, best_h = nn.cpu().numpy(), best.cpu().numpy()
         # thresholds: below every score (every reciprocal pair merges), the median best of the reciprocal pairs (some do), above
         # every score (none does)
         mid = float(np.median(best_h[nn_h[nn_h] == np.arange(n)]))
         for thr in (-1e30, mid, 1e30):
             Sd, Sv, countd, invd = _on(dev, S, d, count, inv)
-            target, merged = ops.ahc_merge(Sv, countd, invd, nn, best, thr)
+            with expect_launches(exactly=["ahc_merge_kernel"]):
+                target, merged = ops.ahc_merge(Sv, countd, invd, nn, best, thr)
             w_s, w_c, w_i, w_t, w_m = A.merge_f32(S[:, :d], count, inv, nn_h, best_h, thr)
             assert int(merged) == w_m and np.array_equal(target.cpu().numpy(), w_t)
             assert np.array_equal(Sd[:, :d].cpu().numpy().view(np.int32), w_s.view(np.int32))

@@ -13,7 +13,12 @@ Conv shapes (B, T, cin, cout, k, dil) and what they cross:
   P   spans 5, 7, 5, 9, 131 with S1's channels (sd_conv1d_cl_packed_f32)
   H1 / H2 / H2w / H2L / H3: S1 .. S3 for sd_conv1d_cl_f16 (which takes activations in groups of 8 channels and refuses S1's 36: 40
   there; H2w: cout 1100; H2L: cout 1024 = four column tiles of 256, which the lockstep walk of the 256x256 kernel needs: 1032 gives
-  five), N128 / W1032 / W256: the narrow and wide forms of sd_conv1d_cl_split16, C*: the column statistics.
+  five), N128 / W1032 / W256 / W1024: the narrow and wide forms of sd_conv1d_cl_split16, C*: the column statistics.
+  S5  8, 128, 32, 512, 3, 2    32 tiles of 128x128 but 128 of 64x64: the 64-row form of the 64x64 ring kernel, which S1 .. S3 never reach
+
+Every run is held to the launch label it must take (tests/helpers/launch_log.py; the labels per case, selection, storage type and
+tuning are stated in tests/helpers/exact_cases.py): the conv operators to exactly that label and no other kernel of the operator, the
+reductions and products to at least the labels named.
 
 Left out, each because the operation is inexact by construction (a reason the issue allows):
   * `asnorm_combine`: divides by std + 1e-6, no power of two.
@@ -36,6 +41,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hel
 import ahc_ref  # noqa: E402
 import exact_cases as E  # noqa: E402
 from kernel_selection import CONV_KERNELS, f16_tiles, restore_conv_kernel, select_conv_kernel  # noqa: E402,F401
+from launch_log import F16_CONV, F32_CONV, SPLIT_CONV, expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -146,6 +152,27 @@ def _launches(kind):
     return N.profile_read(kind)[1]
 
 
+def test_launch_log_counts_and_reports_a_short_buffer(dev):
+    """Two launches under two labels: the counts, the text of sd_launch_log_read, and a buffer shorter than the text -- the result
+    is the bytes the whole text needs (above cap), and the truncated copy is still terminated."""
+    from launch_log import launches
+    from speech_diarization_amd import ops
+    N, lib = _lib()
+    x = torch.ones(5, 8, device=dev)
+    with launches() as log:
+        ops.l2norm_rows(x)
+        ops.l2norm_rows(x)
+        ops.adjacent_cosine(x, eps=0.0)
+        text = b"adjacent_cosine_kernel\t1\nl2norm_rows_kernel\t2\n"
+        full = C.create_string_buffer(b"x" * 64, 64)
+        assert int(lib.sd_launch_log_read(full, 64)) == len(text) + 1 and full.value == text
+        small = C.create_string_buffer(b"xxxxxx", 6)
+        assert int(lib.sd_launch_log_read(small, 4)) == len(text) + 1 > 4
+        assert small.raw[:4] == b"adj\0" and small.raw[4:] == b"xx"          # cap - 1 bytes and the NUL; nothing past cap
+    assert log == {"adjacent_cosine_kernel": 1, "l2norm_rows_kernel": 2}
+    assert N.launch_log_enable(False) is False and N.launch_log_read() == log        # off again; the counts stay readable
+
+
 # ------------------------------------------------------------------ 1. convs
 
 F32_CASES = [n for n in E.CONV_CASE_NAMES if n[0] == "S"]
@@ -162,7 +189,8 @@ def test_conv1d_cl_f32_every_selection_gives_the_integers(dev, name):
         for sel in CONV_KERNELS:
             select_conv_kernel(sel)
             N.profile_enable(True)
-            got = run_conv(dev, c, "f32")
+            with expect_launches(exactly=[E.F32_LABELS[name.split("-")[0]][sel]], family=F32_CONV):
+                got = run_conv(dev, c, "f32")
             wide = _launches(N.SD_PROF_CONV_WIDE)
             N.profile_enable(False)
             check_conv(dev, c, got, F32, sel)
@@ -173,7 +201,8 @@ def test_conv1d_cl_f32_every_selection_gives_the_integers(dev, name):
         restore_conv_kernel()
     if name.startswith("S4"):
         N.profile_enable(True)
-        got = run_conv(dev, c, "seg")
+        with expect_launches(exactly=E.SEG_GEMM_LABELS, family=F32_CONV):
+            got = run_conv(dev, c, "seg")
         n_split = _launches(N.SD_PROF_SEG_SPLITK)
         N.profile_enable(False)
         check_conv(dev, c, got, F32, "seg_gemm")
@@ -185,7 +214,9 @@ def test_conv1d_cl_packed_f32_gives_the_integers(dev, name):
     """Spans 5, 7, 5, 9, 131: "P-rows" returns the source row of every tap, so a tap that crossed a span edge names the row it read;
     "P-dense" carries a bias per span."""
     c = E.conv_case(name)
-    check_conv(dev, c, run_conv(dev, c, "packed"), F32, "packed")
+    with expect_launches(exactly=[E.PACKED_LABEL], family=F32_CONV):
+        got = run_conv(dev, c, "packed")
+    check_conv(dev, c, got, F32, "packed")
 
 
 F16_CASES = [n for n in E.CONV_CASE_NAMES if n[0] == "H"]
@@ -201,12 +232,16 @@ def test_conv1d_cl_f16_gives_the_integers(dev, f16_tiles, name):
     c = E.conv_case(name)
     for xdt in (F16, F32):
         for ydt in (F16, F32):
-            check_conv(dev, c, run_conv(dev, c, "f16", xdt, ydt), ydt, f"{f16_tiles} x {xdt} y {ydt}")
+            with expect_launches(exactly=[E.f16_label(name, f16_tiles, xdt == F16, ydt == F16)], family=F16_CONV):
+                got = run_conv(dev, c, "f16", xdt, ydt)
+            check_conv(dev, c, got, ydt, f"{f16_tiles} x {xdt} y {ydt}")
     if c.cout >= 1024:
         N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, 0), "sd_set_tuning")
         try:
             for ydt in (F16, F32):
-                check_conv(dev, c, run_conv(dev, c, "f16", F16, ydt), ydt, f"{f16_tiles} lockstep y {ydt}")
+                with expect_launches(exactly=[E.f16_label(name, f16_tiles, True, ydt == F16, lockstep=True)], family=F16_CONV):
+                    got = run_conv(dev, c, "f16", F16, ydt)
+                check_conv(dev, c, got, ydt, f"{f16_tiles} lockstep y {ydt}")
         finally:
             N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, -1), "sd_set_tuning")
 
@@ -217,11 +252,24 @@ def test_conv1d_cl_split16_gives_the_integers(dev, name):
     bias): y as f32 and, where cout % 32 == 0, as SD_DT_SPLIT16 -- the bits sd_split16_pack_f32 makes of the integer answer.  The
     2049 s operands sit on the activations ("split_x": lo.hi carries weight) and on the weights ("split_w": hi.lo does, through the
     2^s of the weight pack and w_scale_inv)."""
+    N, lib = _lib()
     c = E.conv_case(name)
     op = "narrow" if name[0] == "N" else "wide"
-    check_conv(dev, c, run_conv(dev, c, op), F32, op)
+    with expect_launches(exactly=E.split_labels(name), family=SPLIT_CONV):
+        got = run_conv(dev, c, op)
+    check_conv(dev, c, got, F32, op)
     if c.cout % 32 == 0:
-        check_conv(dev, c, run_conv(dev, c, op, split_out=True), F32, op + " split out")
+        with expect_launches(exactly=E.split_labels(name, split_out=True), family=SPLIT_CONV):
+            got = run_conv(dev, c, op, split_out=True)
+        check_conv(dev, c, got, F32, op + " split out")
+    if c.cout == 1024:      # W1024: four column tiles; SD_TUNE_T256_LOCKSTEP_TILES = 0 makes the register epilogue walk in lockstep
+        N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, 0), "sd_set_tuning")
+        try:
+            with expect_launches(exactly=E.split_labels(name, lockstep=True), family=SPLIT_CONV):
+                got = run_conv(dev, c, op)
+        finally:
+            N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, -1), "sd_set_tuning")
+        check_conv(dev, c, got, F32, op + " lockstep")
 
 
 def _check_colstat(dev, c, got_y, cs, n_cs, ydt, what):
@@ -234,8 +282,9 @@ def _check_colstat(dev, c, got_y, cs, n_cs, ydt, what):
     _same(torch.where(live, got, torch.zeros_like(got)), want, what + " raw [sum | sumsq] units")
     mean, std = E.colstat_stats(c)
     y = got_y.contiguous()
-    st = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev), want_std=True)
-    only_mean = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev))
+    with expect_launches(exactly=["colstat_finish_kernel<f16>" if ydt == F16 else "colstat_finish_kernel<f32>"]):
+        st = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev), want_std=True)
+        only_mean = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev))
     torch.cuda.synchronize()
     _same(st[:, :c.cout], _dev(mean, F32, dev), what + " mean")
     _same(only_mean, _dev(mean, F32, dev), what + " mean (no std)")
@@ -258,7 +307,8 @@ def test_colstat_f32_gives_the_integer_sums(dev, name):
         for sel in CONV_KERNELS:
             select_conv_kernel(sel)
             cs = torch.full((n_cs + 4096,), NAN, device=dev)
-            got = run_conv(dev, c, "f32", colstat=cs)
+            with expect_launches(exactly=[E.F32_LABELS[name][sel]], family=F32_CONV):
+                got = run_conv(dev, c, "f32", colstat=cs)
             check_conv(dev, c, got, F32, sel)
             _check_colstat(dev, c, got["y"], cs, n_cs, F32, f"{name} {sel}")
     finally:
@@ -273,7 +323,8 @@ def test_colstat_f16_gives_the_integer_sums(dev, f16_tiles, name):
     n_cs = ops.colstat_floats(c.M, c.cout)
     for ydt in (F16, F32):
         cs = torch.full((n_cs + 4096,), NAN, device=dev)
-        got = run_conv(dev, c, "f16", F16, ydt, colstat=cs)
+        with expect_launches(exactly=[E.f16_label(name, f16_tiles, True, ydt == F16)], family=F16_CONV):
+            got = run_conv(dev, c, "f16", F16, ydt, colstat=cs)
         check_conv(dev, c, got, ydt, f16_tiles)
         _check_colstat(dev, c, got["y"], cs, n_cs, ydt, f"{name} f16 {f16_tiles} y {ydt}")
 
@@ -284,7 +335,8 @@ def test_colstat_split16_gives_the_integer_sums(dev):
     c = E.conv_case("C3x128-256")
     n_cs = ops.colstat_floats(c.M, c.cout)
     cs = torch.full((n_cs + 4096,), NAN, device=dev)
-    got = run_conv(dev, c, "wide", colstat=cs)
+    with expect_launches(exactly=E.split_labels("C3x128-256"), family=SPLIT_CONV):
+        got = run_conv(dev, c, "wide", colstat=cs)
     check_conv(dev, c, got, F32, "split16")
     _check_colstat(dev, c, got["y"], cs, n_cs, F32, "C3x128-256 split16")
 
@@ -301,20 +353,22 @@ def test_res2net_chain_f16_gives_the_integer_chain(dev, kind, B, T, dil):
     dl = [dict(w=ops.pack_weight(L["w"], dev, F16), bias=_dev(L["bias"], F32, dev), scale=_dev(L["scale"], F32, dev),
                shift=_dev(L["shift"], F32, dev), dil=dil) for L in layers]
     got = _dev(r, F16, dev)
-    ops.res2net_chain(got, T, dl)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=["chain_pack_kernel", f"res2net_chain_f16_kernel<{(T + 31) // 32}>"]):      # one instantiation per 32-row time tile
+        ops.res2net_chain(got, T, dl)
+        torch.cuda.synchronize()
     _same(got, _dev(want, F16, dev), f"chain {kind} T={T}")
     un = _dev(r, F16, dev)
     s0 = un[:, 128:256].clone()
     s1 = torch.empty_like(s0)
-    for j in range(1, n + 1):
-        src, dst = (s0, s1) if j & 1 else (s1, s0)
-        L = dl[j - 1]
-        kw = dict(cin=128, dil=dil, bias=L["bias"], act="relu", scale=L["scale"], shift=L["shift"], out=un, o_col0=128 * j)
-        if j < n:
-            kw.update(tee=dst, tee_lo=0, tee_hi=128, tee_add=un, ta_col0=128 * (j + 1))
-        ops.conv1d_cl(src, L["w"], T, **kw)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=["conv_gemm_f16_kernel<f16,f16>"], family=F16_CONV):
+        for j in range(1, n + 1):
+            src, dst = (s0, s1) if j & 1 else (s1, s0)
+            L = dl[j - 1]
+            kw = dict(cin=128, dil=dil, bias=L["bias"], act="relu", scale=L["scale"], shift=L["shift"], out=un, o_col0=128 * j)
+            if j < n:
+                kw.update(tee=dst, tee_lo=0, tee_hi=128, tee_add=un, ta_col0=128 * (j + 1))
+            ops.conv1d_cl(src, L["w"], T, **kw)
+        torch.cuda.synchronize()
     _same(un, got, f"unfused chain {kind} T={T}")
 
 
@@ -322,6 +376,11 @@ def test_res2net_chain_f16_gives_the_integer_chain(dev, kind, B, T, dil):
 
 def _dt(N, dtype):
     return N.SD_DT_F16 if dtype == F16 else N.SD_DT_F32
+
+
+def _t(dtype):
+    """The storage type as the launch labels write it."""
+    return "f16" if dtype == F16 else "f32"
 
 
 def _check_stats(got, mean, std, Cc, what, dev):
@@ -339,6 +398,8 @@ def _check_stats(got, mean, std, Cc, what, dev):
 
 # (B, T, C): 16 x 16 workgroups (grid.x * B < 256) and 64 x 4 ones; C = 100 is what the entry takes of "100 padded to a multiple of 4"
 REDUCE_SHAPES = [(5, 64, 100), (40, 64, 3072), (5, 128, 100)]
+# the workgroup shape sd_seg_mean_std takes: 16 x 16 while ceil(C / 256) B < 256 (the 64 x 4 grid would be small), 64 x 4 from there on (12 x 40)
+REDUCE_FORM = {(5, 64, 100): "16x16", (40, 64, 3072): "64x4", (5, 128, 100): "16x16"}
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])
@@ -349,9 +410,10 @@ def test_seg_mean_std_and_se_scale_residual_uniform(dev, dtype, B, T, C_):
     d = E.reduction_case(B, T, C_, f16=dtype == F16)
     xbuf, xv = _framed(d["x"].reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_ + 8), NAN, device=dev)
-    N.check(lib.sd_seg_mean_std_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, C_, 1, C.c_float(1e-12), out.data_ptr(), _stream()),
-            "sd_seg_mean_std_dt")
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},uniform,{REDUCE_FORM[B, T, C_]}>"]):
+        N.check(lib.sd_seg_mean_std_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, C_, 1, C.c_float(1e-12), out.data_ptr(), _stream()),
+                "sd_seg_mean_std_dt")
+        torch.cuda.synchronize()
     assert bool(torch.isnan(out.view(-1)[B * 2 * C_:]).all())
     _check_stats(out.view(-1)[:B * 2 * C_].view(B, 2 * C_), d["mean"], d["std"], C_, f"seg_mean_std {dtype}", dev)
     if dtype == F32:
@@ -361,9 +423,10 @@ def test_seg_mean_std_and_se_scale_residual_uniform(dev, dtype, B, T, C_):
         rbuf, _ = _framed(d["res"].reshape(B * T, C_), dtype, dev)
         ybuf = torch.full((B * T, C_ + 16), NAN, dtype=dtype, device=dev)
         x = xv.contiguous()
-        N.check(lib.sd_se_scale_residual_dt(x.data_ptr(), x.stride(0), _dev(d["gate"], F32, dev).data_ptr(), rbuf.data_ptr(), rbuf.stride(0), 8,
-                                            ybuf.data_ptr(), ybuf.stride(0), 8, B, T, C_, _dt(N, dtype), _stream()), "sd_se_scale_residual_dt")
-        torch.cuda.synchronize()
+        with expect_launches(exactly=[f"se_scale_residual_kernel<{_t(dtype)},uniform>"]):
+            N.check(lib.sd_se_scale_residual_dt(x.data_ptr(), x.stride(0), _dev(d["gate"], F32, dev).data_ptr(), rbuf.data_ptr(), rbuf.stride(0), 8,
+                                                ybuf.data_ptr(), ybuf.stride(0), 8, B, T, C_, _dt(N, dtype), _stream()), "sd_se_scale_residual_dt")
+            torch.cuda.synchronize()
         _untouched(ybuf, 8, 8 + C_, "se_scale_residual")
         _same(ybuf[:, 8:8 + C_], _dev(d["y"].reshape(B * T, C_), dtype, dev), f"se_scale_residual {dtype}")
 
@@ -378,9 +441,10 @@ def test_seg_mean_std_with_lens_ignores_the_padded_frames(dev, dtype, T, n):
     rel = torch.tensor([float(E.rel_len(T, m)) if m != T else 1.0 for m in d["n_live"]], device=dev)
     xbuf, _ = _framed(d["x_poisoned"].reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_), NAN, device=dev)
-    N.check(lib.sd_seg_mean_std_lens_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, rel.data_ptr(), C_, 1, C.c_float(1e-12),
-                                        out.data_ptr(), _stream()), "sd_seg_mean_std_lens_dt")
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},uniform,16x16>"]):      # B = 5, one channel block: the small grid
+        N.check(lib.sd_seg_mean_std_lens_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, rel.data_ptr(), C_, 1, C.c_float(1e-12),
+                                            out.data_ptr(), _stream()), "sd_seg_mean_std_lens_dt")
+        torch.cuda.synchronize()
     _check_stats(out, d["mean"], d["std"], C_, f"seg_mean_std lens T={T} n={n} {dtype}", dev)
 
 
@@ -395,21 +459,35 @@ def test_seg_mean_std_and_se_scale_residual_packed(dev, dtype):
     res = _dev(np.concatenate([p["res"][0] for p in parts]), dtype, dev)
     gate = _dev(np.concatenate([p["gate"] for p in parts]), F32, dev)
     fs = np.concatenate([[0], np.cumsum(spans)]).astype(np.int32)
-    got = ops.seg_mean_std_packed(x, fs)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},packed,64x4>"]):       # a packed map never takes 16 x 16
+        got = ops.seg_mean_std_packed(x, fs)
+        torch.cuda.synchronize()
     _check_stats(got, np.concatenate([p["mean"] for p in parts]), np.concatenate([p["std"] for p in parts]), C_, f"packed seg_mean_std {dtype}", dev)
-    y = ops.se_scale_residual_packed(x, gate, res, fs)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f"se_scale_residual_kernel<{_t(dtype)},packed>"]):
+        y = ops.se_scale_residual_packed(x, gate, res, fs)
+        torch.cuda.synchronize()
     _same(y, _dev(np.concatenate([p["y"][0] for p in parts]), dtype, dev), f"packed se_scale_residual {dtype}")
+
+
+POOL_FAMILY = {"asp_pool_kernel", "asp_pool_lds_kernel"}
+
+
+def _pool_label(dtype, T, C_):
+    """sd_asp_pool: the LDS-resident kernel when C is a multiple of its channel tile (32 f32 / 64 f16; 128 is, 100 is not) and a
+    segment's tile fits 64 KB (T <= 247: 201 does, 256 and 257 do not), the streaming kernel otherwise."""
+    staged = C_ == 128 and T in (57, 128, 131, 201)
+    assert staged or C_ == 100 or T in (256, 257), (T, C_)
+    return f"asp_pool_lds_kernel<{_t(dtype)}>" if staged else f"asp_pool_kernel<{_t(dtype)},uniform>"
 
 
 def _asp_pool(dev, logit, h, dtype, B, T, C_, rel=None):
     N, lib = _lib()
     lg, hd = _dev(logit.reshape(B * T, C_), dtype, dev), _dev(h.reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_), NAN, device=dev)
-    N.check(lib.sd_asp_pool_lens_dt(lg.data_ptr(), C_, hd.data_ptr(), _dt(N, dtype), C_, B, T, None if rel is None else rel.data_ptr(), C_,
-                                    C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_pool_lens_dt")
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[_pool_label(dtype, T, C_)], family={"asp_pool_kernel", "asp_pool_lds_kernel"}):
+        N.check(lib.sd_asp_pool_lens_dt(lg.data_ptr(), C_, hd.data_ptr(), _dt(N, dtype), C_, B, T, None if rel is None else rel.data_ptr(), C_,
+                                        C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_pool_lens_dt")
+        torch.cuda.synchronize()
     return out
 
 
@@ -470,9 +548,10 @@ def test_asp_pool_packed_one_hot(dev):
     parts = [E.pool_onehot_case(1, L, C_, seed=i) for i, L in enumerate(spans)]
     fs = np.concatenate([[0], np.cumsum(spans)]).astype(np.int32)
     for dtype in (F32, F16):
-        got = ops.asp_pool_packed(_dev(np.concatenate([p["logit"][0] for p in parts]), dtype, dev),
-                                  _dev(np.concatenate([p["h"][0] for p in parts]), dtype, dev), fs)
-        torch.cuda.synchronize()
+        with expect_launches(exactly=[f"asp_pool_kernel<{_t(dtype)},packed>"], family=POOL_FAMILY):     # a packed map always streams
+            got = ops.asp_pool_packed(_dev(np.concatenate([p["logit"][0] for p in parts]), dtype, dev),
+                                      _dev(np.concatenate([p["h"][0] for p in parts]), dtype, dev), fs)
+            torch.cuda.synchronize()
         mean = np.concatenate([p["mean"] for p in parts])
         _check_stats(got, mean, np.full_like(mean, E.SQRT_EPS), C_, f"asp_pool packed {dtype}", dev)
 
@@ -486,10 +565,20 @@ def _attend(dev, mode, a1, wc, h, B, T, C_, rel=None):
     hd = _dev(h.reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_), NAN, device=dev)
     dt = {"f32": N.SD_DT_F32, "f16": N.SD_DT_F16, "split16": N.SD_DT_SPLIT16}[mode]
-    N.check(lib.sd_asp_attend_pool_lens_dt(a1d.data_ptr(), wp.data_ptr(), hd.data_ptr(), dt, C_, B, T, None if rel is None else rel.data_ptr(),
-                                           C_, a1d.shape[1], C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_attend_pool_lens_dt")
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[_fused_label(mode, T)], family={"asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel"}):
+        N.check(lib.sd_asp_attend_pool_lens_dt(a1d.data_ptr(), wp.data_ptr(), hd.data_ptr(), dt, C_, B, T, None if rel is None else rel.data_ptr(),
+                                               C_, a1d.shape[1], C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_attend_pool_lens_dt")
+        torch.cuda.synchronize()
     return out
+
+
+def _fused_label(mode, T):
+    """The templates of sd_asp_attend_pool_scaled: f32 / split16 in 16-frame tiles x 4, 8, 13, 16 (T <= 64, 128, 208, 256), f16 in wave
+    slots of 64 frames x 1 .. 4."""
+    if mode == "f16":
+        return f"asp_attend_pool_f16_kernel<{(T + 63) // 64}>"
+    nt = next(n for n in (4, 8, 13, 16) if T <= 16 * n)
+    return f"asp_attend_pool_f32_kernel<{nt}{',split' if mode == 'split16' else ''}>"
 
 
 # T on both sides of every template of the fused kernels: f32 / split16 16-frame tiles x 4, 8, 13, 16; f16 wave slots x 1 .. 4
@@ -545,10 +634,28 @@ def test_fused_attention_pooling_with_lens_uniform_weights_over_the_live_frames(
 
 # ------------------------------------------------------------------ 3. products outside the network
 
-@pytest.mark.parametrize("n", [4, 132, 260, 1030])
+def _affinity_labels(n, split16, whole, aligned):
+    """ops.cosine_affinity: the triangle kernel for the whole matrix when N % 4 == 0 and the output takes 16-byte stores; otherwise
+    the conv operators -- f32: the symmetric launch (whole matrix) or a plain one (`rows=`), which the 32x32 split-K kernel takes
+    below 128 tiles of 128x128 (N <= 1408) and the band walk of the 128x128 kernel above; split16: a filled 2^-8 scale and the wide
+    split conv, whose epilogue is the staged one on these slices (N % 8 != 0 or an odd ldo)."""
+    helpers = ["l2norm_rows_kernel"] + (["split16_pack_kernel"] if split16 else [])
+    if whole and aligned and n % 4 == 0:
+        return helpers + ["affinity_sym_kernel<split16x3>" if split16 else "affinity_sym_kernel<exact f32>"]
+    if split16:
+        return helpers + ["fill_f32_kernel", "conv_gemm_f16_t256_kernel<split,staged>/grid"]
+    return helpers + ["conv_gemm_f32_kernel<dma>/symmetric" if whole and (-(-n // 128)) ** 2 >= 128 else "skinny_gemm_f32_kernel"]
+
+
+AFFINITY_FAMILY = F32_CONV | SPLIT_CONV | {"affinity_sym_kernel"}
+
+
+@pytest.mark.parametrize("n", [4, 132, 260, 1030, 1412])
 def test_cosine_affinity_is_k_over_16(dev, n):
     """f32 and split16 (its alpha is 2^-8 and its row scale 2^4: powers of two, so the whole-matrix path is exact and stays in), the whole
-    matrix and `rows=` blocks, a tight and a padded output (an odd ldo takes the paths without 16-byte stores)."""
+    matrix and `rows=` blocks, a tight and a padded output (an odd ldo takes the paths without 16-byte stores).  n = 1412 = 12 tiles
+    of 128: the smallest multiple of 4 whose unaligned whole matrix leaves the split-K kernel for the symmetric band walk of the
+    128x128 kernel (12 x 12 = 144 >= 128 tiles)."""
     from speech_diarization_amd import ops
     X, K = E.affinity_rows(n)
     xd = _dev(X, F32, dev)
@@ -556,16 +663,18 @@ def test_cosine_affinity_is_k_over_16(dev, n):
     for split16 in (False, True):
         for pad in (0, 4, 7):
             buf = torch.full((n, n + pad), NAN, device=dev)
-            ops.cosine_affinity(xd, out=buf[:, :n] if pad else buf, split16=split16)
-            torch.cuda.synchronize()
+            with expect_launches(exactly=_affinity_labels(n, split16, True, pad != 7), family=AFFINITY_FAMILY):
+                ops.cosine_affinity(xd, out=buf[:, :n] if pad else buf, split16=split16)
+                torch.cuda.synchronize()
             _untouched(buf, 0, n, "cosine_affinity")
             got = buf[:, :n]
             _same(got, want, f"cosine_affinity n={n} split16={split16} pad={pad}")
             assert torch.equal(got, got.T) and bool((got[2] == 0).all()) and bool((got[:, 2] == 0).all())
             assert got[0, 1] == 1 and got[0, n - 1] == 1 and got[n - 1, 1] == 1
         for lo, hi in ((0, min(n, 3)), (n // 3, n // 3 + min(n - n // 3, 130)), (n - 1, n)):
-            blk = ops.cosine_affinity(xd, rows=(lo, hi), split16=split16)
-            torch.cuda.synchronize()
+            with expect_launches(exactly=_affinity_labels(n, split16, False, True), family=AFFINITY_FAMILY):
+                blk = ops.cosine_affinity(xd, rows=(lo, hi), split16=split16)
+                torch.cuda.synchronize()
             _same(blk, want[lo:hi], f"cosine_affinity rows [{lo}, {hi}) n={n} split16={split16}")
 
 
@@ -577,8 +686,9 @@ def test_ahc_nearest_breaks_every_tie_towards_the_lowest_index(dev, n, d):
         S, count, inv, nn_want, best_want = E.ahc_case(n, d, ld)
         sums = _dev(S, F32, dev)[:, :d] if ld > d else _dev(S, F32, dev)
         inv_d = _dev(inv, F32, dev)
-        nn, best = ops.ahc_nearest(sums, inv_d)
-        torch.cuda.synchronize()
+        with expect_launches(exactly=["ahc_nearest_kernel", "ahc_nearest_finish_kernel"]):
+            nn, best = ops.ahc_nearest(sums, inv_d)
+            torch.cuda.synchronize()
         _same(nn, torch.from_numpy(nn_want).to(dev), f"ahc nn n={n} d={d} ld={ld}")
         _same(best, _dev(best_want, F32, dev), f"ahc best n={n} d={d} ld={ld}")
         nn_h = nn.cpu().numpy()
@@ -586,8 +696,9 @@ def test_ahc_nearest_breaks_every_tie_towards_the_lowest_index(dev, n, d):
         assert pairs.size >= 2 and torch.equal(best[pairs], best[nn_h[pairs]])         # reciprocal pairs carry equal bits
         cnt = _dev(count, F32, dev)
         s_ref, c_ref, i_ref, t_ref, m_ref = ahc_ref.merge_f32(np.nan_to_num(S[:, :d]), count, inv, nn_h, best.cpu().numpy(), 0.0)
-        target, n_merged = ops.ahc_merge(sums, cnt, inv_d, nn, best, 0.0)
-        torch.cuda.synchronize()
+        with expect_launches(exactly=["ahc_merge_kernel"]):
+            target, n_merged = ops.ahc_merge(sums, cnt, inv_d, nn, best, 0.0)
+            torch.cuda.synchronize()
         assert int(n_merged) == m_ref and m_ref >= 1
         _same(target, torch.from_numpy(t_ref).to(dev), "ahc merge target")
         _same(sums.contiguous(), torch.from_numpy(s_ref).to(dev), "ahc merged sums")
@@ -608,8 +719,13 @@ def test_affinity_apply_and_degree_are_exact(dev, n, b):
             for zero_diag in (False, True):
                 deg, Y = E.spectral_expected(K, scale, V, zero_diag)
                 what = f"n={n} b={b} ld={ld} onehot={onehot} zero_diag={zero_diag}"
-                _same(ops.affinity_degree(Kd, zero_diag), _dev(deg, F32, dev), "affinity_degree " + what)
-                _same(ops.affinity_apply(Kd, _dev(scale, F32, dev), _dev(V, F32, dev), zero_diag), _dev(Y, F32, dev), "affinity_apply " + what)
+                with expect_launches(exactly=["affinity_degree_kernel"]):
+                    got_deg = ops.affinity_degree(Kd, zero_diag)
+                # <blocks of 16 columns per thread, loads of K>: the aligned ld takes the 16-byte loads, the odd one the scalar loads
+                with expect_launches(exactly=[f"affinity_apply_kernel<{1 if b <= 16 else 2},{'vec' if ld % 4 == 0 else 'scalar'}>", "apply_finish_kernel"]):
+                    got_y = ops.affinity_apply(Kd, _dev(scale, F32, dev), _dev(V, F32, dev), zero_diag)
+                _same(got_deg, _dev(deg, F32, dev), "affinity_degree " + what)
+                _same(got_y, _dev(Y, F32, dev), "affinity_apply " + what)
 
 
 @pytest.mark.parametrize("K", [1, 5, 64])
@@ -618,8 +734,9 @@ def test_affinity_apply_and_degree_are_exact(dev, n, b):
 def test_sim_argmax_returns_the_first_maximum(dev, K, N_, D):
     from speech_diarization_amd import ops
     w, c, best_want, score_want = E.argmax_case(N_, K, D)
-    best, score = ops.sim_argmax(_dev(w, F32, dev), _dev(c, F32, dev))
-    torch.cuda.synchronize()
+    with expect_launches(exactly=["sim_argmax_kernel"]):
+        best, score = ops.sim_argmax(_dev(w, F32, dev), _dev(c, F32, dev))
+        torch.cuda.synchronize()
     _same(best, torch.from_numpy(best_want).to(dev), f"sim_argmax best K={K} N={N_} D={D}")
     _same(score, _dev(score_want, F32, dev), f"sim_argmax score K={K} N={N_} D={D}")
 
@@ -630,8 +747,12 @@ def test_adjacent_cosine_and_l2norm_rows_are_exact(dev):
     X, K = E.affinity_rows(133)
     live = np.delete(X, 2, axis=0)                        # without the zero row: 0 / 0 has no exact answer
     Kl = (live @ live.T) / 16.0
-    _same(ops.adjacent_cosine(_dev(live, F32, dev), eps=0.0), _dev(np.diagonal(Kl, 1).copy(), F32, dev), "adjacent_cosine")
-    _same(ops.l2norm_rows(_dev(live, F32, dev)), _dev(live / 4.0, F32, dev), "l2norm_rows")
+    with expect_launches(exactly=["adjacent_cosine_kernel"]):
+        adj = ops.adjacent_cosine(_dev(live, F32, dev), eps=0.0)
+    _same(adj, _dev(np.diagonal(Kl, 1).copy(), F32, dev), "adjacent_cosine")
+    with expect_launches(exactly=["l2norm_rows_kernel"]):
+        unit = ops.l2norm_rows(_dev(live, F32, dev))
+    _same(unit, _dev(live / 4.0, F32, dev), "l2norm_rows")
     _same(ops.l2norm_rows(_dev(X, F32, dev), sklearn_zero_guard=True), _dev(X / 4.0, F32, dev), "l2norm_rows (sklearn guard)")
 
 
@@ -644,8 +765,9 @@ def test_topk_mean_std_on_tied_integer_rows(dev, n, k):
     x, mean, std = E.topk_case(n, k)
     buf = torch.full((x.shape[0], n + 5), NAN, device=dev)
     buf[:, :n] = torch.from_numpy(x).to(dev)               # (float64 -> f32 keeps the sign of -0.0)
-    got = ops.topk_mean_std(buf[:, :n], k)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=["topk_mean_std_kernel"]):
+        got = ops.topk_mean_std(buf[:, :n], k)
+        torch.cuda.synchronize()
     ok_m, ok_s = torch.from_numpy(~np.isnan(mean)).to(dev), torch.from_numpy(~np.isnan(std)).to(dev)
     assert int(ok_m.sum()) >= (7 if min(k, n) & (min(k, n) - 1) == 0 else 1)
     _same(got[:, 0][ok_m], _dev(mean, F32, dev)[ok_m], f"topk mean n={n} k={k}")
@@ -661,6 +783,7 @@ def test_viterbi_ties_go_to_the_first_state(dev, K, T):
     s = E.viterbi_scores(T, K)
     for alpha in (0.9, 0.995, 0.01):
         want = diar_diag.viterbi_hmm(s, alpha)
-        got = ops.viterbi(torch.from_numpy(s).to(dev), alpha)
-        torch.cuda.synchronize()
+        with expect_launches(exactly=["viterbi_kernel"]):
+            got = ops.viterbi(torch.from_numpy(s).to(dev), alpha)
+            torch.cuda.synchronize()
         _same(got, torch.from_numpy(want).to(dev), f"viterbi K={K} T={T} alpha={alpha}")

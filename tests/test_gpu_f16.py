@@ -4,10 +4,16 @@ Operands are rounded to f16 (11-bit significand, the precision of the TF32 matmu
 enables on its CUDA path), sums are f32.  The bar is north_star's: embeddings within 1e-3 cosine of
 the reference CPU path and identical cluster assignments; the per-operator bound is the f16
 rounding of inputs and outputs (2^-11 relative)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from launch_log import expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -257,7 +263,12 @@ def test_ecapa_f16_full_geometry(dev, B, n):
     from speech_diarization_amd.engine import EmbeddingEngine
     sd = synth.make_ecapa_state_dict(1234)
     wav = synth.synthetic_segments(0, B, n)
-    got = EmbeddingEngine(sd, dev, precision="f16").embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
+    eng = EmbeddingEngine(sd, dev, precision="f16")
+    # the f16 forward: the features cast in front of the stem and, up to T = 212, the fused Res2Net chain behind its weight pack
+    T = 1 + n // 160
+    chain = ["chain_pack_kernel", f"res2net_chain_f16_kernel<{(T + 31) // 32}>"] if T <= 212 else []
+    with expect_launches(exactly=chain, at_least=["cast_f32_f16_kernel"], family={"res2net_chain_f16_kernel", "chain_pack_kernel"}):
+        got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
     ref = pipeline_ref.encode_batch_ref(sd, wav, torch.float64)
     cd = _cos_dist(got, ref)
     assert cd.max() < 1e-3, cd

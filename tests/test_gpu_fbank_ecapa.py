@@ -3,11 +3,23 @@
 The oracle is float64 (ground truth); the HIP path is exact f32.  north_star's bar is
 1e-3 cosine on embeddings; the bounds asserted here are much tighter and written per test.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from kernel_selection import PINNED_LABEL  # noqa: E402
+from launch_log import F32_CONV, expect_launches  # noqa: E402
+
 pytestmark = pytest.mark.gpu
+
+# the kernels of the three fbank routes (sd_fbank_utt16.hip: one launch per utterance; sd_fbank.hip: the folded DFT + finalize pass;
+# sd_fbank_generic.hip: other framings)
+FBANK = {"fbank_utt16_kernel", "fbank_logmel_kernel", "fbank_finalize_kernel", "fill_i32_kernel", "fbank_packed_tiles_kernel",
+         "fbg_pad_kernel", "fbg_dft_f64_kernel", "fbg_finalize_kernel"}
 
 
 def _cos_dist(a, b):
@@ -70,8 +82,10 @@ def test_fbank_both_kernels_at_their_length_switch(dev, kind, n):
     wav[1, n // 3: 2 * n // 3] *= 1e-3
     wav[2] *= 1e-2
     plan = FbankPlan(kind)
+    route = ["fbank_utt16_kernel<uniform>"] if n <= 32100 else ["fill_i32_kernel", "fbank_logmel_kernel<uniform>", "fbank_finalize_kernel<uniform>"]
     for mean_norm in (True, False):
-        got = fbank_device(torch.from_numpy(wav).to(dev), plan, mean_norm=mean_norm).cpu().numpy()
+        with expect_launches(exactly=route, family=FBANK):
+            got = fbank_device(torch.from_numpy(wav).to(dev), plan, mean_norm=mean_norm).cpu().numpy()
         ref = (fbank_ref.fbank_batch_ref(wav, mean_nor=mean_norm) if kind == "torchaudio" else fbank_ref.speechbrain_fbank_ref(wav, mean_norm=mean_norm))
         assert got.shape == ref.shape == (3, 1 + n // 160, 80)
         tol = 2e-4 if kind == "torchaudio" else 1e-3
@@ -167,7 +181,9 @@ def test_ecapa_small_geometry_matches_oracle(dev, conv_kernel, width, B, n):
     sd = synth.make_ecapa_state_dict(21, synth.EcapaConfig.small(width))
     wav = synth.synthetic_segments(3, B, n)
     eng = EmbeddingEngine(sd, dev, max_batch=4)         # max_batch < B: exercises micro-batching
-    got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
+    # (no layer of the small geometries has cout >= 1024: "wide256" has nothing to take there)
+    with expect_launches(at_least=[PINNED_LABEL[conv_kernel]] if conv_kernel in PINNED_LABEL and conv_kernel != "wide256" else []):
+        got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
     feats = fbank_ref.speechbrain_fbank_ref(wav)
     ref = ecapa_ref.EcapaRef(sd, torch.float64).forward_features(torch.from_numpy(feats)).numpy()
     assert got.shape == ref.shape == (B, 192)
@@ -187,7 +203,8 @@ def test_ecapa_full_geometry_matches_oracle(dev, conv_kernel, B, n):
     sd = synth.make_ecapa_state_dict(1234)
     wav = synth.synthetic_segments(0, B, n)
     eng = EmbeddingEngine(sd, dev)
-    got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
+    with expect_launches(at_least=[PINNED_LABEL[conv_kernel]] if conv_kernel in PINNED_LABEL else []):
+        got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
     ref = pipeline_ref.encode_batch_ref(sd, wav, torch.float64)
     cd = _cos_dist(got, ref)
     assert cd.max() < 1e-5, cd           # north_star bar: 1e-3
@@ -375,7 +392,8 @@ def test_fbank_batch_at_other_sample_rates(dev, sr, n, B):
     from speech_diarization_amd import speech_encode, synth
     wav = synth.synthetic_segments(11, B, n, std=0.2)
     for n_mels, mean_nor in ((80, True), (40, False)):
-        got = speech_encode.fbank_batch(wav, sr=sr, n_mels=n_mels, mean_nor=mean_nor)
+        with expect_launches(exactly=["fbg_pad_kernel", "fbg_dft_f64_kernel", "fbg_finalize_kernel"], family=FBANK):
+            got = speech_encode.fbank_batch(wav, sr=sr, n_mels=n_mels, mean_nor=mean_nor)
         ref = fbank_ref.fbank_batch_ref(wav, sr=sr, n_mels=n_mels, mean_nor=mean_nor)
         assert got.shape == ref.shape and got.dtype == np.float32
         assert np.abs(got - ref).max() < 5e-5, (sr, n_mels, np.abs(got - ref).max())

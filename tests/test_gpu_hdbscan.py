@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import guarded as G  # noqa: E402
 import hdbscan_ref as H  # noqa: E402
+from launch_log import expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,14 @@ def _bits(t):
 
 
 def _ks(n):
-    return sorted({k for k in (1, 2, 16, n - 1) if 1 <= k <= min(16, n - 1)})
+    """k on both edges of every instantiation of the core kernel (a running top-1, 2, 4, 8 or 16): 1, 2, 3-4, 5-8, 9-16."""
+    return sorted({k for k in (1, 2, 3, 4, 5, 8, 9, 16, n - 1) if 1 <= k <= min(16, n - 1)})
+
+
+def _core_labels(k):
+    """The instantiation of the core kernel and of its finish kernel for k neighbours: a running top-1, 2, 4, 8 or 16."""
+    kk = next(c for c in (1, 2, 4, 8, 16) if k <= c)
+    return [f"hdb_core_kernel<{kk}>", f"hdb_core_finish_kernel<{kk}>"]
 
 
 def _components(n):
@@ -57,7 +65,8 @@ def test_core_equals_the_numpy_kth_largest_on_integer_rows(dev, n):
         Sd = torch.from_numpy(S).to(dev)
         Gm = H.gram_f32(S[:, :d])
         for k in _ks(n):
-            got = ops.hdb_core(Sd[:, :d], k)
+            with expect_launches(exactly=_core_labels(k)):
+                got = ops.hdb_core(Sd[:, :d], k)
             want = torch.from_numpy(H.core_from_gram(Gm, k).astype(np.float32)).to(dev)
             assert torch.equal(got, want), f"core n={n} d={d} k={k}: {int((got != want).sum())} rows differ"
 
@@ -74,7 +83,8 @@ def test_outgoing_equals_the_numpy_statement_on_integer_rows(dev, n):
             cores["k2"] = H.core_from_gram(Gm, 2).astype(np.float32)
         for cname, core in cores.items():
             for name, comp in _components(n).items():
-                nn, best = ops.hdb_outgoing(Sd[:, :d], _f32(core, dev), _i32(comp, dev))
+                with expect_launches(exactly=["hdb_outgoing_kernel", "hdb_outgoing_finish_kernel"]):
+                    nn, best = ops.hdb_outgoing(Sd[:, :d], _f32(core, dev), _i32(comp, dev))
                 w_nn, w_best = H.outgoing_from_gram(Gm, core, comp)
                 assert torch.equal(nn, _i32(w_nn, dev)), f"nn n={n} d={d} core={cname} comp={name}: {int((nn.cpu() != torch.from_numpy(w_nn)).sum())} rows differ"
                 assert torch.equal(best, _f32(w_best, dev)), f"best n={n} d={d} core={cname} comp={name}"

@@ -13,7 +13,8 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-from kernel_selection import conv_kernel  # noqa: E402,F401  (the eight selections of the exact-f32 conv, shared fixture)
+from kernel_selection import conv_kernel, f32_conv_label  # noqa: E402,F401  (the eight selections of the exact-f32 conv, shared fixture)
+from launch_log import F32_CONV, expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,9 +50,11 @@ def test_conv1d_cl_matches_torch(dev, conv_kernel, B, T, cin, cout, k, dil):
     scale = torch.rand(cout, generator=g, dtype=torch.float64) + 0.5
     shift = torch.randn(cout, generator=g, dtype=torch.float64)
     ref = torch.relu(_ref_conv_cl(x, w, b, T, dil)) * scale + shift
-    got = ops.conv1d_cl(x.float().to(dev), ops.pack_weight(w.float(), dev), T, cin=cin, dil=dil, bias=b.float().to(dev),
-                        act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
-    torch.cuda.synchronize()
+    # the kernel this selection takes at this shape (a pin falls through where a side condition fails: T = 1, cout < 1024)
+    with expect_launches(exactly=[f32_conv_label(conv_kernel, B * T, T, cout)], family=F32_CONV):
+        got = ops.conv1d_cl(x.float().to(dev), ops.pack_weight(w.float(), dev), T, cin=cin, dil=dil, bias=b.float().to(dev),
+                            act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
+        torch.cuda.synchronize()
     err = (got.cpu().double() - ref).abs().max().item()
     assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
 
@@ -67,8 +70,9 @@ def test_conv1d_cl_slices_tee_and_per_segment_bias(dev, conv_kernel):
     out = torch.zeros(B * T, C, device=dev)
     tee = torch.zeros(B * T, hid, device=dev)
     # input = column slice [64, 96), output into column slice [32, 64), tee = y + xbig[:, 96:128]
-    ops.conv1d_cl(x_d, ops.pack_weight(w.float(), dev), T, cin=hid, dil=2, bias=segb.float().to(dev), bias_per_seg=True,
-                  act="relu", act2="tanh", a_col0=64, out=out, o_col0=32, tee=tee, tee_lo=0, tee_hi=hid, tee_add=x_d, ta_col0=96)
+    with expect_launches(exactly=[f32_conv_label(conv_kernel, B * T, T, hid, tee_add=True)], family=F32_CONV):
+        ops.conv1d_cl(x_d, ops.pack_weight(w.float(), dev), T, cin=hid, dil=2, bias=segb.float().to(dev), bias_per_seg=True,
+                      act="relu", act2="tanh", a_col0=64, out=out, o_col0=32, tee=tee, tee_lo=0, tee_hi=hid, tee_add=x_d, ta_col0=96)
     torch.cuda.synchronize()
     y = _ref_conv_cl(xbig[:, 64:96].contiguous(), w, None, T, 2) + segb.repeat_interleave(T, dim=0)
     y = torch.tanh(torch.relu(y))
@@ -327,7 +331,8 @@ def test_asnorm_scores_gpu_matches_reference_goldens_and_host(dev, golden_dir):
         cases = json.load(f)
     for case in cases:
         e, cents, cohort = (np.asarray(case[k], dtype=np.float64) for k in ("embs", "centers", "cohort"))
-        got = dd.asnorm_scores(e, cents, cohort, topk=20, device=dev)
+        with expect_launches(exactly=["asnorm_combine_kernel", "topk_mean_std_kernel"]):
+            got = dd.asnorm_scores(e, cents, cohort, topk=20, device=dev)
         assert got.dtype == np.float32
         assert np.abs(got - np.asarray(case["asnorm"])).max() < 2e-4          # reference output (float64) vs the f32 device path
     rng = np.random.default_rng(9)
@@ -344,7 +349,9 @@ def test_viterbi_gpu_path_equals_the_reference_path(dev, golden_dir):
         cases = json.load(f)
     for case in cases:
         scores = np.asarray(case["scores"], dtype=np.float32)
-        assert dd.viterbi_hmm(scores, alpha=0.9, device=dev).tolist() == case["viterbi"]
+        with expect_launches(exactly=["viterbi_kernel"]):
+            path = dd.viterbi_hmm(scores, alpha=0.9, device=dev)
+        assert path.tolist() == case["viterbi"]
         assert dd.viterbi_hmm(scores, device=dev).tolist() == case["viterbi_sticky"]
     rng = np.random.default_rng(4)
     for T, K, alpha in [(1, 3, 0.9), (2, 2, 0.995), (129, 8, 0.9), (1000, 16, 0.995), (36000, 8, 0.995), (300, 1, 0.9), (257, 64, 0.9)]:

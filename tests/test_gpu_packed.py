@@ -4,11 +4,16 @@ The packed fbank is bitwise `sd_fbank_f32` of each span alone on both fbank rout
 under every kernel selection of `sd_set_tuning`; `encode_spans` matches the float64 oracle of each span alone, the B = 1 call and, for equal
 lengths, the uniform forward; permutations, NaN samples and duplicates stay in their rows bit for bit."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from launch_log import F32_CONV, expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +60,10 @@ def test_fbank_packed_is_bitwise_the_span_alone(dev):
     starts += [0, total - 480000, starts[5] + 17, starts[3] + 4000]        # both ends of the signal; overlapping spans
     order = g.permutation(len(lengths))                                    # the routes interleaved in the pack
     starts, lengths = [starts[i] for i in order], [lengths[i] for i in order]
-    got = fbank_packed_device(sig, starts, lengths, plan)
+    # both routes of the pack: the spans of up to 201 frames on the one-launch kernel, the longer ones tiled for the folded-DFT kernel
+    with expect_launches(exactly=["fbank_utt16_kernel<packed>", "fbank_packed_tiles_kernel", "fill_i32_kernel", "fbank_logmel_kernel<packed>",
+                                  "fbank_finalize_kernel<packed>"]):
+        got = fbank_packed_device(sig, starts, lengths, plan)
     fs = span_frame_offsets(lengths)
     for s, (a, n) in enumerate(zip(starts, lengths)):
         alone = fbank_device(sig[a:a + n].contiguous()[None], plan)[0]
@@ -100,9 +108,10 @@ def test_packed_conv_matches_f64(dev, conv_kernel, k, dil, cin, cout):
     scale = torch.rand(cout, generator=g, dtype=torch.float64) + 0.5
     shift = torch.randn(cout, generator=g, dtype=torch.float64)
     ref = torch.relu(_ref_conv(x, w, b, T, dil)) * scale + shift
-    got = ops.conv1d_cl_packed(x.float().to(dev), ops.pack_weight(w.float(), dev), _offsets(T), cin=cin, dil=dil, bias=b.float().to(dev),
-                               act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
-    torch.cuda.synchronize()
+    with expect_launches(exactly=["conv_gemm_f32_packed_kernel"], family=F32_CONV):      # whatever the selection: no other kernel has the span map
+        got = ops.conv1d_cl_packed(x.float().to(dev), ops.pack_weight(w.float(), dev), _offsets(T), cin=cin, dil=dil, bias=b.float().to(dev),
+                                   act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
+        torch.cuda.synchronize()
     err = (got.cpu().double() - ref).abs().max().item()
     assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
 
@@ -142,9 +151,11 @@ def test_packed_reductions_match_f64(dev, conv_kernel):
     gate = torch.rand(len(T), Cc, generator=g, dtype=torch.float64)
     res = torch.randn(M, Cc, generator=g, dtype=torch.float64)
     xd = x.float().to(dev)
-    st = ops.seg_mean_std_packed(xd, fs).cpu().double()
-    pool = ops.asp_pool_packed(lg.float().to(dev), xd, fs).cpu().double()
-    y = ops.se_scale_residual_packed(xd, gate.float().to(dev), res.float().to(dev), fs).cpu().double()
+    with expect_launches(exactly=["seg_mean_std_kernel<f32,packed,64x4>", "asp_pool_kernel<f32,packed>", "se_scale_residual_kernel<f32,packed>"],
+                         family={"seg_mean_std_kernel", "asp_pool_kernel", "asp_pool_lds_kernel", "se_scale_residual_kernel"}):
+        st = ops.seg_mean_std_packed(xd, fs).cpu().double()
+        pool = ops.asp_pool_packed(lg.float().to(dev), xd, fs).cpu().double()
+        y = ops.se_scale_residual_packed(xd, gate.float().to(dev), res.float().to(dev), fs).cpu().double()
     for s in range(len(T)):
         xs, ls = x[fs[s]:fs[s + 1]], lg[fs[s]:fs[s + 1]]
         mu = xs.mean(0)

@@ -14,7 +14,8 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-from kernel_selection import conv_kernel, f16_tiles  # noqa: E402,F401  (the selections of the f32 and the f16 / split16 convs, shared fixtures)
+from kernel_selection import PINNED_LABEL, conv_kernel, f16_tiles, f32_conv_label  # noqa: E402,F401  (the selections of the f32 and the f16 / split16 convs, shared fixtures)
+from launch_log import F32_CONV, expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -80,9 +81,10 @@ def test_short_conv1d_cl_f32_matches_f64(dev, conv_kernel, B, T, cin, cout, k, d
     from speech_diarization_amd import ops
     x, w, b, scale, shift = _conv_case(B * 1000 + T + cout, B, T, cin, cout, k)
     ref = torch.relu(_ref_conv_cl(x, w, b, T, dil)) * scale + shift
-    got = ops.conv1d_cl(x.float().to(dev), ops.pack_weight(w.float(), dev), T, cin=cin, dil=dil, bias=b.float().to(dev),
-                        act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f32_conv_label(conv_kernel, B * T, T, cout)], family=F32_CONV):
+        got = ops.conv1d_cl(x.float().to(dev), ops.pack_weight(w.float(), dev), T, cin=cin, dil=dil, bias=b.float().to(dev),
+                            act="relu", scale=scale.float().to(dev), shift=shift.float().to(dev))
+        torch.cuda.synchronize()
     err = (got.cpu().double() - ref).abs().max().item()
     assert err < 2e-5 * max(1.0, ref.abs().max().item()), err
 
@@ -109,8 +111,9 @@ def test_short_conv1d_cl_f32_epilogues(dev, conv_kernel, B, T, cin, cout, dil):
               shift=shift.float().to(dev), act2="sigmoid", a_col0=64, tee=tee, tee_lo=0, tee_hi=hid)
     if with_add:
         kw.update(tee_add=add_d, ta_col0=0)
-    got = ops.conv1d_cl(xd, ops.pack_weight(w.float(), dev), T, **kw)
-    torch.cuda.synchronize()
+    with expect_launches(exactly=[f32_conv_label(conv_kernel, B * T, T, cout, tee_add=with_add)], family=F32_CONV):
+        got = ops.conv1d_cl(xd, ops.pack_weight(w.float(), dev), T, **kw)
+        torch.cuda.synchronize()
     y = _ref_conv_cl(xbig[:, 64:].contiguous(), w, None, T, dil) + segb.repeat_interleave(T, dim=0)
     y = torch.sigmoid(torch.relu(y) * scale + shift)
     assert (got.cpu().double() - y).abs().max() < 1e-5
@@ -480,7 +483,10 @@ def test_forward_along_the_length_axis_matches_f64(dev, precision, n):
 @pytest.mark.parametrize("T", [5, 6, 9, 17])
 def test_short_forward_under_every_f32_conv_selection(dev, conv_kernel, T):
     wav, ref = _case((T - 1) * 160)
-    got = _engine(dev, "f32").embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
+    eng = _engine(dev, "f32")
+    # (the full geometry has layers every pin applies to: time-axis convs for the row tiles, cout >= 1024 for the 256x256 kernel)
+    with expect_launches(at_least=[PINNED_LABEL[conv_kernel]] if conv_kernel in PINNED_LABEL else []):
+        got = eng.embed(torch.from_numpy(wav).to(dev)).cpu().numpy()
     _check(got, ref, "f32", f"T={T} {conv_kernel}")
 
 

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import guarded as G  # noqa: E402
 import spectral_ref as R  # noqa: E402
+from launch_log import expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 warnings.filterwarnings("ignore", message="Graph is not fully connected")
@@ -50,7 +51,8 @@ def test_degree_against_f64(dev, n):
         K, Kd = _dev_affinity(n, ld, dev)
         for zd in (False, True):
             ref = R.degree_ref(K, zd)
-            deg = ops.affinity_degree(Kd, zd).cpu().numpy().astype(np.float64)
+            with expect_launches(exactly=["affinity_degree_kernel"]):
+                deg = ops.affinity_degree(Kd, zd).cpu().numpy().astype(np.float64)
             rel = np.abs(deg - ref) / np.where(ref > 0, ref, 1.0)
             print(f"degree N={n} ld={ld} zero_diag={zd}: max rel err {rel.max():.3e}")
             assert np.all(np.isfinite(deg)) and rel.max() <= DEGREE_BAR
@@ -69,7 +71,9 @@ def test_apply_against_f64(dev, n):
             scale = R.grid_scale(K, zd)
             for b in R.GRID_B:
                 V = R.grid_block(n, b, seed=n + b)
-                Y = ops.affinity_apply(Kd, torch.from_numpy(scale).to(dev), torch.from_numpy(V).to(dev), zd).cpu().numpy()
+                # one or two blocks of 16 columns per thread; 16-byte loads of K when its rows are 16-byte aligned, scalar ones otherwise
+                with expect_launches(exactly=[f"affinity_apply_kernel<{1 if b <= 16 else 2},{'vec' if ld % 4 == 0 else 'scalar'}>", "apply_finish_kernel"]):
+                    Y = ops.affinity_apply(Kd, torch.from_numpy(scale).to(dev), torch.from_numpy(V).to(dev), zd).cpu().numpy()
                 r = R.apply_error_over_bound(Y, K, scale, V, zd)
                 print(f"apply N={n} ld={ld} zero_diag={zd} b={b}: error / bound {r:.4f}")
                 assert np.all(np.isfinite(Y))

@@ -12,6 +12,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 
 import wav_lens_ref as R  # noqa: E402
+from launch_log import expect_launches  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +52,8 @@ def test_device_rule_equals_host_rule(dev, T):
     rd = torch.from_numpy(rel).to(dev)
     nn_ = torch.empty(rel.size, dtype=torch.int32, device=dev)
     nm_ = torch.empty_like(nn_)
-    N.check(lib.sd_wav_lens_frames(rd.data_ptr(), rel.size, T, nn_.data_ptr(), nm_.data_ptr(), _stream()), "sd_wav_lens_frames")
+    with expect_launches(exactly=["wav_lens_frames_kernel"]):
+        N.check(lib.sd_wav_lens_frames(rd.data_ptr(), rel.size, T, nn_.data_ptr(), nm_.data_ptr(), _stream()), "sd_wav_lens_frames")
     hn, hm = length_frames(torch.from_numpy(rel), T)
     assert torch.equal(nn_.cpu().long(), hn) and torch.equal(nm_.cpu().long(), hm)
     N.check(lib.sd_wav_lens_frames(None, 5, T, nn_.data_ptr(), nm_.data_ptr(), _stream()), "sd_wav_lens_frames(NULL)")

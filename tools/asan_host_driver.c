@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "sd_hip.h"
+#include "sd_hip_trace.h"
 
 static int failures = 0;
 #define EXPECT(cond, what) do { if (!(cond)) { ++failures; fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, what); } } while (0)
@@ -51,6 +52,14 @@ int main(void) {
   EXPECT(sd_profile_read(-1, &ms, &n, &work) < 0 && sd_profile_read(SD_PROF_KINDS, &ms, &n, &work) < 0, "profile kind range");
   EXPECT(sd_profile_read(0, NULL, &n, &work) < 0 && sd_profile_read(0, &ms, NULL, &work) < 0 && sd_profile_read(0, &ms, &n, NULL) < 0, "profile nulls");
   EXPECT(sd_profile_enable(1) == SD_OK && sd_profile_read(SD_PROF_SEG_SPLITK, &ms, &n, &work) == SD_OK && n == 0 && sd_profile_enable(0) == SD_OK, "profile empty");
+  /* launch log (sd_hip_trace.h): the states, the empty text, a short and a missing buffer */
+  EXPECT(sd_trace_abi_version() == SD_TRACE_ABI_VERSION, "trace abi version");
+  EXPECT(sd_launch_log_enable(1) == 0 && sd_launch_log_enable(1) == 1 && sd_launch_log_enable(0) == 1 && sd_launch_log_enable(0) == 0, "launch log states");
+  {
+    char text[4] = {'x', 'x', 'x', 'x'};
+    EXPECT(sd_launch_log_read(NULL, 0) == 1 && sd_launch_log_read(text, 1) == 1 && text[0] == 0 && text[1] == 'x', "launch log empty text");
+    EXPECT(sd_launch_log_read(text, sizeof text) == 1 && text[0] == 0, "launch log read");
+  }
   for (int key = -2; key < 12; ++key) (void)sd_set_tuning(key, -1);
   for (int key = -2; key < 12; ++key) (void)sd_set_tuning(key, 0);
 
