@@ -161,7 +161,10 @@ int sd_fbank_lens_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, in
 #define SD_DT_F32 0
 #define SD_DT_F16 1
 #define SD_DT_SPLIT16 2 /* f32 VALUES carried as two f16 halves (hi = f16(v), lo = f16(v - hi)), interleaved per 32 values:
-                           value column c sits at halfs 64 (c / 32) + (c % 32) (hi) and + 32 (lo) of its row */
+                           value column c sits at halfs 64 (c / 32) + (c % 32) (hi) and + 32 (lo) of its row.
+                           hi + lo = v to 2^-22 relative while 2^-2 <= |v| <= 65504; below 2^-2 lo is an f16 subnormal (a
+                           multiple of 2^-24; kept, never flushed) and the error is 2^-25 ABSOLUTE per value; below 2^-14
+                           hi is subnormal too, and |v| < 2^-25 is carried as 0.  Larger |v| are clamped to 65504. */
 
 /* Channel-last 1-D convolution as an implicit GEMM on the matrix cores:
  *   y[m, n] = act2( affine( act( bias[n] + sum_{j<taps} sum_{c<cin}
@@ -214,9 +217,10 @@ size_t sd_seg_gemm_scratch_bytes(int M, int cin_pad, int cout);
 int sd_conv1d_cl_f16(const sd_conv_args* args, sd_stream_t stream);
 /* "f32-split16x3": the same operator at f32-level accuracy on the f16 matrix cores.  Every f32 operand value is split
  * v = hi + lo (two f16) and a product is hi.hi + hi.lo + lo.hi on v_mfma_f32_16x16x32_f16 with f32 accumulation: the
- * dropped lo.lo term and the representation error are 2^-22 relative per product (exact f32: 2^-24), three f16 MFMAs
- * instead of one f32 MFMA at 1/16 of their rate.  x: SD_DT_SPLIT16 rows [M][lda] (lda, a_col0, cin, cin_pad count VALUE
- * columns; lda, a_col0 and cin_pad multiples of 32; made by sd_split16_pack_f32); w: SD_DT_SPLIT16 [cout][taps][cin_pad],
+ * dropped lo.lo term and the representation error are 2^-22 relative per product (exact f32: 2^-24) WHILE THE
+ * ACTIVATIONS ARE AT LEAST 2^-2 IN MAGNITUDE (see "Domain" below), three f16 MFMAs instead of one f32 MFMA at 1/16 of
+ * their rate.  x: SD_DT_SPLIT16 rows [M][lda] (lda, a_col0, cin, cin_pad count VALUE columns; lda, a_col0 and cin_pad
+ * multiples of 32; made by sd_split16_pack_f32); w: SD_DT_SPLIT16 [cout][taps][cin_pad],
  * optionally pre-scaled by a power of two 2^s to keep the low halves of small weights out of the f16 subnormals (the
  * caller then passes bias * 2^s and scale * 2^-s: exact); y: f32.  256x256 tiles (the wide layers: cout >= 256 pays);
  * epilogue as sd_conv1d_cl_f16's 256x256 kernel (tee without tee_add; colstat needs T >= 128).
@@ -227,7 +231,16 @@ int sd_conv1d_cl_f16(const sd_conv_args* args, sd_stream_t stream);
  * y may be SD_DT_SPLIT16 instead of f32 (y_dtype; ldo, o_col0 in VALUE columns, ldo % 32 == 0, aligned slices, no colstat): the
  * result leaves as split halves, bit for bit what sd_split16_pack_f32 would make of the f32 result, for a consumer that is another
  * split conv (the narrow form, and the wide form through its LDS-staged epilogue); the tee copy stays f32.
- * Domain: |x| <= 65504 (larger values are clamped when packed / staged). */
+ * Domain and error model.  Upper edge: |x| <= 65504 (larger values are clamped when packed / staged).  Lower edge: the
+ * activations are split as they are (mul = 1), so a value below 2^-2 has an f16-subnormal low half and is carried to 2^-25
+ * ABSOLUTE, not 2^-22 relative (SD_DT_SPLIT16 above; the f16 MFMA, the pack kernel and the staging split all keep subnormals).
+ * With ALL of x at scale 2^e the error of y relative to its largest value is f32-level down to 2^-4, about 1.4e-6 at 2^-8 and
+ * 2e-5 at 2^-12 -- it grows by 2 per halving -- and the kernels track the numpy statement of this arithmetic to the last digit
+ * shown (profiles/split16_scale.json; tests/test_gpu_scale.py).  A network whose activations are O(1) with a minority of small
+ * channels, as every BatchNorm output is, stays at f32 level: the absolute error of the small channels is small against the
+ * sum.  The weights do not have this edge: their pack scales them by 2^s into [512, 1024).  A caller that knows the size of
+ * its rows can do the same on the x side with `mul` of sd_split16_pack_f32: the cosine affinity passes mul = 16 for its unit
+ * rows (entries of about 1 / sqrt(D) <= 2^-2 become >= 2^-2 where it matters) and folds 2^-8 into its alpha. */
 int sd_conv1d_cl_split16(const sd_conv_args* args, sd_stream_t stream);
 /* f32 [M][ldx] columns [col0, col0 + C), each multiplied by `mul` (a power of two: exact; 1 for activations) ->
  * SD_DT_SPLIT16 rows out [M][ldo] (ldo value columns, a multiple of 32, >= C rounded up to 32; the padding columns

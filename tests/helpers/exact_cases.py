@@ -9,6 +9,13 @@ Every generator checks its own bit budget on the host and raises `BudgetError` w
   * a mean divides by a power of two (or the quotient is an integer), quotient and square inside 24 bits.
 A GPU mismatch on one of these cases is therefore never rounding.
 
+Every generator also takes an exponent `e` (default 0: the case itself): the TWIN whose value operands -- x, bias and per-segment bias,
+BN shift / colstat pivot, tee_add, the h of the pooling kernels, both inputs of se_scale_residual, eps by 4^e; never a weight, a scale,
+a gate or a logit -- are times 2^e.  The operators are homogeneous of degree one in them, so the twin's answer is ldexp(answer, e), bit
+for bit, and the budget is checked again on the scaled values: every f32 normal and exact, every f16 exact, subnormals included
+(`F32_EXPONENTS`, `F16_EXPONENTS`; tests/test_gpu_scale.py, tests/test_scale_rules.py).  `split16_halves` / `split16_conv_sum` state the
+arithmetic of the split operators (include/sd_hip.h) in numpy, for the twins whose halves are f16 subnormals.
+
 `CASE_TABLE` names, for every case, the launch LABELS (include/sd_hip_trace.h: kernel, instantiation, walk) its runs reach on the
 MI355X, and `F32_LABELS` / `f16_label` / `split_labels` the one label of each single run (case x selection x storage types x tuning);
 tests/test_gpu_exact.py holds every run to its label through the launch log, so these are checked facts, not intentions.  Each entry
@@ -22,25 +29,90 @@ import numpy as np
 
 F32_LIMIT = 1 << 24
 F16_LIMIT = 2048
+F16_MAX = 65504.0
+# the exponents of the scaled twins: a case times 2^e must give the bits of ldexp(expected, e).  f32 storage: far from 1 both ways and
+# still normal (eps 4^e as well); f16 storage (x, y, chain state, pooled h; the activations of the split operators, which are carried
+# as f16 halves): +4 the top of the range, -14 astride the normal / subnormal edge, -20 mostly subnormal
+F32_EXPONENTS = (-40, -12, 12, 40)
+F16_EXPONENTS = (4, -14, -20)
 
 
 class BudgetError(ValueError):
     """A case left the range in which its arithmetic is exact."""
 
 
-def need_f32(name, *arrays):
-    """Every value is an f32 below 2^24 in magnitude that survives the round trip (so: no rounding when it is formed)."""
+def need_f32(name, *arrays, e=0):
+    """Every value is an f32 below 2^24 in magnitude that survives the round trip (so: no rounding when it is formed).  `e`: the arrays
+    are those of a twin scaled by 2^e (4^e: pass 2 e) -- divided by 2^e they meet the rule above, and as they stand every non-zero
+    value is a NORMAL f32 that survives the round trip: normal and exact, so inside a 24-bit span."""
     for a in arrays:
         a = np.asarray(a, dtype=np.float64)
-        if a.size and (np.abs(a).max() >= F32_LIMIT or not np.array_equal(a.astype(np.float32).astype(np.float64), a)):
-            raise BudgetError(f"{name}: a value leaves the exact f32 range (max |v| = {np.abs(a).max():g})")
+        if not a.size:
+            continue
+        base = np.ldexp(a, -e)
+        if np.abs(base).max() >= F32_LIMIT or not np.array_equal(base.astype(np.float32).astype(np.float64), base):
+            raise BudgetError(f"{name}: a value leaves the exact f32 range (max |v| = {np.abs(base).max():g} times 2^{e})")
+        with np.errstate(over="ignore"):
+            back = a.astype(np.float32).astype(np.float64)
+        if e and (not np.array_equal(back, a) or (np.abs(a[a != 0]) < 2.0 ** -126).any()):
+            raise BudgetError(f"{name}: a value times 2^{e} is no normal f32")
 
 
-def need_f16(name, *arrays):
+def need_f16(name, *arrays, e=0):
+    """Every value is an exact f16 of at most 2048; of a twin scaled by 2^e: an exact f16, subnormals included (a multiple of 2^-24),
+    of at most 65504, whose unscaled value meets the rule above."""
     for a in arrays:
         a = np.asarray(a, dtype=np.float64)
-        if a.size and (np.abs(a).max() > F16_LIMIT or not np.array_equal(a.astype(np.float16).astype(np.float64), a)):
-            raise BudgetError(f"{name}: a value is not an exact f16 of at most {F16_LIMIT} (max |v| = {np.abs(a).max():g})")
+        if not a.size:
+            continue
+        base = np.ldexp(a, -e)
+        if np.abs(base).max() > F16_LIMIT or not np.array_equal(base.astype(np.float16).astype(np.float64), base):
+            raise BudgetError(f"{name}: a value is not an exact f16 of at most {F16_LIMIT} (max |v| = {np.abs(base).max():g})")
+        with np.errstate(over="ignore"):
+            back = a.astype(np.float16).astype(np.float64)
+        if e and (np.abs(a).max() > F16_MAX or not np.array_equal(back, a)):
+            raise BudgetError(f"{name}: a value times 2^{e} is no exact f16 (max |v| = {np.abs(a).max():g})")
+
+
+def scaled(e, *arrays):
+    """ldexp(a, e) of every array (None stays None): exact in float64 for every exponent used here."""
+    out = tuple(None if a is None else np.ldexp(np.asarray(a, dtype=np.float64), e) for a in arrays)
+    return out[0] if len(out) == 1 else out
+
+
+def split16_halves(v, mul=1.0):
+    """The header's statement of SD_DT_SPLIT16 in numpy: hi = f16(clamp(v mul)), lo = f16(v mul - hi), round to nearest even, f16
+    subnormals kept (numpy's float16 has them).  -> (hi, lo) as float64."""
+    v = np.clip(np.asarray(v, dtype=np.float32) * np.float32(mul), -F16_MAX, F16_MAX).astype(np.float32)
+    hi = v.astype(np.float16)
+    lo = (v - hi.astype(np.float32)).astype(np.float16)
+    return hi.astype(np.float64), lo.astype(np.float64)
+
+
+def split16_rows(v):
+    """[M, C] f32 values -> the SD_DT_SPLIT16 rows sd_split16_pack_f32 must make of them: f16 [M, 2 C32], per 32 values
+    [hi x 32 | lo x 32], the padding values zero."""
+    M, Cc = np.shape(v)
+    cp = -(-Cc // 32) * 32
+    hi, lo = np.zeros((M, cp), np.float16), np.zeros((M, cp), np.float16)
+    h, lw = split16_halves(v)
+    hi[:, :Cc], lo[:, :Cc] = h, lw
+    return np.concatenate([hi.reshape(M, cp // 32, 1, 32), lo.reshape(M, cp // 32, 1, 32)], axis=2).reshape(M, 2 * cp)
+
+
+def split16_weight_shift(w):
+    """The s of the weight pack: max |w| 2^s in [512, 1024) (engine.split16_exponent restated)."""
+    top = float(np.abs(w).max())
+    return 0 if top == 0 else 9 - int(np.floor(np.log2(top)))
+
+
+def split16_conv_sum(x, w, src):
+    """The three-product sum of sd_conv1d_cl_split16 in float64: x and w 2^s split into f16 halves, hi.hi + hi.lo + lo.hi over every
+    tap and channel, times 2^-s; the lo.lo term dropped, as the kernel drops it."""
+    s = split16_weight_shift(w)
+    xh, xl = split16_halves(x)
+    wh, wl = split16_halves(np.ldexp(np.asarray(w, dtype=np.float64), s))
+    return np.ldexp(conv_sum(xh, wh, src) + conv_sum(xh, wl, src) + conv_sum(xl, wh, src), -s)
 
 
 def need_mean(name, total, divisor):
@@ -320,6 +392,7 @@ class ConvCase:
     kernels: tuple = ()
     bound: float = 0.0          # sum |x| |w| of the largest output: no partial sum, in any order, passes it
     f16: bool = False           # the case is also run with f16 storage
+    e: int = 0                  # a twin: the value operands (x, bias, shift, tee_add; "w:-q": w instead of x) times 2^e
 
     @property
     def M(self):
@@ -338,13 +411,9 @@ class ConvCase:
         return np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int32)
 
 
-def finish_conv(c: ConvCase) -> ConvCase:
-    """Fill in the expected outputs and check the budget for every storage type the case is run with."""
-    src = source_rows(c.lengths, c.k, c.dil)
-    acc = conv_sum(c.x, c.w, src)
-    c.bound = float(conv_sum(np.abs(c.x), np.abs(c.w), src).max())
-    if c.bound >= F32_LIMIT:
-        raise BudgetError(f"{c.name}: sum |x| |w| = {c.bound:g} reaches 2^24")
+def conv_epilogue(c: ConvCase, acc):
+    """bias, relu, scale, shift and the tee of case `c` on the accumulators `acc`, in float64: sets c.y / c.tee, returns every
+    intermediate an f32 epilogue holds."""
     r = acc
     steps = [acc]
     if c.bias is not None:
@@ -362,6 +431,41 @@ def finish_conv(c: ConvCase) -> ConvCase:
     if c.tee_hi:
         c.tee = r[:, c.tee_lo:c.tee_hi] + (c.tee_add if c.tee_add is not None else 0.0)
         steps.append(c.tee)
+    return steps
+
+
+def conv_twin(c: ConvCase, e, storage, side="x") -> ConvCase:
+    """Case `c` with its value operands times 2^e: x (side "w": the weights instead, for the split operator, whose host pack absorbs
+    the factor into its 2^s), bias, shift and tee_add; scale stays.  Every operation of the operator is homogeneous of degree one in
+    them, so the expected y and tee are ldexp(., e) -- unless the split operator cannot carry x 2^e in two f16 halves (2049 2^-26),
+    where they are what `split16_conv_sum` makes of the halves.  `storage`: "f32", "f16" (x, y, tee, tee_add stored as f16) or
+    "split" (x carried as f16 halves, y f32).  The budget is checked on the scaled values."""
+    t = ConvCase(**{**c.__dict__, "e": e, "name": f"{c.name}@{side if side != 'x' else ''}2^{e}"})
+    if side == "x":
+        t.x = scaled(e, c.x)
+    else:
+        t.w = scaled(e, c.w)
+    t.bias, t.shift, t.tee_add = scaled(e, c.bias, c.shift, c.tee_add)
+    src = source_rows(c.lengths, c.k, c.dil)
+    if np.ldexp(c.bound, e) >= 2.0 ** 127:
+        raise BudgetError(f"{t.name}: sum |x| |w| reaches 2^127")
+    acc = split16_conv_sum(t.x, t.w, src) if storage == "split" else conv_sum(t.x, t.w, src)
+    steps = conv_epilogue(t, acc)
+    need_f32(t.name, *steps, *([t.tee_add] if t.tee_add is not None else []), e=e)
+    need_f32(t.name, t.x if side == "x" else t.w, e=e)
+    if storage == "f16":
+        need_f16(t.name, t.x, t.y, *([t.tee] if t.tee_hi else []), *([t.tee_add] if t.tee_add is not None else []), e=e)
+    return t
+
+
+def finish_conv(c: ConvCase) -> ConvCase:
+    """Fill in the expected outputs and check the budget for every storage type the case is run with."""
+    src = source_rows(c.lengths, c.k, c.dil)
+    acc = conv_sum(c.x, c.w, src)
+    c.bound = float(conv_sum(np.abs(c.x), np.abs(c.w), src).max())
+    if c.bound >= F32_LIMIT:
+        raise BudgetError(f"{c.name}: sum |x| |w| = {c.bound:g} reaches 2^24")
+    steps = conv_epilogue(c, acc)
     need_f32(c.name, *steps, c.x, c.w)
     if c.f16:
         need_f16(c.name, c.x, c.w, c.y, *([c.tee] if c.tee_hi else []), *([c.tee_add] if c.tee_add is not None else []))
@@ -470,11 +574,20 @@ def colstat_units(c: ConvCase, unit=128):
             if sel.size:
                 out[u, p] = v[sel].sum(0)
                 out[u, 3 + p] = (v[sel] ** 2).sum(0)
-    need_f32(c.name + " (colstat)", np.nan_to_num(out))
+    need_f32(c.name + " (colstat)", np.nan_to_num(out[:, :3]), e=c.e)
+    need_f32(c.name + " (colstat)", np.nan_to_num(out[:, 3:]), e=2 * c.e)
     return out
 
 
 SQRT_EPS = float(np.sqrt(np.float32(1e-12)))      # what sqrtf(fmaxf(0, 1e-12f)) returns: 1e-6 to f32 rounding
+
+
+def twin_eps(e=0):
+    """f32(1e-12) 4^e: the variance clamp of a twin at 2^e, a normal f32 for every exponent used here."""
+    eps = float(np.float32(1e-12)) * 4.0 ** e
+    if not 2.0 ** -126 <= eps < 2.0 ** 128 or float(np.float32(eps)) != eps:
+        raise BudgetError(f"eps 4^{e} = {eps:g} is no normal f32")
+    return eps
 
 
 def exact_std(var):
@@ -485,13 +598,29 @@ def exact_std(var):
 
 
 def colstat_stats(c: ConvCase):
-    yr = c.y.reshape(c.B, c.T, c.cout)
-    return yr.mean(1), exact_std(yr.var(1))
+    """(mean, std) per segment; of a twin: ldexp of the unscaled statistics (sqrt(eps 4^e) = sqrt(eps) 2^e where the variance is 0)."""
+    yr = np.ldexp(c.y, -c.e).reshape(c.B, c.T, c.cout)
+    return scaled(c.e, yr.mean(1), exact_std(yr.var(1)))
+
+
+def default_storage(name):
+    """How the operator a case is built for carries its activations: H* as f16, N* / W* as two f16 halves, the others as f32."""
+    return {"H": "f16", "N": "split", "W": "split"}.get(name[0], "f32")
 
 
 @functools.lru_cache(maxsize=None)
-def conv_case(name):
-    """Every conv case of CASE_TABLE by name (built once per process, never modified)."""
+def _conv_twin(name, e, storage, side):
+    return conv_twin(_conv_case(name), e, storage, side)
+
+
+def conv_case(name, e=0, storage=None, side="x"):
+    """Every conv case of CASE_TABLE by name (built once per process, never modified).  `e` != 0: its twin at 2^e (`conv_twin`) for the
+    storage given (default: that of the operator the case is named for)."""
+    return _conv_twin(name, e, storage or default_storage(name), side) if e else _conv_case(name)
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_case(name):
     shape, _, what = name.partition("-")
     if shape[0] == "C":
         bt, cout = name[1:].split("-")
@@ -517,10 +646,11 @@ CHAIN_SHAPES = ((3, 61, 3), (2, 212, 4), (2, 32, 2), (2, 65, 3), (2, 97, 2), (2,
 
 
 @functools.lru_cache(maxsize=None)
-def chain_case(kind, B, T, dil, n=7, ld=1024 + 64):
+def chain_case(kind, B, T, dil, n=7, ld=1024 + 64, e=0):
     """"onehot": one-hot weights [128][128][3], so the chain is a composition of gathers and adds; "sums": four +-1 weights per output
     channel (taps and channels mixed), so every output is a signed sum.  Integer bias / shift, scale 1 (layer 3: 2), relu.
-    -> (r [B T, ld] small integers, layers, the expected r after the chain); every chain state y_j and c_{j+1} + y_j an exact f16."""
+    -> (r [B T, ld] small integers, layers, the expected r after the chain); every chain state y_j and c_{j+1} + y_j an exact f16.
+    `e`: the twin with r, every bias and every shift times 2^e, whose chain is ldexp(., e) state by state."""
     name = "chain-" + kind
     register(name, "gather" if kind == "onehot" else "dense")
     rng = np.random.default_rng(T + dil + (kind == "sums"))
@@ -528,6 +658,7 @@ def chain_case(kind, B, T, dil, n=7, ld=1024 + 64):
     r = rng.integers(0, 3, (M, ld)).astype(np.float64)
     src = source_rows((T,) * B, 3, dil)
     layers = []
+    states = []
     out = r.copy()
     u = r[:, 128:256].copy()
     for j in range(1, n + 1):
@@ -543,10 +674,16 @@ def chain_case(kind, B, T, dil, n=7, ld=1024 + 64):
         y = np.maximum(acc + L["bias"][None, :], 0.0) * L["scale"][None, :] + L["shift"][None, :]
         need_f32(name, conv_sum(np.abs(u), np.abs(w), src))
         need_f16(name, y, u)
+        states += [y, u]
         out[:, 128 * j:128 * j + 128] = y
         if j < n:
             u = y + r[:, 128 * (j + 1):128 * (j + 2)]
         layers.append(L)
+    if e:
+        need_f16(name, *scaled(e, r, *states), e=e)
+        need_f32(name, *scaled(e, *states), e=e)
+        r, out = scaled(e, r, out)
+        layers = [dict(L, bias=scaled(e, L["bias"]), shift=scaled(e, L["shift"])) for L in layers]
     return r, layers, out
 
 
@@ -561,11 +698,28 @@ def rel_len(T, n):
     return np.float32(n / T)
 
 
-def reduction_case(B, T, C, lens=None, f16=False, seed=0):
+def reduction_case(B, T, C, lens=None, f16=False, seed=0, e=0):
+    """The case below (built once per process, never modified), or its twin at 2^e: x and res times 2^e (the gate and the poison stay)
+    and `eps` = f32(1e-12) 4^e; mean, std and y are ldexp(., e), and the std of a constant column sqrt(eps) 2^e."""
+    d = _reduction_case(B, T, C, lens, f16, seed)
+    if not e:
+        return d
+    name = "reduce-poison" if lens else "reduce-int"
+    x, res, mean, std, y = scaled(e, d["x"], d["res"], d["mean"], d["std"], d["y"])
+    need_f32(name, x, res, mean, y, e=e)
+    need_f32(name, scaled(2 * e, d["sq"]), e=2 * e)
+    if f16:
+        need_f16(name, x, res, y, e=e)
+    xp = np.where(np.arange(T)[None, :, None] < d["n_live"][:, None, None], x, d["x_poisoned"])
+    return dict(d, x=x, x_poisoned=xp, res=res, mean=mean, std=std, y=y, eps=twin_eps(e))
+
+
+@functools.lru_cache(maxsize=None)
+def _reduction_case(B, T, C, lens, f16, seed):
     """Integer x [B, T, C] in {-3 .. 3} (columns 0 mod 5: 0 / 2 alternating, variance 1 over an even number of frames; 1 mod 5: constant),
     gate in {0.25, 0.5, 1}, integer res.  `lens`: the live frames of each segment in turn; the frames past them hold POISON (f16: the
     largest f16) in `x_poisoned`.  -> dict with the expected mean / std (NaN where the variance is no perfect square) over the live
-    frames and y = x gate + res over all rows."""
+    frames and y = x gate + res over all rows (`sq`: the sums of squared deviations, for the twins' budget)."""
     name = "reduce-poison" if lens else "reduce-int"
     register(name)
     rng = np.random.default_rng(seed + C + T)
@@ -589,7 +743,8 @@ def reduction_case(B, T, C, lens=None, f16=False, seed=0):
     xp = x.copy()
     for b in range(B):
         xp[b, n_live[b]:] = POISON_F16 if f16 else POISON
-    return dict(x=x, x_poisoned=xp, gate=gate, res=res, mean=mean, std=std, y=y, n_live=n_live)
+    sq = np.stack([((x[b, :n_live[b]] - mean[b]) ** 2).sum(0) for b in range(B)])
+    return dict(x=x, x_poisoned=xp, gate=gate, res=res, mean=mean, std=std, y=y, n_live=n_live, eps=twin_eps(0), sq=sq)
 
 
 def pool_frames(T):
@@ -601,7 +756,7 @@ def pool_frames(T):
 
 
 @functools.lru_cache(maxsize=None)
-def pool_onehot_case(B, T, C, lens=None, fused=False, seed=0):
+def pool_onehot_case(B, T, C, lens=None, fused=False, seed=0, e=0, f16=False):
     """logit 0 at frame t*(b, c) and -200 elsewhere (exp underflows to exactly 0; -200 is an f16 value), integer h: the mean is
     h[b, t*, c] and the variance 0.  t* walks pool_frames() below the live frames.  Padded frames hold a +200 logit and POISON in h
     (`h_f16`: the largest f16)."""
@@ -623,11 +778,15 @@ def pool_onehot_case(B, T, C, lens=None, fused=False, seed=0):
     for b in range(B):
         hp[b, n_live[b]:] = POISON
         hp16[b, n_live[b]:] = POISON_F16
-    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, tstar=tstar, n_live=n_live)
+    if e:                                                   # the twin: h times 2^e (`f16`: stored as f16), the logits and the poison as they are
+        (need_f16 if f16 else need_f32)(name, scaled(e, h), e=e)
+        live = np.arange(T)[None, :, None] < n_live[:, None, None]
+        hp, hp16, mean = np.where(live, scaled(e, h), hp), np.where(live, scaled(e, h), hp16), scaled(e, mean)
+    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, tstar=tstar, n_live=n_live, eps=twin_eps(e), sqrt_eps=np.ldexp(SQRT_EPS, e))
 
 
 @functools.lru_cache(maxsize=None)
-def pool_uniform_case(B, T, C, level=1.0, fused=False, n=None, seed=0):
+def pool_uniform_case(B, T, C, level=1.0, fused=False, n=None, seed=0, e=0, f16=False):
     """All logits of a channel equal (`level` times a per-channel integer) over the n live frames (all T when n is None), n a power of
     two, integer h: the exact mean, and the exact std on the columns built for it (0 / 2 alternating: variance 1; constant: sqrt(eps)).
     Padded frames hold a +200 logit and POISON in h (`h_f16`: the largest f16)."""
@@ -649,7 +808,14 @@ def pool_uniform_case(B, T, C, level=1.0, fused=False, n=None, seed=0):
     need_f16(name, h, logit)
     hp, hp16 = h.copy(), h.copy()
     hp[:, n:], hp16[:, n:] = POISON, POISON_F16
-    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, std=exact_std(live.var(1)), n_live=np.full(B, n))
+    std = exact_std(live.var(1))
+    if e:
+        (need_f16 if f16 else need_f32)(name, scaled(e, h), e=e)
+        need_f32(name, scaled(e, mean), e=e)
+        need_f32(name, scaled(2 * e, ((live - mean[:, None]) ** 2).sum(1)), e=2 * e)
+        hp[:, :n] = hp16[:, :n] = scaled(e, live)
+        mean, std = scaled(e, mean, std)
+    return dict(logit=logit, h=hp, h_f16=hp16, mean=mean, std=std, n_live=np.full(B, n), eps=twin_eps(e))
 
 
 def attend_factors(logit, att=128):
@@ -667,9 +833,52 @@ def attend_factors(logit, att=128):
     return a1.reshape(B, T, att), wc
 
 
+FUSED_WS = 256.0        # the power of two the public entry of the fused pooling multiplies its weights with before it splits them
+
+
+def fused_split_logits(a1, wc, flush=False):
+    """The logits of the fused pooling's split product in numpy: a1 and wc 2^8 split into f16 halves, hi.hi + hi.lo + lo.hi in float64,
+    times 2^-8.  `flush`: what an implementation that dropped f16 subnormals would compute instead."""
+    ah, al = split16_halves(a1)
+    wh, wl = split16_halves(wc, FUSED_WS)
+    if flush:
+        ah, al, wh, wl = (np.where(np.abs(v) < 2.0 ** -14, 0.0, v) for v in (ah, al, wh, wl))
+    return (ah @ wh.T + ah @ wl.T + al @ wh.T) / FUSED_WS
+
+
+@functools.lru_cache(maxsize=None)
+def fused_split_case(B, T, C, n, side, att=128):
+    """The fused pooling's split logits decided by an f16-subnormal low half.  h, mean and std are those of `pool_uniform_case` (n live
+    frames, logits 0).  The even live frames get their logit 0 from a zero weight; the odd ones from a sum that cancels only if the
+    subnormal takes part:
+      side "a1": a1 = (2^-3 + 2^-16, 1) against wc = (1, -(2^-3 + 2^-16)): the halves of 2^-3 + 2^-16 are (2^-3, 2^-16), the low one an
+                 f16 subnormal; those of wc 2^8 are (256, 0) and (-32, -2^-8): 32 + 2^-8 - 32 - 2^-8 = 0
+      side "wc": a1 = (2^10, 1) against wc = (2049 2^-28, -(2 + 2^-10) 2^-8): the halves of 2049 2^-20 are (2^-9, 2^-20), those of
+                 -(2 + 2^-10) are (-2, -2^-10): 2 + 2^-10 - 2 - 2^-10 = 0
+    Every partial sum is a small multiple of a power of two, so the accumulators are exactly 0 in any order, the softmax is uniform
+    and the answer is the exact mean and std.  Without the subnormal the odd frames sit 2^-16 (2^-18) below the even ones, their
+    weights 1.5e-5 (3.8e-6) lower, and the mean of a column that alternates 0 / 2 moves by tens of ulps.  Padded frames: a logit of
+    +200 from a channel of their own and POISON in h.  -> dict(a1 [B, T, att], wc [C, att], h, mean, std, n_live, eps)"""
+    d = pool_uniform_case(B, T, C, level=0.0, fused=True, n=n)
+    pair = {"a1": ((0.125 + 2.0 ** -16, 1.0), (1.0, -(0.125 + 2.0 ** -16))),
+            "wc": ((1024.0, 1.0), (2049.0 * 2.0 ** -28, -(2.0 + 2.0 ** -10) / FUSED_WS))}[side]
+    a1 = np.zeros((B, T, att))
+    a1[:, 1:n:2, 0], a1[:, 1:n:2, 1] = pair[0]
+    a1[:, 0:n:2, 2] = 1.0
+    a1[:, n:, 3] = 1.0
+    wc = np.zeros((C, att))
+    wc[:, 0], wc[:, 1] = pair[1]
+    wc[:, 3] = 200.0
+    need_f32("fused-split", a1, wc)
+    logit = fused_split_logits(a1.reshape(B * T, att), wc).reshape(B, T, C)
+    if logit[:, :n].any() or not (logit[:, n:] == 200.0).all():
+        raise BudgetError(f"fused-split {side}: the live logits are not all 0")
+    return dict(d, a1=a1, wc=wc)
+
+
 # ------------------------------------------------------------------ products outside the network
 
-def affinity_rows(n, d=192, seed=0):
+def affinity_rows(n, d=192, seed=0, e=0):
     """Rows in {0, +-1} with exactly 16 non-zeros (norm 4, cosine k / 16); row 2 zero; rows 1 and n - 1 copies of row 0 (cosine 1).
     -> (X, K) with K[i][j] = k / 16."""
     register("affinity-k16", "dense"), register("affinity-duplicates", "gather")
@@ -682,6 +891,10 @@ def affinity_rows(n, d=192, seed=0):
     X[n - 1] = X[0]
     K = (X @ X.T) / 16.0
     need_f32("affinity", K * 16.0, K)
+    if e:                                                   # the twin: every row times 2^e; the cosines are those of the unscaled rows
+        need_f32("affinity", scaled(e, X), e=e)
+        need_f32("affinity", scaled(2 * e, np.abs(X) @ np.abs(X).T), e=2 * e)
+        X = scaled(e, X)
     return X, K
 
 
@@ -745,7 +958,7 @@ def spectral_expected(K, scale, V, zero_diag):
     return A.sum(1), scale[:, None] * (A @ (scale[:, None] * V))
 
 
-def argmax_case(N, K, D, seed=0):
+def argmax_case(N, K, D, seed=0, e=0):
     """Integer rows and centres, the centres at (0, K - 1) and (3, 4) duplicated: np.argmax returns the first maximum."""
     register("argmax-duplicates", "gather"), register("argmax-int", "dense")
     rng = np.random.default_rng(seed + N + K + D)
@@ -759,7 +972,9 @@ def argmax_case(N, K, D, seed=0):
         c[3] = c[0]                                         # (K - 1 == 4: the two pairs share a centre)
     sim = w @ c.T
     need_f32("sim_argmax", np.abs(w) @ np.abs(c).T)
-    return w, c, sim.argmax(1).astype(np.int32), sim.max(1)
+    if e:                                                   # the twin: the rows times 2^e -- the same index, the score times 2^e
+        need_f32("sim_argmax", scaled(e, w), scaled(e, np.abs(w) @ np.abs(c).T), e=e)
+    return scaled(e, w), c, sim.argmax(1).astype(np.int32), scaled(e, sim.max(1))
 
 
 def topk_reference(x, k):
@@ -768,7 +983,7 @@ def topk_reference(x, k):
     return top.mean(1), top.std(1)
 
 
-def topk_case(n, k, seed=0):
+def topk_case(n, k, seed=0, e=0):
     """Rows [7, n] of integers, signs mixed, +0.0 and -0.0 together -> (x, mean, std), NaN where the exact answer is not representable
     (k no power of two and the quotient no integer; a variance that is no perfect square).
       row 0: k / 2 copies of +3 above a long run of -3, the k-th value, of which k / 2 are taken: mean 0, std 3
@@ -804,6 +1019,10 @@ def topk_case(n, k, seed=0):
     need_f32("topk", np.abs(top).sum(1), mean[mean_ok], ((top - mean[:, None]) ** 2)[mean_ok], ss[mean_ok])
     root = np.sqrt(ss / kk)
     std_ok = mean_ok & np.array([(pow2 or s % kk == 0) for s in ss]) & (root * 64 == np.round(root * 64))
+    if e:                                                   # the twin: x times 2^e (ldexp keeps the sign of -0.0)
+        need_f32("topk", *scaled(e, x, np.abs(top).sum(1), mean[mean_ok]), e=e)
+        need_f32("topk", *scaled(2 * e, ((top - mean[:, None]) ** 2)[mean_ok], ss[mean_ok]), e=2 * e)
+        x, mean, std = scaled(e, x, mean, std)
     return x, np.where(mean_ok, mean, np.nan), np.where(std_ok, std, np.nan)
 
 

@@ -16,6 +16,9 @@ Conv shapes (B, T, cin, cout, k, dil) and what they cross:
   five), N128 / W1032 / W256 / W1024: the narrow and wide forms of sd_conv1d_cl_split16, C*: the column statistics.
   S5  8, 128, 32, 512, 3, 2    32 tiles of 128x128 but 128 of 64x64: the 64-row form of the 64x64 ring kernel, which S1 .. S3 never reach
 
+Every test body takes an exponent `e` (default 0, and 0 in every test of this file): tests/test_gpu_scale.py runs the same bodies on the
+twins at 2^e (tests/helpers/exact_cases.py), so a twin sees the shapes, selections, buffers and launch labels of its unscaled case.
+
 Every run is held to the launch label it must take (tests/helpers/launch_log.py; the labels per case, selection, storage type and
 tuning are stated in tests/helpers/exact_cases.py): the conv operators to exactly that label and no other kernel of the operator, the
 reductions and products to at least the labels named.
@@ -139,8 +142,9 @@ def run_conv(dev, c, op, xdt=F32, ydt=F32, split_out=False, colstat=None):
 def check_conv(dev, c, got, ydt, what):
     from speech_diarization_amd import ops
     what = f"{c.name} {what}"
-    if "ysplit" in got:        # bit for bit what sd_split16_pack_f32 makes of the integer answer
+    if "ysplit" in got:        # bit for bit what sd_split16_pack_f32 makes of the integer answer, and what the header's rule makes of it in numpy
         _same(got["ysplit"], ops.split16_pack(_dev(c.y, F32, dev), 0, c.cout), what + " y (split)")
+        _same(got["ysplit"], torch.from_numpy(E.split16_rows(c.y)), what + " y (split, numpy pack)")
     else:
         _same(got["y"], _dev(c.y, ydt, dev), what + " y")
     if c.tee_hi:
@@ -179,12 +183,12 @@ F32_CASES = [n for n in E.CONV_CASE_NAMES if n[0] == "S"]
 
 
 @pytest.mark.parametrize("name", F32_CASES)
-def test_conv1d_cl_f32_every_selection_gives_the_integers(dev, name):
+def test_conv1d_cl_f32_every_selection_gives_the_integers(dev, name, e=0):
     """All eight selections of the exact-f32 operator must give the reference's bits, hence each other's.  S2 under "wide256" must have
     launched the 256x256 kernel; S4 also goes through sd_seg_gemm_f32, whose grid split-K (cin_pad = 544: five splits of 128, the last
-    ragged) must have run."""
+    ragged) must have run.  (`e`, here and below: the twin at 2^e that tests/test_gpu_scale.py runs through the same body.)"""
     N, _ = _lib()
-    c = E.conv_case(name)
+    c = E.conv_case(name, e)
     try:
         for sel in CONV_KERNELS:
             select_conv_kernel(sel)
@@ -210,10 +214,10 @@ def test_conv1d_cl_f32_every_selection_gives_the_integers(dev, name):
 
 
 @pytest.mark.parametrize("name", ["P-rows", "P-chan", "P-dense"])
-def test_conv1d_cl_packed_f32_gives_the_integers(dev, name):
+def test_conv1d_cl_packed_f32_gives_the_integers(dev, name, e=0):
     """Spans 5, 7, 5, 9, 131: "P-rows" returns the source row of every tap, so a tap that crossed a span edge names the row it read;
     "P-dense" carries a bias per span."""
-    c = E.conv_case(name)
+    c = E.conv_case(name, e)
     with expect_launches(exactly=[E.PACKED_LABEL], family=F32_CONV):
         got = run_conv(dev, c, "packed")
     check_conv(dev, c, got, F32, "packed")
@@ -223,13 +227,13 @@ F16_CASES = [n for n in E.CONV_CASE_NAMES if n[0] == "H"]
 
 
 @pytest.mark.parametrize("name", F16_CASES)
-def test_conv1d_cl_f16_gives_the_integers(dev, f16_tiles, name):
+def test_conv1d_cl_f16_gives_the_integers(dev, f16_tiles, name, e=0):
     """f16 and f32 x, f16 and f32 y, under both tile choices; the cout >= 1024 cases also with SD_TUNE_T256_LOCKSTEP_TILES = 0, which
     makes H2L (register epilogue, four column tiles) take the lockstep walk of the 256x256 kernel from its first tile: hardware dispatch
     and lockstep must both give the integers.  H2-dense takes the register epilogue, H2-dense-tee / H2w-dense-tee
     (cout 1032 / 1100, per-segment bias, a tee) the staged one."""
     N, lib = _lib()
-    c = E.conv_case(name)
+    c = E.conv_case(name, e)
     for xdt in (F16, F32):
         for ydt in (F16, F32):
             with expect_launches(exactly=[E.f16_label(name, f16_tiles, xdt == F16, ydt == F16)], family=F16_CONV):
@@ -247,13 +251,13 @@ def test_conv1d_cl_f16_gives_the_integers(dev, f16_tiles, name):
 
 
 @pytest.mark.parametrize("name", [n for n in E.CONV_CASE_NAMES if n[0] in "NW"])
-def test_conv1d_cl_split16_gives_the_integers(dev, name):
+def test_conv1d_cl_split16_gives_the_integers(dev, name, e=0, side="x"):
     """Wide form (x packed by sd_split16_pack_f32, cout 1032 and 256) and narrow form (f32 x, cout 128, full tee + tee_add, per-segment
     bias): y as f32 and, where cout % 32 == 0, as SD_DT_SPLIT16 -- the bits sd_split16_pack_f32 makes of the integer answer.  The
     2049 s operands sit on the activations ("split_x": lo.hi carries weight) and on the weights ("split_w": hi.lo does, through the
     2^s of the weight pack and w_scale_inv)."""
     N, lib = _lib()
-    c = E.conv_case(name)
+    c = E.conv_case(name, e, side=side)
     op = "narrow" if name[0] == "N" else "wide"
     with expect_launches(exactly=E.split_labels(name), family=SPLIT_CONV):
         got = run_conv(dev, c, op)
@@ -282,26 +286,28 @@ def _check_colstat(dev, c, got_y, cs, n_cs, ydt, what):
     _same(torch.where(live, got, torch.zeros_like(got)), want, what + " raw [sum | sumsq] units")
     mean, std = E.colstat_stats(c)
     y = got_y.contiguous()
+    eps = E.twin_eps(c.e)                                   # 1e-12 4^e: a constant column's std is sqrt(eps) 2^e
     with expect_launches(exactly=["colstat_finish_kernel<f16>" if ydt == F16 else "colstat_finish_kernel<f32>"]):
-        st = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev), want_std=True)
-        only_mean = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev))
+        st = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev), want_std=True, eps=eps)
+        only_mean = ops.colstat_finish(cs, y, c.B, c.T, pivot=_dev(c.shift, F32, dev), eps=eps)
     torch.cuda.synchronize()
     _same(st[:, :c.cout], _dev(mean, F32, dev), what + " mean")
     _same(only_mean, _dev(mean, F32, dev), what + " mean (no std)")
-    var0 = torch.from_numpy(std == E.SQRT_EPS).to(dev)
-    square = torch.from_numpy(~np.isnan(std) & (std != E.SQRT_EPS)).to(dev)
+    root = float(np.ldexp(E.SQRT_EPS, c.e))
+    var0 = torch.from_numpy(std == root).to(dev)
+    square = torch.from_numpy(~np.isnan(std) & (std != root)).to(dev)
     got_sd = st[:, c.cout:]
     assert int(var0.sum()) > 0 and int(square.sum()) > 0
     _same(got_sd[square], _dev(std, F32, dev)[square], what + " std (perfect squares)")
-    torch.testing.assert_close(got_sd[var0], torch.full_like(got_sd[var0], 1e-6), rtol=1e-6, atol=0.0)
+    torch.testing.assert_close(got_sd[var0], torch.full_like(got_sd[var0], float(np.ldexp(1e-6, c.e))), rtol=1e-6, atol=0.0)
 
 
 @pytest.mark.parametrize("name", ["C3x128-256", "C5x64-256"])
-def test_colstat_f32_gives_the_integer_sums(dev, name):
+def test_colstat_f32_gives_the_integer_sums(dev, name, e=0):
     """Under every selection ("tiles64" takes the 128x64 kernel at T >= 128; the 80 / 96 / 112-row selections must fall back to units of
     128 rows, see the module docstring)."""
     from speech_diarization_amd import ops
-    c = E.conv_case(name)
+    c = E.conv_case(name, e, "f32")
     n_cs = ops.colstat_floats(c.M, c.cout)
     try:
         for sel in CONV_KERNELS:
@@ -316,10 +322,10 @@ def test_colstat_f32_gives_the_integer_sums(dev, name):
 
 
 @pytest.mark.parametrize("name", ["C3x128-256", "C5x64-256", "C11x64-1024", "C3x128-1024"])
-def test_colstat_f16_gives_the_integer_sums(dev, f16_tiles, name):
+def test_colstat_f16_gives_the_integer_sums(dev, f16_tiles, name, e=0):
     """cout 1024: (11, 64) is taken by the 128x128 kernel (T < 128), (3, 128) by the 256x256 kernel under "wide256"."""
     from speech_diarization_amd import ops
-    c = E.conv_case(name)
+    c = E.conv_case(name, e, "f16")
     n_cs = ops.colstat_floats(c.M, c.cout)
     for ydt in (F16, F32):
         cs = torch.full((n_cs + 4096,), NAN, device=dev)
@@ -329,10 +335,10 @@ def test_colstat_f16_gives_the_integer_sums(dev, f16_tiles, name):
         _check_colstat(dev, c, got["y"], cs, n_cs, ydt, f"{name} f16 {f16_tiles} y {ydt}")
 
 
-def test_colstat_split16_gives_the_integer_sums(dev):
+def test_colstat_split16_gives_the_integer_sums(dev, e=0):
     """The wide split kernel takes column statistics from T >= 128: (3, 128) only."""
     from speech_diarization_amd import ops
-    c = E.conv_case("C3x128-256")
+    c = E.conv_case("C3x128-256", e, "split")
     n_cs = ops.colstat_floats(c.M, c.cout)
     cs = torch.full((n_cs + 4096,), NAN, device=dev)
     with expect_launches(exactly=E.split_labels("C3x128-256"), family=SPLIT_CONV):
@@ -343,13 +349,13 @@ def test_colstat_split16_gives_the_integer_sums(dev):
 
 @pytest.mark.parametrize("kind", ["onehot", "sums"])
 @pytest.mark.parametrize("B,T,dil", E.CHAIN_SHAPES)
-def test_res2net_chain_f16_gives_the_integer_chain(dev, kind, B, T, dil):
+def test_res2net_chain_f16_gives_the_integer_chain(dev, kind, B, T, dil, e=0):
     """The fused chain must equal the integer chain, and the seven unfused f16 convs (tee + tee_add carrying c_{j+1} + y_j) must give
     the same bits.  "onehot": a composition of gathers and adds; "sums": four +-1 weights per output channel."""
     from speech_diarization_amd import ops
     n = 7
     assert ops.res2net_chain_supported(T, 128, n, 3, dil)
-    r, layers, want = E.chain_case(kind, B, T, dil)
+    r, layers, want = E.chain_case(kind, B, T, dil, e=e)
     dl = [dict(w=ops.pack_weight(L["w"], dev, F16), bias=_dev(L["bias"], F32, dev), scale=_dev(L["scale"], F32, dev),
                shift=_dev(L["shift"], F32, dev), dil=dil) for L in layers]
     got = _dev(r, F16, dev)
@@ -383,17 +389,19 @@ def _t(dtype):
     return "f16" if dtype == F16 else "f32"
 
 
-def _check_stats(got, mean, std, Cc, what, dev):
-    """mean bit for bit; std bit for bit where the variance is a perfect square, sqrt(eps) where it is 0."""
+def _check_stats(got, mean, std, Cc, what, dev, e=0):
+    """mean bit for bit; std bit for bit where the variance is a perfect square, sqrt(eps) where it is 0 (a twin at 2^e, whose eps is
+    1e-12 4^e: sqrt(eps) 2^e)."""
     _same(got[:, :Cc], _dev(mean, F32, dev), what + " mean")
     if std is None:
         return
-    var0 = torch.from_numpy(std == E.SQRT_EPS).to(dev)
-    square = torch.from_numpy(~np.isnan(std) & (std != E.SQRT_EPS)).to(dev)
+    root = float(np.ldexp(E.SQRT_EPS, e))
+    var0 = torch.from_numpy(std == root).to(dev)
+    square = torch.from_numpy(~np.isnan(std) & (std != root)).to(dev)
     sd = got[:, Cc:]
     _same(sd[square], _dev(std, F32, dev)[square], what + " std (perfect squares)")
     if int(var0.sum()):
-        torch.testing.assert_close(sd[var0], torch.full_like(sd[var0], 1e-6), rtol=1e-6, atol=0.0)
+        torch.testing.assert_close(sd[var0], torch.full_like(sd[var0], float(np.ldexp(1e-6, e))), rtol=1e-6, atol=0.0)
 
 
 # (B, T, C): 16 x 16 workgroups (grid.x * B < 256) and 64 x 4 ones; C = 100 is what the entry takes of "100 padded to a multiple of 4"
@@ -404,21 +412,21 @@ REDUCE_FORM = {(5, 64, 100): "16x16", (40, 64, 3072): "64x4", (5, 128, 100): "16
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("B,T,C_", REDUCE_SHAPES)
-def test_seg_mean_std_and_se_scale_residual_uniform(dev, dtype, B, T, C_):
+def test_seg_mean_std_and_se_scale_residual_uniform(dev, dtype, B, T, C_, e=0):
     from speech_diarization_amd import ops
     N, lib = _lib()
-    d = E.reduction_case(B, T, C_, f16=dtype == F16)
+    d = E.reduction_case(B, T, C_, f16=dtype == F16, e=e)
     xbuf, xv = _framed(d["x"].reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_ + 8), NAN, device=dev)
     with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},uniform,{REDUCE_FORM[B, T, C_]}>"]):
-        N.check(lib.sd_seg_mean_std_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, C_, 1, C.c_float(1e-12), out.data_ptr(), _stream()),
+        N.check(lib.sd_seg_mean_std_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, C_, 1, C.c_float(d["eps"]), out.data_ptr(), _stream()),
                 "sd_seg_mean_std_dt")
         torch.cuda.synchronize()
     assert bool(torch.isnan(out.view(-1)[B * 2 * C_:]).all())
-    _check_stats(out.view(-1)[:B * 2 * C_].view(B, 2 * C_), d["mean"], d["std"], C_, f"seg_mean_std {dtype}", dev)
+    _check_stats(out.view(-1)[:B * 2 * C_].view(B, 2 * C_), d["mean"], d["std"], C_, f"seg_mean_std {dtype}", dev, e)
     if dtype == F32:
         _same(ops.seg_mean(xbuf, B, T, col0=8, C_=C_), _dev(d["mean"], F32, dev), "seg_mean")
-        _check_stats(ops.seg_mean_std(xv.contiguous(), B, T), d["mean"], d["std"], C_, "seg_mean_std_f32", dev)
+        _check_stats(ops.seg_mean_std(xv.contiguous(), B, T, eps=d["eps"]), d["mean"], d["std"], C_, "seg_mean_std_f32", dev, e)
     if C_ % 8 == 0 or dtype == F32:
         rbuf, _ = _framed(d["res"].reshape(B * T, C_), dtype, dev)
         ybuf = torch.full((B * T, C_ + 16), NAN, dtype=dtype, device=dev)
@@ -433,36 +441,36 @@ def test_seg_mean_std_and_se_scale_residual_uniform(dev, dtype, B, T, C_):
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("T,n", E.LENS)
-def test_seg_mean_std_with_lens_ignores_the_padded_frames(dev, dtype, T, n):
+def test_seg_mean_std_with_lens_ignores_the_padded_frames(dev, dtype, T, n, e=0):
     """rel_len = n / T with n a power of two; every padded frame holds 1e30 (f16: 65504), so a frame that leaks shows."""
     N, lib = _lib()
     B, C_ = 5, 100
-    d = E.reduction_case(B, T, C_, lens=(n,), f16=dtype == F16)
+    d = E.reduction_case(B, T, C_, lens=(n,), f16=dtype == F16, e=e)
     rel = torch.tensor([float(E.rel_len(T, m)) if m != T else 1.0 for m in d["n_live"]], device=dev)
     xbuf, _ = _framed(d["x_poisoned"].reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_), NAN, device=dev)
     with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},uniform,16x16>"]):      # B = 5, one channel block: the small grid
-        N.check(lib.sd_seg_mean_std_lens_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, rel.data_ptr(), C_, 1, C.c_float(1e-12),
+        N.check(lib.sd_seg_mean_std_lens_dt(xbuf.data_ptr(), _dt(N, dtype), xbuf.stride(0), 8, B, T, rel.data_ptr(), C_, 1, C.c_float(d["eps"]),
                                             out.data_ptr(), _stream()), "sd_seg_mean_std_lens_dt")
         torch.cuda.synchronize()
-    _check_stats(out, d["mean"], d["std"], C_, f"seg_mean_std lens T={T} n={n} {dtype}", dev)
+    _check_stats(out, d["mean"], d["std"], C_, f"seg_mean_std lens T={T} n={n} {dtype}", dev, e)
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])
-def test_seg_mean_std_and_se_scale_residual_packed(dev, dtype):
+def test_seg_mean_std_and_se_scale_residual_packed(dev, dtype, e=0):
     """Packed spans of 64, 128, 32, 64 and 16 rows (powers of two: exact means): the span map of the statistics and of the gate."""
     from speech_diarization_amd import ops
     spans = (64, 128, 32, 64, 16)
     C_ = 104
-    parts = [E.reduction_case(1, L, C_, f16=dtype == F16, seed=i) for i, L in enumerate(spans)]
+    parts = [E.reduction_case(1, L, C_, f16=dtype == F16, seed=i, e=e) for i, L in enumerate(spans)]
     x = _dev(np.concatenate([p["x"][0] for p in parts]), dtype, dev)
     res = _dev(np.concatenate([p["res"][0] for p in parts]), dtype, dev)
     gate = _dev(np.concatenate([p["gate"] for p in parts]), F32, dev)
     fs = np.concatenate([[0], np.cumsum(spans)]).astype(np.int32)
     with expect_launches(exactly=[f"seg_mean_std_kernel<{_t(dtype)},packed,64x4>"]):       # a packed map never takes 16 x 16
-        got = ops.seg_mean_std_packed(x, fs)
+        got = ops.seg_mean_std_packed(x, fs, eps=parts[0]["eps"])
         torch.cuda.synchronize()
-    _check_stats(got, np.concatenate([p["mean"] for p in parts]), np.concatenate([p["std"] for p in parts]), C_, f"packed seg_mean_std {dtype}", dev)
+    _check_stats(got, np.concatenate([p["mean"] for p in parts]), np.concatenate([p["std"] for p in parts]), C_, f"packed seg_mean_std {dtype}", dev, e)
     with expect_launches(exactly=[f"se_scale_residual_kernel<{_t(dtype)},packed>"]):
         y = ops.se_scale_residual_packed(x, gate, res, fs)
         torch.cuda.synchronize()
@@ -480,13 +488,13 @@ def _pool_label(dtype, T, C_):
     return f"asp_pool_lds_kernel<{_t(dtype)}>" if staged else f"asp_pool_kernel<{_t(dtype)},uniform>"
 
 
-def _asp_pool(dev, logit, h, dtype, B, T, C_, rel=None):
+def _asp_pool(dev, logit, h, dtype, B, T, C_, rel=None, eps=1e-12):
     N, lib = _lib()
     lg, hd = _dev(logit.reshape(B * T, C_), dtype, dev), _dev(h.reshape(B * T, C_), dtype, dev)
     out = torch.full((B, 2 * C_), NAN, device=dev)
     with expect_launches(exactly=[_pool_label(dtype, T, C_)], family={"asp_pool_kernel", "asp_pool_lds_kernel"}):
         N.check(lib.sd_asp_pool_lens_dt(lg.data_ptr(), C_, hd.data_ptr(), _dt(N, dtype), C_, B, T, None if rel is None else rel.data_ptr(), C_,
-                                        C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_pool_lens_dt")
+                                        C.c_float(eps), out.data_ptr(), _stream()), "sd_asp_pool_lens_dt")
         torch.cuda.synchronize()
     return out
 
@@ -497,66 +505,66 @@ POOL_SHAPES = [(3, 128, 128), (3, 256, 128), (3, 64, 100), (2, 201, 128), (2, 25
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("B,T,C_", POOL_SHAPES)
-def test_asp_pool_one_hot_logits_return_one_frame(dev, dtype, B, T, C_):
+def test_asp_pool_one_hot_logits_return_one_frame(dev, dtype, B, T, C_, e=0):
     """logit 0 at t*(b, c) and -200 elsewhere: the mean is h[b, t*, c] bit for bit, the std sqrt(eps); t* walks both sides of every
     row-phase, staging-pass and chunk boundary, the first and the last frame."""
-    d = E.pool_onehot_case(B, T, C_)
-    got = _asp_pool(dev, d["logit"], d["h"], dtype, B, T, C_)
-    _check_stats(got, d["mean"], np.full_like(d["mean"], E.SQRT_EPS), C_, f"asp_pool one-hot T={T} C={C_} {dtype}", dev)
+    d = E.pool_onehot_case(B, T, C_, e=e, f16=bool(e) and dtype == F16)
+    got = _asp_pool(dev, d["logit"], d["h"], dtype, B, T, C_, eps=d["eps"])
+    _check_stats(got, d["mean"], np.full_like(d["mean"], d["sqrt_eps"]), C_, f"asp_pool one-hot T={T} C={C_} {dtype}", dev, e)
     if dtype == F32:
         from speech_diarization_amd import ops
-        plain = ops.asp_pool(_dev(d["logit"].reshape(B * T, C_), F32, dev), _dev(d["h"].reshape(B * T, C_), F32, dev), B, T)
+        plain = ops.asp_pool(_dev(d["logit"].reshape(B * T, C_), F32, dev), _dev(d["h"].reshape(B * T, C_), F32, dev), B, T, eps=d["eps"])
         _same(plain, got, "sd_asp_pool_f32")
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("B,T,C_", [(3, 128, 128), (3, 256, 128), (3, 64, 100)])
-def test_asp_pool_uniform_weights_give_the_exact_mean_and_std(dev, dtype, B, T, C_):
-    d = E.pool_uniform_case(B, T, C_)
-    got = _asp_pool(dev, d["logit"], d["h"], dtype, B, T, C_)
-    _check_stats(got, d["mean"], d["std"], C_, f"asp_pool uniform T={T} C={C_} {dtype}", dev)
+def test_asp_pool_uniform_weights_give_the_exact_mean_and_std(dev, dtype, B, T, C_, e=0):
+    d = E.pool_uniform_case(B, T, C_, e=e, f16=bool(e) and dtype == F16)
+    got = _asp_pool(dev, d["logit"], d["h"], dtype, B, T, C_, eps=d["eps"])
+    _check_stats(got, d["mean"], d["std"], C_, f"asp_pool uniform T={T} C={C_} {dtype}", dev, e)
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("T,n", E.LENS)
 @pytest.mark.parametrize("C_", [128, 100])
-def test_asp_pool_with_lens_ignores_the_padded_frames(dev, dtype, T, n, C_):
+def test_asp_pool_with_lens_ignores_the_padded_frames(dev, dtype, T, n, C_, e=0):
     """A +200 logit and a 1e30 value (f16: 65504) sit in every padded frame."""
     B = 3
-    d = E.pool_onehot_case(B, T, C_, lens=(n, T, n))
+    d = E.pool_onehot_case(B, T, C_, lens=(n, T, n), e=e, f16=bool(e) and dtype == F16)
     rel = torch.tensor([float(E.rel_len(T, m)) if m != T else 1.0 for m in d["n_live"]], device=dev)
-    got = _asp_pool(dev, d["logit"], d["h"] if dtype == F32 else d["h_f16"], dtype, B, T, C_, rel)
-    _check_stats(got, d["mean"], np.full_like(d["mean"], E.SQRT_EPS), C_, f"asp_pool lens T={T} n={n} {dtype}", dev)
+    got = _asp_pool(dev, d["logit"], d["h"] if dtype == F32 else d["h_f16"], dtype, B, T, C_, rel, eps=d["eps"])
+    _check_stats(got, d["mean"], np.full_like(d["mean"], d["sqrt_eps"]), C_, f"asp_pool lens T={T} n={n} {dtype}", dev, e)
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])
 @pytest.mark.parametrize("T,n", E.LENS)
 @pytest.mark.parametrize("C_", [128, 100])
-def test_asp_pool_with_lens_uniform_weights_over_the_live_frames(dev, dtype, T, n, C_):
+def test_asp_pool_with_lens_uniform_weights_over_the_live_frames(dev, dtype, T, n, C_, e=0):
     """Equal logits over the n live frames (a power of two), the padded ones poisoned: the exact mean and std of the live frames."""
     B = 3
-    d = E.pool_uniform_case(B, T, C_, n=n)
+    d = E.pool_uniform_case(B, T, C_, n=n, e=e, f16=bool(e) and dtype == F16)
     rel = torch.full((B,), float(E.rel_len(T, n)), device=dev)
-    got = _asp_pool(dev, d["logit"], d["h"] if dtype == F32 else d["h_f16"], dtype, B, T, C_, rel)
-    _check_stats(got, d["mean"], d["std"], C_, f"asp_pool lens uniform T={T} n={n} {dtype}", dev)
+    got = _asp_pool(dev, d["logit"], d["h"] if dtype == F32 else d["h_f16"], dtype, B, T, C_, rel, eps=d["eps"])
+    _check_stats(got, d["mean"], d["std"], C_, f"asp_pool lens uniform T={T} n={n} {dtype}", dev, e)
 
 
-def test_asp_pool_packed_one_hot(dev):
+def test_asp_pool_packed_one_hot(dev, e=0, dtypes=(F32, F16)):
     from speech_diarization_amd import ops
     spans = (64, 257, 5, 128)
     C_ = 128
-    parts = [E.pool_onehot_case(1, L, C_, seed=i) for i, L in enumerate(spans)]
+    parts = [E.pool_onehot_case(1, L, C_, seed=i, e=e, f16=bool(e) and dtypes == (F16,)) for i, L in enumerate(spans)]
     fs = np.concatenate([[0], np.cumsum(spans)]).astype(np.int32)
-    for dtype in (F32, F16):
+    for dtype in dtypes:
         with expect_launches(exactly=[f"asp_pool_kernel<{_t(dtype)},packed>"], family=POOL_FAMILY):     # a packed map always streams
             got = ops.asp_pool_packed(_dev(np.concatenate([p["logit"][0] for p in parts]), dtype, dev),
-                                      _dev(np.concatenate([p["h"][0] for p in parts]), dtype, dev), fs)
+                                      _dev(np.concatenate([p["h"][0] for p in parts]), dtype, dev), fs, eps=parts[0]["eps"])
             torch.cuda.synchronize()
         mean = np.concatenate([p["mean"] for p in parts])
-        _check_stats(got, mean, np.full_like(mean, E.SQRT_EPS), C_, f"asp_pool packed {dtype}", dev)
+        _check_stats(got, mean, np.full_like(mean, parts[0]["sqrt_eps"]), C_, f"asp_pool packed {dtype}", dev, e)
 
 
-def _attend(dev, mode, a1, wc, h, B, T, C_, rel=None):
+def _attend(dev, mode, a1, wc, h, B, T, C_, rel=None, eps=1e-12):
     from speech_diarization_amd import ops
     N, lib = _lib()
     dtype = F16 if mode == "f16" else F32
@@ -567,7 +575,7 @@ def _attend(dev, mode, a1, wc, h, B, T, C_, rel=None):
     dt = {"f32": N.SD_DT_F32, "f16": N.SD_DT_F16, "split16": N.SD_DT_SPLIT16}[mode]
     with expect_launches(exactly=[_fused_label(mode, T)], family={"asp_attend_pool_f32_kernel", "asp_attend_pool_f16_kernel"}):
         N.check(lib.sd_asp_attend_pool_lens_dt(a1d.data_ptr(), wp.data_ptr(), hd.data_ptr(), dt, C_, B, T, None if rel is None else rel.data_ptr(),
-                                               C_, a1d.shape[1], C.c_float(1e-12), out.data_ptr(), _stream()), "sd_asp_attend_pool_lens_dt")
+                                               C_, a1d.shape[1], C.c_float(eps), out.data_ptr(), _stream()), "sd_asp_attend_pool_lens_dt")
         torch.cuda.synchronize()
     return out
 
@@ -587,49 +595,49 @@ FUSED_T = [64, 65, 128, 129, 192, 193, 208, 209, 256]
 
 @pytest.mark.parametrize("mode", ["f32", "f16", "split16"])
 @pytest.mark.parametrize("T", FUSED_T)
-def test_fused_attention_pooling_one_hot(dev, mode, T):
+def test_fused_attention_pooling_one_hot(dev, mode, T, e=0):
     """The logits are built inside the kernel from a one-hot a1 and an integer wc (0 at t*, -200 elsewhere)."""
     B, C_ = 3, 256
-    d = E.pool_onehot_case(B, T, C_, fused=True)
+    d = E.pool_onehot_case(B, T, C_, fused=True, e=e, f16=bool(e) and mode == "f16")
     a1, wc = E.attend_factors(d["logit"])
-    got = _attend(dev, mode, a1, wc, d["h"], B, T, C_)
-    _check_stats(got, d["mean"], np.full_like(d["mean"], E.SQRT_EPS), C_, f"fused one-hot {mode} T={T}", dev)
+    got = _attend(dev, mode, a1, wc, d["h"], B, T, C_, eps=d["eps"])
+    _check_stats(got, d["mean"], np.full_like(d["mean"], d["sqrt_eps"]), C_, f"fused one-hot {mode} T={T}", dev, e)
 
 
 @pytest.mark.parametrize("mode", ["f32", "f16", "split16"])
 @pytest.mark.parametrize("T", [64, 128, 256])
-def test_fused_attention_pooling_uniform_weights(dev, mode, T):
+def test_fused_attention_pooling_uniform_weights(dev, mode, T, e=0):
     """All logits 0 (see the module docstring for why not another level): the exact mean; the f32 / split16 kernels (two-pass variance)
     the exact std as well, the f16 kernel (E[h^2] - mu^2 in f32, exact on these integers) too."""
     B, C_ = 3, 256
-    d = E.pool_uniform_case(B, T, C_, level=0.0, fused=True)
+    d = E.pool_uniform_case(B, T, C_, level=0.0, fused=True, e=e, f16=bool(e) and mode == "f16")
     a1, wc = E.attend_factors(d["logit"])
-    got = _attend(dev, mode, a1, wc, d["h"], B, T, C_)
-    _check_stats(got, d["mean"], d["std"], C_, f"fused uniform {mode} T={T}", dev)
+    got = _attend(dev, mode, a1, wc, d["h"], B, T, C_, eps=d["eps"])
+    _check_stats(got, d["mean"], d["std"], C_, f"fused uniform {mode} T={T}", dev, e)
 
 
 @pytest.mark.parametrize("mode", ["f32", "f16", "split16"])
 @pytest.mark.parametrize("T,n", E.LENS)
-def test_fused_attention_pooling_with_lens_ignores_the_padded_frames(dev, mode, T, n):
+def test_fused_attention_pooling_with_lens_ignores_the_padded_frames(dev, mode, T, n, e=0):
     B, C_ = 3, 256
-    d = E.pool_onehot_case(B, T, C_, lens=(n, T, n), fused=True)
+    d = E.pool_onehot_case(B, T, C_, lens=(n, T, n), fused=True, e=e, f16=bool(e) and mode == "f16")
     a1, wc = E.attend_factors(d["logit"])
     rel = torch.tensor([float(E.rel_len(T, m)) if m != T else 1.0 for m in d["n_live"]], device=dev)
-    got = _attend(dev, mode, a1, wc, d["h_f16"] if mode == "f16" else d["h"], B, T, C_, rel)
-    _check_stats(got, d["mean"], np.full_like(d["mean"], E.SQRT_EPS), C_, f"fused lens {mode} T={T} n={n}", dev)
+    got = _attend(dev, mode, a1, wc, d["h_f16"] if mode == "f16" else d["h"], B, T, C_, rel, eps=d["eps"])
+    _check_stats(got, d["mean"], np.full_like(d["mean"], d["sqrt_eps"]), C_, f"fused lens {mode} T={T} n={n}", dev, e)
 
 
 @pytest.mark.parametrize("mode", ["f32", "f16", "split16"])
 @pytest.mark.parametrize("T,n", E.LENS)
-def test_fused_attention_pooling_with_lens_uniform_weights_over_the_live_frames(dev, mode, T, n):
+def test_fused_attention_pooling_with_lens_uniform_weights_over_the_live_frames(dev, mode, T, n, e=0):
     """Logits 0 over the n live frames, a +200 logit and 1e30 (f16: 65504) in every padded one: the exact mean and std of the live
     frames.  (The one-hot case cannot see a padded value that reaches the variance: its expected std is the clamp itself.)"""
     B, C_ = 3, 256
-    d = E.pool_uniform_case(B, T, C_, level=0.0, fused=True, n=n)
+    d = E.pool_uniform_case(B, T, C_, level=0.0, fused=True, n=n, e=e, f16=bool(e) and mode == "f16")
     a1, wc = E.attend_factors(d["logit"])
     rel = torch.full((B,), float(E.rel_len(T, n)), device=dev)
-    got = _attend(dev, mode, a1, wc, d["h_f16"] if mode == "f16" else d["h"], B, T, C_, rel)
-    _check_stats(got, d["mean"], d["std"], C_, f"fused lens uniform {mode} T={T} n={n}", dev)
+    got = _attend(dev, mode, a1, wc, d["h_f16"] if mode == "f16" else d["h"], B, T, C_, rel, eps=d["eps"])
+    _check_stats(got, d["mean"], d["std"], C_, f"fused lens uniform {mode} T={T} n={n}", dev, e)
 
 
 # ------------------------------------------------------------------ 3. products outside the network
@@ -651,13 +659,13 @@ AFFINITY_FAMILY = F32_CONV | SPLIT_CONV | {"affinity_sym_kernel"}
 
 
 @pytest.mark.parametrize("n", [4, 132, 260, 1030, 1412])
-def test_cosine_affinity_is_k_over_16(dev, n):
+def test_cosine_affinity_is_k_over_16(dev, n, e=0):
     """f32 and split16 (its alpha is 2^-8 and its row scale 2^4: powers of two, so the whole-matrix path is exact and stays in), the whole
     matrix and `rows=` blocks, a tight and a padded output (an odd ldo takes the paths without 16-byte stores).  n = 1412 = 12 tiles
     of 128: the smallest multiple of 4 whose unaligned whole matrix leaves the split-K kernel for the symmetric band walk of the
     128x128 kernel (12 x 12 = 144 >= 128 tiles)."""
     from speech_diarization_amd import ops
-    X, K = E.affinity_rows(n)
+    X, K = E.affinity_rows(n, e=e)
     xd = _dev(X, F32, dev)
     want = _dev(K, F32, dev)
     for split16 in (False, True):
@@ -731,9 +739,9 @@ def test_affinity_apply_and_degree_are_exact(dev, n, b):
 @pytest.mark.parametrize("K", [1, 5, 64])
 @pytest.mark.parametrize("N_", [1, 41, 130])
 @pytest.mark.parametrize("D", [7, 192, 200])
-def test_sim_argmax_returns_the_first_maximum(dev, K, N_, D):
+def test_sim_argmax_returns_the_first_maximum(dev, K, N_, D, e=0):
     from speech_diarization_amd import ops
-    w, c, best_want, score_want = E.argmax_case(N_, K, D)
+    w, c, best_want, score_want = E.argmax_case(N_, K, D, e=e)
     with expect_launches(exactly=["sim_argmax_kernel"]):
         best, score = ops.sim_argmax(_dev(w, F32, dev), _dev(c, F32, dev))
         torch.cuda.synchronize()
@@ -741,28 +749,29 @@ def test_sim_argmax_returns_the_first_maximum(dev, K, N_, D):
     _same(score, _dev(score_want, F32, dev), f"sim_argmax score K={K} N={N_} D={D}")
 
 
-def test_adjacent_cosine_and_l2norm_rows_are_exact(dev):
+def test_adjacent_cosine_and_l2norm_rows_are_exact(dev, e=0):
     """Rows of norm 4 with eps = 0 / eps_add = 0; a zero row under the sklearn guard."""
     from speech_diarization_amd import ops
-    X, K = E.affinity_rows(133)
+    X, K = E.affinity_rows(133, e=e)
     live = np.delete(X, 2, axis=0)                        # without the zero row: 0 / 0 has no exact answer
+    X, live = E.scaled(-e, X, live)                       # (the expected values below: those of the unscaled rows)
     Kl = (live @ live.T) / 16.0
     with expect_launches(exactly=["adjacent_cosine_kernel"]):
-        adj = ops.adjacent_cosine(_dev(live, F32, dev), eps=0.0)
+        adj = ops.adjacent_cosine(_dev(E.scaled(e, live), F32, dev), eps=0.0)
     _same(adj, _dev(np.diagonal(Kl, 1).copy(), F32, dev), "adjacent_cosine")
     with expect_launches(exactly=["l2norm_rows_kernel"]):
-        unit = ops.l2norm_rows(_dev(live, F32, dev))
+        unit = ops.l2norm_rows(_dev(E.scaled(e, live), F32, dev))
     _same(unit, _dev(live / 4.0, F32, dev), "l2norm_rows")
-    _same(ops.l2norm_rows(_dev(X, F32, dev), sklearn_zero_guard=True), _dev(X / 4.0, F32, dev), "l2norm_rows (sklearn guard)")
+    _same(ops.l2norm_rows(_dev(E.scaled(e, X), F32, dev), sklearn_zero_guard=True), _dev(X / 4.0, F32, dev), "l2norm_rows (sklearn guard)")
 
 
 @pytest.mark.parametrize("n", [50, 257, 1000])
 @pytest.mark.parametrize("k", [1, 64, "n"])
-def test_topk_mean_std_on_tied_integer_rows(dev, n, k):
+def test_topk_mean_std_on_tied_integer_rows(dev, n, k, e=0):
     """The k-th value tied many times, mixed signs (the ordered-key map flips at 0), +0.0 and -0.0 together, ld > n."""
     from speech_diarization_amd import ops
     k = n if k == "n" else k
-    x, mean, std = E.topk_case(n, k)
+    x, mean, std = E.topk_case(n, k, e=e)
     buf = torch.full((x.shape[0], n + 5), NAN, device=dev)
     buf[:, :n] = torch.from_numpy(x).to(dev)               # (float64 -> f32 keeps the sign of -0.0)
     with expect_launches(exactly=["topk_mean_std_kernel"]):
