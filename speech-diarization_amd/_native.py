@@ -230,51 +230,22 @@ def load() -> C.CDLL:
                 "There is deliberately no CPU fallback."
             )
         lib = C.CDLL(str(lib_path))
-        missing = [name for name in PROTOTYPES if not hasattr(lib, name)]
-        if missing:
-            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip.h: {missing}")
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.sd_abi_version() != SD_ABI_VERSION:
-            raise RuntimeError(f"libsd_hip.so ABI {lib.sd_abi_version()} != binding ABI {SD_ABI_VERSION}; rebuild")
-        missing = [name for name in SPECTRAL_PROTOTYPES if not hasattr(lib, name)]
-        if missing:
-            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_spectral.h: {missing}")
-        for name, (res, args) in SPECTRAL_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.sd_spectral_abi_version() != SD_SPECTRAL_ABI_VERSION:
-            raise RuntimeError(f"libsd_hip.so spectral ABI {lib.sd_spectral_abi_version()} != binding ABI {SD_SPECTRAL_ABI_VERSION}; rebuild")
-        missing = [name for name in AHC_PROTOTYPES if not hasattr(lib, name)]
-        if missing:
-            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_ahc.h: {missing}")
-        for name, (res, args) in AHC_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.sd_ahc_abi_version() != SD_AHC_ABI_VERSION:
-            raise RuntimeError(f"libsd_hip.so AHC ABI {lib.sd_ahc_abi_version()} != binding ABI {SD_AHC_ABI_VERSION}; rebuild")
-        missing = [name for name in HDBSCAN_PROTOTYPES if not hasattr(lib, name)]
-        if missing:
-            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_hdbscan.h: {missing}")
-        for name, (res, args) in HDBSCAN_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.sd_hdbscan_abi_version() != SD_HDBSCAN_ABI_VERSION:
-            raise RuntimeError(f"libsd_hip.so HDBSCAN ABI {lib.sd_hdbscan_abi_version()} != binding ABI {SD_HDBSCAN_ABI_VERSION}; rebuild")
-        missing = [name for name in TRACE_PROTOTYPES if not hasattr(lib, name)]
-        if missing:
-            raise RuntimeError(f"{lib_path} lacks symbols declared in include/sd_hip_trace.h: {missing}")
-        for name, (res, args) in TRACE_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.sd_trace_abi_version() != SD_TRACE_ABI_VERSION:
-            raise RuntimeError(f"libsd_hip.so trace ABI {lib.sd_trace_abi_version()} != binding ABI {SD_TRACE_ABI_VERSION}; rebuild")
+        for header, table, version, expected, label in (
+                ("sd_hip.h", PROTOTYPES, "sd_abi_version", SD_ABI_VERSION, ""),
+                ("sd_hip_spectral.h", SPECTRAL_PROTOTYPES, "sd_spectral_abi_version", SD_SPECTRAL_ABI_VERSION, "spectral "),
+                ("sd_hip_ahc.h", AHC_PROTOTYPES, "sd_ahc_abi_version", SD_AHC_ABI_VERSION, "AHC "),
+                ("sd_hip_hdbscan.h", HDBSCAN_PROTOTYPES, "sd_hdbscan_abi_version", SD_HDBSCAN_ABI_VERSION, "HDBSCAN "),
+                ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
+            missing = [name for name in table if not hasattr(lib, name)]
+            if missing:
+                raise RuntimeError(f"{lib_path} lacks symbols declared in include/{header}: {missing}")
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
+            got = getattr(lib, version)()
+            if got != expected:
+                raise RuntimeError(f"libsd_hip.so {label}ABI {got} != binding ABI {expected}; rebuild")
         for which, st in enumerate((sd_conv_args, sd_layer, sd_se_res2_block, sd_ecapa_weights)):
             if lib.sd_sizeof(which) != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__}: binding layout is {C.sizeof(st)} bytes, the library's {lib.sd_sizeof(which)}; rebuild")

@@ -502,6 +502,21 @@ def affinity_degree(K: torch.Tensor, zero_diag: bool = False) -> torch.Tensor:
     return deg
 
 
+def _rows_ld(rows: torch.Tensor, what: str) -> tuple[int, int, int]:
+    """(n, d, row stride) of a non-empty f32 matrix with contiguous rows; `what` names it in the message."""
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] == 0 or rows.shape[1] == 0 or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise ValueError(f"{what} must be a non-empty f32 matrix with contiguous rows, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
+    n, d = rows.shape
+    return n, d, max(rows.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
+
+
+def _workspace(ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
+    """`ws` if it holds `need` bytes, a fresh uint8 workspace otherwise."""
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+    return ws
+
+
 def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_diag: bool = False,
                    ws: torch.Tensor | None = None) -> torch.Tensor:
     """Y = diag(scale) max(K, 0) diag(scale) V on the GPU, the diagonal of K taken as 0 when `zero_diag`.  K f32 [N, N] read in
@@ -521,9 +536,7 @@ def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_d
         return Y
     lib = N.load()
     with torch.cuda.device(K.device):
-        need = int(lib.sd_affinity_apply_workspace_bytes(n, b))
-        if ws is None or ws.numel() * ws.element_size() < need:
-            ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=K.device)
+        ws = _workspace(ws, int(lib.sd_affinity_apply_workspace_bytes(n, b)), K.device)
         N.check(lib.sd_affinity_apply_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), scale.data_ptr(), V.data_ptr(), b, b,
                                           Y.data_ptr(), b, ws.data_ptr(), ws.numel() * ws.element_size(), _stream(K)), "sd_affinity_apply_f32")
     return Y
@@ -531,20 +544,13 @@ def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_d
 
 # ----------------------------------------------------------------------------- average-linkage clustering (include/sd_hip_ahc.h)
 
-def _ahc_sums(sums: torch.Tensor) -> tuple[int, int, int]:
-    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[0] == 0 or sums.shape[1] == 0 or sums.stride(1) != 1 and sums.shape[1] > 1:
-        raise ValueError(f"cluster sums must be a non-empty f32 matrix with contiguous rows, got {tuple(sums.shape)} {sums.dtype} strides {sums.stride()}")
-    n, d = sums.shape
-    return n, d, max(sums.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
-
-
 def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: torch.Tensor | None = None):
     """The nearest other cluster of every cluster under score(i, j) = <sums[i], sums[j]> (inv_count[i] inv_count[j]):
     sums f32 [n, d] read in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine),
     inv_count f32 [n] -> (nn int32 [n], best f32 [n]); exactly symmetric scores, lowest index among equal ones, bitwise reproducible.
     `ws`: a uint8 workspace of at least sd_ahc_nearest_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
     _need_cuda(sums, inv_count)
-    n, d, ld = _ahc_sums(sums)
+    n, d, ld = _rows_ld(sums, "cluster sums")
     inv_count = inv_count.contiguous().float()
     if inv_count.shape != (n,):
         raise ValueError(f"inv_count {tuple(inv_count.shape)} does not match the {n} cluster sums")
@@ -552,9 +558,7 @@ def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: torch.Tensor | 
     best = torch.empty((n,), dtype=torch.float32, device=sums.device)
     lib = N.load()
     with torch.cuda.device(sums.device):
-        need = int(lib.sd_ahc_nearest_workspace_bytes(n, d))
-        if ws is None or ws.numel() * ws.element_size() < need:
-            ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=sums.device)
+        ws = _workspace(ws, int(lib.sd_ahc_nearest_workspace_bytes(n, d)), sums.device)
         N.check(lib.sd_ahc_nearest_f32(sums.data_ptr(), ld, n, d, inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(),
                                        ws.numel() * ws.element_size(), _stream(sums)), "sd_ahc_nearest_f32")
     return nn, best
@@ -565,7 +569,7 @@ def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, 
     and its count into row i and refreshes inv_count[i] -> (target int32 [n]: i for the upper row of a pair, the row itself otherwise;
     n_merged int32 [1], still on the device)."""
     _need_cuda(sums, count, inv_count, nn, best)
-    n, d, ld = _ahc_sums(sums)
+    n, d, ld = _rows_ld(sums, "cluster sums")
     for name, t, dt in (("count", count, torch.float32), ("inv_count", inv_count, torch.float32), ("nn", nn, torch.int32),
                         ("best", best, torch.float32)):
         if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
@@ -580,30 +584,17 @@ def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)
 
-def _hdb_rows(rows: torch.Tensor) -> tuple[int, int, int]:
-    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] == 0 or rows.shape[1] == 0 or rows.stride(1) != 1 and rows.shape[1] > 1:
-        raise ValueError(f"rows must be a non-empty f32 matrix with contiguous rows, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
-    n, d = rows.shape
-    return n, d, max(rows.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
-
-
-def _hdb_ws(ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
-    return ws
-
-
 def hdb_core(rows: torch.Tensor, k: int, ws: torch.Tensor | None = None) -> torch.Tensor:
     """core[i] = the k-th largest <rows[i], rows[j]> over j != i, duplicates counted (1 <= k <= min(16, n - 1)): rows f32 [n, d] read
     in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine) -> f32 [n].  The products are
     those of `hdb_outgoing`, bit for bit.  `ws`: a uint8 workspace of at least sd_hdb_core_workspace_bytes(n, d, k) to reuse across
     calls (allocated when None)."""
     _need_cuda(rows)
-    n, d, ld = _hdb_rows(rows)
+    n, d, ld = _rows_ld(rows, "rows")
     core = torch.empty((n,), dtype=torch.float32, device=rows.device)
     lib = N.load()
     with torch.cuda.device(rows.device):
-        ws = _hdb_ws(ws, int(lib.sd_hdb_core_workspace_bytes(n, d, int(k))), rows.device)
+        ws = _workspace(ws, int(lib.sd_hdb_core_workspace_bytes(n, d, int(k))), rows.device)
         N.check(lib.sd_hdb_core_f32(rows.data_ptr(), ld, n, d, int(k), core.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
                                     _stream(rows)), "sd_hdb_core_f32")
     return core
@@ -615,7 +606,7 @@ def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws:
     best = -inf for a row whose component is everything.  Exactly symmetric w, lowest index among equal ones, bitwise reproducible.
     `ws`: a uint8 workspace of at least sd_hdb_outgoing_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
     _need_cuda(rows, core, comp)
-    n, d, ld = _hdb_rows(rows)
+    n, d, ld = _rows_ld(rows, "rows")
     for name, t, dt in (("core", core, torch.float32), ("comp", comp, torch.int32)):
         if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
@@ -623,7 +614,7 @@ def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws:
     best = torch.empty((n,), dtype=torch.float32, device=rows.device)
     lib = N.load()
     with torch.cuda.device(rows.device):
-        ws = _hdb_ws(ws, int(lib.sd_hdb_outgoing_workspace_bytes(n, d)), rows.device)
+        ws = _workspace(ws, int(lib.sd_hdb_outgoing_workspace_bytes(n, d)), rows.device)
         N.check(lib.sd_hdb_outgoing_f32(rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(),
                                         ws.data_ptr(), ws.numel() * ws.element_size(), _stream(rows)), "sd_hdb_outgoing_f32")
     return nn, best

@@ -187,6 +187,34 @@ def test_against_float64(dev, n):
         assert e_core <= bound and e_best <= bound and e_own <= bound
 
 
+TWIN_SHAPES = [(2, 1, 4), (129, 33, 36), (300, 192, 192)]      # (n, d, ld)
+
+
+@pytest.mark.parametrize("n,d,ld", TWIN_SHAPES)
+def test_outgoing_without_core_and_components_is_the_nearest_pass_of_ahc(dev, n, d, ld):
+    """The two files compute with one tile (csrc/sd_gram_tile.h): with core = +inf and every row a component of its own,
+    w = fminf(+inf, acc) = acc and every other row is a candidate; with inv_count = 1 the AHC score is acc · (1 · 1) = acc.  Both
+    sides are exact, so `nn` and the bits of `best` must agree.  (129, 33, 36) puts one row into the second row and column block,
+    ends d inside a group of four and pads the stride; 300 rows have diagonal, off-diagonal and partial tiles.  Rows of -2 .. 2 tie
+    everywhere (the lowest-index rule); unit rows round."""
+    from speech_diarization_amd import ops
+    ints = H.integer_rows(n, d, ld, seed=300 * n + d, lo=-2, hi=3)
+    unit = np.full((n, ld), np.nan, np.float32)
+    unit[:, :d] = H.unit_rows(np.random.default_rng(n + d).standard_normal((n, d)))
+    inf = torch.full((n,), INF, device=dev)
+    singles = torch.arange(n, dtype=torch.int32, device=dev)
+    ones = torch.ones((n,), device=dev)
+    for name, S in (("integer", ints), ("unit", unit)):
+        Sv = torch.from_numpy(S).to(dev)[:, :d]
+        with expect_launches(exactly=["hdb_outgoing_kernel", "hdb_outgoing_finish_kernel"]):
+            nn_h, best_h = ops.hdb_outgoing(Sv, inf, singles)
+        with expect_launches(exactly=["ahc_nearest_kernel", "ahc_nearest_finish_kernel"]):
+            nn_a, best_a = ops.ahc_nearest(Sv, ones)
+        assert torch.equal(nn_h, nn_a), f"nn {name} rows: {int((nn_h != nn_a).sum())} of {n} differ"
+        assert torch.equal(_bits(best_h), _bits(best_a)), f"best {name} rows: {int((_bits(best_h) != _bits(best_a)).sum())} of {n} differ"
+        assert bool((nn_h >= 0).all()) and bool((nn_h != singles).all())
+
+
 # ------------------------------------------------------------------ exact buffer sizes, guard bands
 
 EDGE_SHAPES = [(2, 4, 4), (3, 7, 8), (129, 190, 192), (300, 192, 192), (257, 190, 196)]      # (n, d, ld)

@@ -82,6 +82,26 @@ def test_workspace_formulas():
         assert int(lib.sd_hdb_core_workspace_bytes(n, d, k)) == 0, (n, d, k)
 
 
+# ------------------------------------------------------------------ one statement of the tile
+
+def test_the_gram_tile_is_stated_once():
+    """`<a, b>` and `<b, a>` are the same bits in the AHC and the HDBSCAN kernels because both call the tile, the loads and the
+    tie rule of csrc/sd_gram_tile.h: neither file issues the f32 MFMA itself or defines a `load4` / `take` of its own.  sd_affinity.hip,
+    whose exact-f32 step stages differently and legitimately has its own, shows that the search finds the builtin where it is."""
+    csrc = N.PKG_DIR / "csrc"
+    mfma = "__builtin_amdgcn_mfma_f32_16x16x4f32"
+    own = re.compile(r"^[^\n;]*\b\w*(?:load4|take)\s*\([^;{]*\)\s*\{", re.M)      # a definition, not a call
+    header = (csrc / "sd_gram_tile.h").read_text()
+    assert mfma in header and "__global__" not in header
+    assert {m.group(0).split("(")[0].split()[-1] for m in own.finditer(header)} == {"gt_load4", "gt_take"}
+    for name in ("sd_ahc.hip", "sd_hdbscan.hip"):
+        text = (csrc / name).read_text()
+        assert mfma not in text, name
+        assert not own.search(text), (name, own.search(text).group(0))
+        assert '#include "sd_gram_tile.h"' in text and "gt_tile(" in text, name
+    assert mfma in (csrc / "sd_affinity.hip").read_text()
+
+
 # ------------------------------------------------------------------ refusals before launch (no device needed: fake non-null pointers)
 
 def _core(lib, rows=0x1000, ld=192, n=100, d=192, k=2, core=0x2000, ws=0x5000, ws_bytes=None):

@@ -1,9 +1,9 @@
 """Time the device HDBSCAN route on the GPU -> profiles/hdbscan_timing.json.
 
 * Kernel cost at N = 7609 and N = 50000 (d = 192, planted unit rows): one `sd_hdb_outgoing_f32` pass with all-singleton components
-  beside one `sd_ahc_nearest_f32` pass at the same shape in the same process (csrc/sd_ahc.hip is the parent commit's file, byte for
-  byte, so this IS the parent's pass), their ratio against the bar of 1.25, and the core pass (`sd_hdb_core_f32`, k = 1 and 2: a
-  full-Gram pass) beside them.  Device events, median of 5 windows of `reps` calls after 3 warm-up calls.
+  beside one `sd_ahc_nearest_f32` pass at the same shape in the same process (both run the one tile and argmax of
+  csrc/sd_gram_tile.h), their ratio against the bar of 1.25, and the core pass (`sd_hdb_core_f32`, k = 1 and 2: a full-Gram pass)
+  beside them.  Device events, median of 5 windows of `reps` calls after 3 warm-up calls.
 * End to end at N = 7609 (a 1 h meeting at 2 s / 0.25 s windows; 8 planted speakers): `hdbscan_rows` at (2, None, True) "euclidean"
   and at (6, 3, False) "cosine", each the median of 5 clusterings after a warm-up one, with the rounds, the ms inside the kernels
   (device events around every operator call) and the ms of the host tree step (scikit-learn's `_process_mst` + `tree_to_labels`);
