@@ -31,6 +31,12 @@ def _hipcc() -> str:
     return exe
 
 
+def compile_flags() -> list[str]:
+    """hipcc and the flags every source is compiled with (tools/isa_diff.py compiles with the same)"""
+    return [_hipcc(), f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC",
+            "-fno-gpu-rdc", f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-function"]
+
+
 def _fingerprint() -> str:
     h = hashlib.sha256()
     files = sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.h")) + sorted(INCLUDE.glob("*.h"))
@@ -56,10 +62,7 @@ def build(force: bool = False, verbose: bool = False, stamp: bool = False, varia
         return LIB_PATH
     obj_dir = CSRC / "obj"
     obj_dir.mkdir(exist_ok=True)
-    common = [
-        _hipcc(), f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC",
-        "-fno-gpu-rdc", f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-function",
-    ]
+    common = compile_flags()
     if stamp:
         common.append("-DSD_STAMP")
     procs = []
@@ -93,8 +96,7 @@ def _build_variant(name: str, cflags: str, verbose: bool) -> Path:
     obj_dir = CSRC / "obj" / f"v_{name}"
     out_dir.mkdir(exist_ok=True)
     obj_dir.mkdir(parents=True, exist_ok=True)
-    common = [_hipcc(), f"--offload-arch={OFFLOAD_ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", f"-I{INCLUDE}", f"-I{CSRC}",
-              "-Wall", "-Wno-unused-function"] + cflags.split()
+    common = compile_flags() + cflags.split()
     procs, objs = [], []
     for src in SOURCES:
         obj = obj_dir / (Path(src).stem + ".o")

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sd_common.h"
+#include "sd_conv_tile.h"
 
 namespace {
 
@@ -35,10 +36,6 @@ constexpr int AF_OPER = AF_T * AF_ROW;       // 16 KB: one operand of one K step
 constexpr int AF_STAGE = 2 * AF_OPER;        // rows of the tile's row block, then of its column block
 constexpr int AF_LDS = 2 * AF_STAGE;         // 64 KB: two workgroups per CU
 constexpr int AF_SUP = 8;                    // super-tile edge in tiles
-
-#define AF_GLDS16(gptr, lptr)                                                              \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 __device__ __forceinline__ float af_dpp_xor1(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
@@ -61,20 +58,6 @@ __device__ __forceinline__ f32x4 af_quad_transpose(f32x4 v, int b) {
     if (o2) { v[0] = g0; v[1] = g1; } else { v[2] = g0; v[3] = g1; }
   }
   return v;
-}
-
-// a <-> b on one lane bit: odd 16-lane rows of a trade with the even rows of b / the upper 32 lanes of a with the lower 32 of b
-__device__ __forceinline__ void af_swap16(float& a, float& b) {
-  const auto w = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-  const unsigned w0 = w[0], w1 = w[1];       // (a bit_cast applied to the vector ELEMENT reads element 0 for both: hipcc 7.2)
-  a = __builtin_bit_cast(float, w0);
-  b = __builtin_bit_cast(float, w1);
-}
-__device__ __forceinline__ void af_swap32(float& a, float& b) {
-  const auto w = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-  const unsigned w0 = w[0], w1 = w[1];       // (a bit_cast applied to the vector ELEMENT reads element 0 for both: hipcc 7.2)
-  a = __builtin_bit_cast(float, w0);
-  b = __builtin_bit_cast(float, w1);
 }
 
 __device__ __forceinline__ void af_store4(float* p, f32x4 v) {
@@ -179,10 +162,10 @@ __device__ __forceinline__ void af_epilogue(const f32x4 (&acc)[4][4], bool diag,
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        af_swap16(t[0][c], t[1][c]);
-        af_swap16(t[2][c], t[3][c]);
-        af_swap32(t[0][c], t[2][c]);
-        af_swap32(t[1][c], t[3][c]);
+        sd_swap16(t[0][c], t[1][c]);
+        sd_swap16(t[2][c], t[3][c]);
+        sd_swap32(t[0][c], t[2][c]);
+        sd_swap32(t[1][c], t[3][c]);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {                       // t[r]: row 16 i + 4 r + qb, columns 16 fq + 4 qa .. + 3
@@ -242,12 +225,7 @@ __global__ __launch_bounds__(256, 2) void affinity_sym_kernel(const char* __rest
   const int wm = wid >> 1, wn = wid & 1;
 
   // workgroup -> tile: XCD blockIdx % 8 walks a contiguous eighth of the super-tiles, 64 consecutive workgroups each
-  int wg;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
+  const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
   int tile_m, tile_n;
   if (!af_tile_of(wg >> 6, wg & 63, nsup, nt, tile_m, tile_n)) return;       // workgroup-uniform: below the diagonal or past the edge
 
@@ -279,12 +257,12 @@ __global__ __launch_bounds__(256, 2) void affinity_sym_kernel(const char* __rest
 #endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      AF_GLDS16(pa[i], base + i * 32 * AF_ROW);
+      SD_GLDS16(pa[i], base + i * 32 * AF_ROW);
       pa[i] += AF_ROW;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      AF_GLDS16(pb[i], base + AF_OPER + i * 32 * AF_ROW);
+      SD_GLDS16(pb[i], base + AF_OPER + i * 32 * AF_ROW);
       pb[i] += AF_ROW;
     }
   };

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "sd_common.h"
+#include "sd_conv_tile.h"
 #include "sd_epilogue.h"
 
 namespace {
@@ -38,10 +39,6 @@ static_assert(BM * LDC <= 2 * (BM + BN) * LDP, "C tile must fit in the operand s
 #ifdef SD_STAMP
 __device__ unsigned long long sd_c32_stamp_buf[8192 * 10];
 #endif
-
-#define SD_GLDS16_F32(gptr, lptr)                                                          \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 // one 128x128 output tile.  DMA = true: the operand stage is written by LDS-DMA
 // (global_load_lds_dwordx4, no VGPR staging and no ds_write phase).  DMA rows are 128 bytes with no
@@ -112,15 +109,11 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
     for (int i = 0; i < 4; ++i) {
       int tt = a_t[i] + delta;
       if constexpr (PACKED) {
-        const int Ts = a_len[i];
-        tt = tt < 0 ? -tt : tt;
-        tt = tt >= Ts ? 2 * (Ts - 1) - tt : tt;
-        int r = a_seg[i] + tt;
+        int r = a_seg[i] + sd_reflect(tt, a_len[i]);
         r = r < 0 ? 0 : (r >= p.M ? p.M - 1 : r);
         aptr[i] = X + (size_t)r * p.lda;
       } else {
-        tt = tt < 0 ? -tt : tt;
-        tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+        tt = sd_reflect(tt, p.T);
         aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
       }
     }
@@ -165,9 +158,9 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
     const int acol = col < p.cin ? col : 0;
 #pragma unroll
     for (int i = i0; i < i1; ++i) {
-      SD_GLDS16_F32(aptr[i] + acol, As + buf * BM * BK + (32 * i + 8 * wid) * BK);
+      SD_GLDS16(aptr[i] + acol, As + buf * BM * BK + (32 * i + 8 * wid) * BK);
       if (i < NBI) {
-        SD_GLDS16_F32(wptr[i] + gchunk, Bs + buf * TBN * BK + (32 * i + 8 * wid) * BK);
+        SD_GLDS16(wptr[i] + gchunk, Bs + buf * TBN * BK + (32 * i + 8 * wid) * BK);
         wptr[i] += BK;
       }
     }
@@ -273,19 +266,7 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
   // read of the operand stage), then sd_store_tile applies bias / activation / BN affine and
   // issues 16-byte row-contiguous stores (sd_epilogue.h)
   float* Cs = smem;
-  const int hrow = (lane >> 5) * 4;
-#pragma unroll
-  for (int ni = 0; ni < NJ; ++ni) {
-    const int cl = wn * 32 * NJ + ni * 32 + (lane & 31);
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + hrow;
-        Cs[rl * TLDC + cl] = acc[mi][ni][r];
-      }
-    }
-  }
+  SD_ACC32_TO_TILE(Cs, TLDC, wm * 64, wn * 32 * NJ, 2, NJ, lane, acc[mi][ni][r]);
 #ifdef SD_STAMP
   __builtin_amdgcn_s_waitcnt(0xC07F);
   const unsigned long long t_e1 = __builtin_amdgcn_s_memtime();
@@ -349,12 +330,12 @@ template <bool DMA>
 __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const sd_conv_args p, const int vec, const int order, const int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int n_tiles = (p.cout + BN - 1) / BN;
-  const int q = ntiles >> 3, r = ntiles & 7, xcd = blockIdx.x & 7;
-  const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;   // this XCD's logical tiles
+  const int xcd = blockIdx.x & 7;
+  const int first = sd_xcd_first(blockIdx.x, ntiles);                         // this XCD's logical tiles
   const int peers = ((int)gridDim.x - xcd + 7) >> 3;                          // workgroups dealt to this XCD
   const int m_tiles = ntiles / n_tiles;
   const int start = order == 0 ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
-  const int count = order == 0 ? ntiles : q + (xcd < r ? 1 : 0);
+  const int count = order == 0 ? ntiles : sd_xcd_count(blockIdx.x, ntiles);
   const int step = order == 0 ? (int)gridDim.x : peers;
   for (int i = start; i < count; i += step) {      // (one call site: the tile body is inlined once)
     int tm, tn;
@@ -419,8 +400,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_vh_kernel(const sd_conv_
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int n_tiles = (p.cout + BN - 1) / BN;
   int wg;
-  {                                           // workgroups b, b + 8, ... (one XCD) take consecutive tiles, column tile fastest
-    const int nwg = gridDim.x, b = blockIdx.x;
+  {                                           // sd_xcd_tile(blockIdx.x, gridDim.x) (sd_conv_tile.h), kept as this kernel's own text: through
+    const int nwg = gridDim.x, b = blockIdx.x;   // the helper the three instantiations get another register assignment (tools/isa_diff.py)
     const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
     wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
   }
@@ -455,8 +436,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_vh_kernel(const sd_conv_
 #pragma unroll
     for (int i = 0; i < NAI; ++i) {
       int tt = a_t[i] + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+      tt = sd_reflect(tt, p.T);
       aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
     }
   };
@@ -468,10 +448,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_vh_kernel(const sd_conv_
 #pragma unroll
     for (int i = 0; i < NAI; ++i)
       if (32 * i + 8 * wid < VM)              // wave-uniform: this wave's 8 rows of slot i exist
-        SD_GLDS16_F32(aptr[i] + acol, As + buf * VM * BK + (32 * i + 8 * wid) * BK);
+        SD_GLDS16(aptr[i] + acol, As + buf * VM * BK + (32 * i + 8 * wid) * BK);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      SD_GLDS16_F32(wptr[i], Bs + buf * BN * BK + (32 * i + 8 * wid) * BK);
+      SD_GLDS16(wptr[i], Bs + buf * BN * BK + (32 * i + 8 * wid) * BK);
       wptr[i] += BK;
     }
     ld_c0 += BK;
@@ -542,9 +522,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_vh_kernel(const sd_conv_
 __global__ __launch_bounds__(256, 3) void conv_gemm_f32_n64_kernel(const sd_conv_args p, const int vec) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int n_tiles = (p.cout + 63) / 64;
-  const int nwg = gridDim.x, b = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+  const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
   const int tm = wg / n_tiles;
   conv_tile_f32<true, 1>(p, vec, tm, wg - tm * n_tiles, smem);
 }
@@ -585,12 +563,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f32_t256_kernel(const sd_con
   const int wm = wid >> 2, wn = wid & 3;
 
   const int n_tiles = (p.cout + WBN - 1) / WBN;
-  int wg;
-  {                                          // XCD-aware: workgroups b, b + 8, ... (one XCD) take consecutive tiles
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
+  const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
   const int tile_n = wg % n_tiles;
   const int tile_m = wg / n_tiles;
   const int m0 = tile_m * WBM, n0 = tile_n * WBN;
@@ -615,8 +588,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f32_t256_kernel(const sd_con
       m = m < p.M ? m : p.M - 1;
       const int seg = (m / p.T) * p.T;
       int tt = m - seg + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+      tt = sd_reflect(tt, p.T);
       ptr[i] = X + (size_t)(seg + tt) * p.lda;
     }
   };
@@ -637,7 +609,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f32_t256_kernel(const sd_con
     char* base = dst + W_B_BASE + st * W_B_STAGE;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      SD_GLDS16_F32(ptr[i], base + i * 32 * W_ROW);
+      SD_GLDS16(ptr[i], base + i * 32 * W_ROW);
       ptr[i] += WBK;
     }
   };
@@ -646,7 +618,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f32_t256_kernel(const sd_con
     const int col = ld_c0 + ls4;
     const int acol = col < p.cin ? col : 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) SD_GLDS16_F32(ptr[i] + acol, base + i * 32 * W_ROW);
+    for (int i = 0; i < 8; ++i) SD_GLDS16(ptr[i] + acol, base + i * 32 * W_ROW);
     ld_c0 += WBK;
     if (ld_c0 >= p.cin_pad) {
       ld_c0 = 0;
@@ -720,6 +692,8 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f32_t256_kernel(const sd_con
 #pragma unroll
   for (int hm = 0; hm < 2; ++hm) {
     if (wm == hm) {
+      // SD_ACC32_TO_TILE(Cs, WBN, 0, wn * 64, 4, 2, lane, acc[mi][ni][r]) (sd_conv_tile.h), kept as this kernel's own text: the headline kernel's
+      // device code does not move (tools/isa_diff.py: through the macro the register allocation of the whole kernel changes)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int cl = wn * 64 + j * 32 + fn;
@@ -770,8 +744,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_f32_kernel(const sd_conv_args
   const int half = p.taps / 2;
   for (int tap = 0; tap < p.taps; ++tap) {
     int tt = t + (tap - half) * p.dil;
-    tt = tt < 0 ? -tt : tt;
-    tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+    tt = sd_reflect(tt, p.T);
     const float* xa = X + (size_t)(seg + tt) * p.lda;
     const float* wt = wb + (size_t)tap * p.cin_pad;
 #pragma unroll 4
@@ -784,8 +757,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_f32_kernel(const sd_conv_args
     }
   }
   float* mine = red + wid * SK_T * SK_LD;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mine[((i & 3) + 8 * (i >> 2) + 4 * h) * SK_LD + r] = acc[i];
+  SD_ACC32_TO_TILE(mine, SK_LD, 0, 0, 1, 1, lane, acc[r]);
   __syncthreads();
   // 1024 outputs / 256 threads: thread -> row tid / 8, columns 4 * (tid % 8) .. +3
   const int row = tid >> 3, c0 = (tid & 7) * 4;
@@ -847,8 +819,7 @@ __global__ __launch_bounds__(256) void seg_gemm_partial_f32_kernel(const sd_conv
     for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
   }
   float* mine = red + wid * SK_T * SK_LD;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) mine[((i & 3) + 8 * (i >> 2) + 4 * h) * SK_LD + r] = acc[i];
+  SD_ACC32_TO_TILE(mine, SK_LD, 0, 0, 1, 1, lane, acc[r]);
   __syncthreads();
   const int row = tid >> 3, c0 = (tid & 7) * 4;
   f32x4 v;
@@ -944,8 +915,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_s64_kernel(const sd_conv
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       int tt = a_t[i] + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+      tt = sd_reflect(tt, p.T);
       aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
     }
   };
@@ -957,10 +927,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_s64_kernel(const sd_conv
     const int col = ld_c0 + gchunk;
     const int acol = col < p.cin ? col : 0;        // columns past cin meet zero weights
 #pragma unroll
-    for (int i = 0; i < NA; ++i) SD_GLDS16_F32(aptr[i] + acol, As + (32 * i + 8 * wid) * BK);
+    for (int i = 0; i < NA; ++i) SD_GLDS16(aptr[i] + acol, As + (32 * i + 8 * wid) * BK);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      SD_GLDS16_F32(wptr[i], Bs + (32 * i + 8 * wid) * BK);
+      SD_GLDS16(wptr[i], Bs + (32 * i + 8 * wid) * BK);
       wptr[i] += BK;
     }
     ld_c0 += BK;
@@ -1023,8 +993,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f32_s64_kernel(const sd_conv
   const unsigned long long t_loop = __builtin_amdgcn_s_memtime();
 #endif
   float* Cs = smem;
-  {
-    const int cl = wn * 32 + (lane & 31), hrow = (lane >> 5) * 4;
+  {                                                // SD_ACC32_TO_TILE(mine, LDCS, wm * 32, wn * 32, 1, 1, lane, acc[r]) (sd_conv_tile.h), kept as this
+    const int cl = wn * 32 + (lane & 31), hrow = (lane >> 5) * 4;      // kernel's own text: through the macro <32> differs in 8 lines (tools/isa_diff.py)
     float* mine = Cs + kh * TM * LDCS;             // (TM = 32: the second K half's partial tile behind the first's)
 #pragma unroll
     for (int r = 0; r < 16; ++r) mine[(wm * 32 + (r & 3) + 8 * (r >> 2) + hrow) * LDCS + cl] = acc[r];
@@ -1081,6 +1051,13 @@ constexpr long S64_DEFAULT = 128L;
 std::atomic<long> g_s64_below{tune_env("SD_S64_TILES", S64_DEFAULT)};
 std::atomic<long> g_half_tiles{tune_env("SD_F32_N64", -1L)};     // -1: by the rule; 0 never; 1 whenever possible
 std::atomic<long> g_tile_rows{tune_env("SD_F32_TILE_ROWS", -1L)};  // -1: by the rule; 0: 128-row tiles only; 80 / 96 / 112: that height whenever possible
+
+// conv_gemm_f32_vh_kernel<J> by J - 5: tiles of 16 J = 80 / 96 / 112 rows, two stages of (16 J + BN) staged rows
+struct VhKernel { void (*fn)(sd_conv_args, int); const char* label; size_t lds; };
+constexpr size_t vh_lds(int j) { return (size_t)2 * (16 * j + BN) * BK * sizeof(float); }
+const VhKernel g_vh_kernels[3] = {{conv_gemm_f32_vh_kernel<5>, "conv_gemm_f32_vh_kernel<5>", vh_lds(5)},
+                                  {conv_gemm_f32_vh_kernel<6>, "conv_gemm_f32_vh_kernel<6>", vh_lds(6)},
+                                  {conv_gemm_f32_vh_kernel<7>, "conv_gemm_f32_vh_kernel<7>", vh_lds(7)}};
 }  // namespace
 
 extern "C" int sd_set_tuning(int key, long value) {
@@ -1172,7 +1149,8 @@ int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec) {
   return SD_OK;
 }
 
-static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool symmetric, int* stat_rows) {
+static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream_, bool symmetric, int* stat_rows) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f32: null args");
   SD_CHECK_ARG(a->w_dtype == SD_DT_F32, "sd_conv1d_cl_f32: w_dtype %d not supported by the f32 operator", a->w_dtype);
   SD_CHECK_ARG(a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_f32: x/y must be f32 (use sd_conv1d_cl_f16 for f16 activations)");
@@ -1193,13 +1171,8 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
     const size_t lds64 = (size_t)S64_ST * S64_STAGE * sizeof(float);
     static const int s32 = [] { const char* e = sd_experiment_env("SD_S64_HALF"); return e ? atoi(e) : -1; }();   // 0 | 1: never / always 32-row tiles
     const bool half = s32 != 0 && (s32 == 1 || g < 128);
-    if (half) {
-      SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_s64_kernel<32>), (int)lds64));
-      hipLaunchKernelGGL(conv_gemm_f32_s64_kernel<32>, dim3((unsigned)(((a->M + 31) / 32) * nt64)), dim3(256), lds64, static_cast<hipStream_t>(stream), *a, vec);
-    } else {
-      SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_s64_kernel<64>), (int)lds64));
-      hipLaunchKernelGGL(conv_gemm_f32_s64_kernel<64>, dim3((unsigned)g), dim3(256), lds64, static_cast<hipStream_t>(stream), *a, vec);
-    }
+    if (half) SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_s64_kernel<32>, -1, 0.0, ((a->M + 31) / 32) * nt64, 256, lds64, stream, *a, vec));
+    else SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_s64_kernel<64>, -1, 0.0, g, 256, lds64, stream, *a, vec));
     SD_CHECK_LAUNCH(half ? "conv_gemm_f32_s64_kernel<32>" : "conv_gemm_f32_s64_kernel<64>");
     return SD_OK;
   }
@@ -1207,7 +1180,7 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
   if (!a->colstat && tiles_m * tiles_n < skinny_below) {
     const long g = (long)((a->M + SK_T - 1) / SK_T) * ((a->cout + SK_T - 1) / SK_T);
     // (not counted in the SD_PROF_CONV_GEMM roofline figures: a different kernel, 0.2 % of the flops)
-    hipLaunchKernelGGL(skinny_gemm_f32_kernel, dim3((unsigned)g), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+    SD_CHECK_HIP(sd_launch_conv(skinny_gemm_f32_kernel, -1, 0.0, g, 256, 0, stream, *a));
     SD_CHECK_LAUNCH("skinny_gemm_f32_kernel");
     return SD_OK;
   }
@@ -1217,12 +1190,7 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
   {
     const long t256 = ((a->M + WBM - 1) / WBM) * ((a->cout + WBN - 1) / WBN);
     if (wide_ok && !symmetric && a->cout >= 1024 && t256 >= g_wide_from.load(std::memory_order_relaxed) && t256 > 0 && !(a->tee && a->tee_add) && !(a->colstat && a->T < 128)) {
-      SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_t256_kernel), W_LDS_BYTES));
-      {
-        SdProfScope prof(SD_PROF_CONV_WIDE, static_cast<hipStream_t>(stream),
-                         2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-        hipLaunchKernelGGL(conv_gemm_f32_t256_kernel, dim3((unsigned)t256), dim3(512), W_LDS_BYTES, static_cast<hipStream_t>(stream), *a, vec);
-      }
+      SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_t256_kernel, SD_PROF_CONV_WIDE, sd_conv_flops(a), t256, 512, W_LDS_BYTES, stream, *a, vec));
       SD_CHECK_LAUNCH("conv_gemm_f32_t256_kernel");
       return SD_OK;
     }
@@ -1253,30 +1221,16 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
         }
       if (best) {
         const long tj = ((a->M + 16 * best - 1) / (16 * best)) * tiles_n;
-        const size_t ldsv = (size_t)2 * (16 * best + BN) * BK * sizeof(float);
-        const void* fn = best == 5 ? reinterpret_cast<const void*>(conv_gemm_f32_vh_kernel<5>)
-                       : best == 6 ? reinterpret_cast<const void*>(conv_gemm_f32_vh_kernel<6>) : reinterpret_cast<const void*>(conv_gemm_f32_vh_kernel<7>);
-        SD_CHECK_HIP(sd_func_max_lds(fn, (int)ldsv));
-        {
-          SdProfScope prof(SD_PROF_CONV_GEMM, static_cast<hipStream_t>(stream), 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-          const dim3 grid((unsigned)tj), block(256);
-          hipStream_t hs = static_cast<hipStream_t>(stream);
-          if (best == 5) hipLaunchKernelGGL(conv_gemm_f32_vh_kernel<5>, grid, block, ldsv, hs, *a, vec);
-          else if (best == 6) hipLaunchKernelGGL(conv_gemm_f32_vh_kernel<6>, grid, block, ldsv, hs, *a, vec);
-          else hipLaunchKernelGGL(conv_gemm_f32_vh_kernel<7>, grid, block, ldsv, hs, *a, vec);
-        }
-        SD_CHECK_LAUNCH(best == 5 ? "conv_gemm_f32_vh_kernel<5>" : best == 6 ? "conv_gemm_f32_vh_kernel<6>" : "conv_gemm_f32_vh_kernel<7>");
+        const VhKernel& k = g_vh_kernels[best - 5];
+        SD_CHECK_HIP(sd_launch_conv(k.fn, SD_PROF_CONV_GEMM, sd_conv_flops(a), tj, 256, k.lds, stream, *a, vec));
+        SD_CHECK_LAUNCH(k.label);
         if (stat_rows) *stat_rows = 16 * best;
         return SD_OK;
       }
     }
     if (can && n64 != 0 && (n64 == 1 || cost64 < 0.97 * cost128)) {
       const size_t lds64 = (size_t)2 * (BM + 64) * BK * sizeof(float);
-      SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_n64_kernel), (int)lds64));
-      {
-        SdProfScope prof(SD_PROF_CONV_GEMM, static_cast<hipStream_t>(stream), 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-        hipLaunchKernelGGL(conv_gemm_f32_n64_kernel, dim3((unsigned)t64), dim3(256), lds64, static_cast<hipStream_t>(stream), *a, vec);
-      }
+      SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_n64_kernel, SD_PROF_CONV_GEMM, sd_conv_flops(a), t64, 256, lds64, stream, *a, vec));
       SD_CHECK_LAUNCH("conv_gemm_f32_n64_kernel");
       return SD_OK;
     }
@@ -1287,8 +1241,6 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
     return e ? atoi(e) : SD_F32_DMA_DEFAULT;
   }();
   const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);   // the C tile of the epilogue needs BM * LDC <= this
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_kernel<false>), (int)lds));
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_kernel<true>), (int)lds));
   static const int order = [] {
     const char* e = sd_experiment_env("SD_TILE_ORDER");
     return e ? atoi(e) : 1;
@@ -1300,24 +1252,16 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
     const char* e = sd_experiment_env("SD_PERSIST");
     return e ? atoi(e) : 0;
   }();
-  {
-    SdProfScope prof(SD_PROF_CONV_GEMM, static_cast<hipStream_t>(stream),
-                     2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    long ntiles = tiles_m * tiles_n;
-    int ord = order;
-    if (symmetric && tiles_n >= 2) {                      // the list of band entries (see the kernel)
-      ntiles = 0;
-      for (long b = 0; 8 * b < tiles_n; ++b) ntiles += (tiles_n - 8 * b < 8 ? tiles_n - 8 * b : 8) * (tiles_n - 8 * b);
-      ord = 2;
-    }
-    const long grid = (persist > 0 && ntiles > persist) ? persist : ntiles;
-    if (dma)
-      hipLaunchKernelGGL(conv_gemm_f32_kernel<true>, dim3((unsigned)grid), dim3(256), lds,
-                         static_cast<hipStream_t>(stream), *a, vec, ord, (int)ntiles);
-    else
-      hipLaunchKernelGGL(conv_gemm_f32_kernel<false>, dim3((unsigned)grid), dim3(256), lds,
-                         static_cast<hipStream_t>(stream), *a, vec, ord, (int)ntiles);
+  long ntiles = tiles_m * tiles_n;
+  int ord = order;
+  if (symmetric && tiles_n >= 2) {                        // the list of band entries (see the kernel)
+    ntiles = 0;
+    for (long b = 0; 8 * b < tiles_n; ++b) ntiles += (tiles_n - 8 * b < 8 ? tiles_n - 8 * b : 8) * (tiles_n - 8 * b);
+    ord = 2;
   }
+  const long grid = (persist > 0 && ntiles > persist) ? persist : ntiles;
+  SD_CHECK_HIP(sd_launch_conv(dma ? conv_gemm_f32_kernel<true> : conv_gemm_f32_kernel<false>, SD_PROF_CONV_GEMM, sd_conv_flops(a), grid, 256, lds, stream, *a, vec,
+                              ord, (int)ntiles));
   // (the register-staged form only under SD_F32_DMA=0, read through sd_experiment_env above)
   SD_CHECK_LAUNCH(dma ? (symmetric ? "conv_gemm_f32_kernel<dma>/symmetric" : "conv_gemm_f32_kernel<dma>")
                       : (symmetric ? "conv_gemm_f32_kernel<reg>/symmetric" : "conv_gemm_f32_kernel<reg>"));
@@ -1326,7 +1270,8 @@ static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool sy
 
 // Packed spans: the position-dependent layers (taps > 1: reflect padding inside the span; a per-segment bias: the span's row) on the
 // 128x128 kernel's packed form, whatever sd_set_tuning selects for uniform launches (no other kernel has the span map).  a->T is ignored.
-extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream) {
+extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_packed_f32: null args");
   SD_CHECK_ARG(B >= 1 && frame_start_dev != nullptr, "sd_conv1d_cl_packed_f32: B=%d, frame_start %p", B, (const void*)frame_start_dev);
   SD_CHECK_ARG(a->w_dtype == SD_DT_F32 && a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_packed_f32: x / w / y must be f32");
@@ -1335,12 +1280,7 @@ extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_s
   const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
   SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_packed_f32: grid too large");
   const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);     // as the uniform launch: the epilogue's C tile needs BM * LDC
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(conv_gemm_f32_packed_kernel), (int)lds));
-  {
-    SdProfScope prof(SD_PROF_CONV_GEMM, static_cast<hipStream_t>(stream), 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    hipLaunchKernelGGL(conv_gemm_f32_packed_kernel, dim3((unsigned)tiles), dim3(256), lds, static_cast<hipStream_t>(stream), *a, vec,
-                       frame_start_dev, B);
-  }
+  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_packed_kernel, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles, 256, lds, stream, *a, vec, frame_start_dev, B));
   SD_CHECK_LAUNCH("conv_gemm_f32_packed_kernel");
   return SD_OK;
 }

@@ -14,6 +14,7 @@
 // 16*kk + 8h, exactly the A/B fragment of the 32x32x16 MFMA).  Workgroup ids are remapped so
 // the n-tiles that share an A row panel run on one XCD and find it in that XCD's L2.
 #include "sd_common.h"
+#include "sd_conv_tile.h"
 #include "sd_epilogue.h"
 #include <cstdlib>
 
@@ -46,177 +47,37 @@ __device__ __forceinline__ h8 load_a8<float>(const float* p) {
   return r;
 }
 
+// What the two register-staged 128x128 kernels differ in.  A K step is one 128-byte LDS row per operand row (BK halfs):
+//   RegF16<TA>: 64 values of both operands as f16 (activations f16, or f32 converted while staging);
+//   RegSplit16: 32 f32 values, split while staging into [hi x 32 | lo x 32], against SD_DT_SPLIT16 weights that lie that way in memory.
+template <typename TA_>
+struct RegF16 {
+  using TA = TA_;
+  using AVec = h8;                            // what a thread holds of one activation row between the fetch and the LDS write
+  static constexpr bool SPLIT = false;
+  static constexpr int KV = BK;               // values per K step
+  static constexpr int AV = 8;                // activation values per thread and row
+  static __device__ __forceinline__ AVec load_a(const TA* p) { return load_a8<TA>(p); }
+};
+struct RegSplit16 {
+  using TA = float;
+  using AVec = f32x4;
+  static constexpr bool SPLIT = true;
+  static constexpr int KV = 32;
+  static constexpr int AV = 4;
+  static __device__ __forceinline__ AVec load_a(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+};
+
 template <typename TA, typename TO>
 __global__ __launch_bounds__(256, 2) void conv_gemm_f16_kernel(const sd_conv_args p, const int vec) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  _Float16* As = reinterpret_cast<_Float16*>(smem_raw);  // [2][BM][LDP]
-  _Float16* Bs = As + 2 * BM * LDP;                       // [2][BN][LDP]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-
-  // XCD-aware, bijective remap: consecutive tiles (n fastest: they share the A row panel) go
-  // to one XCD instead of being dealt round-robin over the eight L2s
-  const int n_tiles = (p.cout + BN - 1) / BN;
-  int wg;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
-  const int tile_n = wg % n_tiles;
-  const int tile_m = wg / n_tiles;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  // staging role: 8 threads per 64-half row, 4 rows per thread; all loads unconditional
-  // (rows/channels past the end clamp to the last valid one and are never stored, columns past
-  // cin re-read column 0 against the zero-filled weight padding)
-  const int c8 = tid & 7;
-  const int r0 = tid >> 3;
-  int a_seg[4], a_t[4];
-  const _Float16* wptr[4];
-  const TA* aptr[4];
-  const int ktot = p.taps * p.cin_pad;
-  const _Float16* W = static_cast<const _Float16*>(p.w);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int m = m0 + r0 + 32 * i;
-    m = m < p.M ? m : p.M - 1;
-    const int seg = (m / p.T) * p.T;
-    a_seg[i] = seg;
-    a_t[i] = m - seg;
-    int n = n0 + r0 + 32 * i;
-    n = n < p.cout ? n : p.cout - 1;
-    wptr[i] = W + (size_t)n * ktot + c8 * 8;
-  }
-  const int nk = p.taps * (p.cin_pad / BK);
-  const int half = p.taps / 2;
-  const TA* X = static_cast<const TA*>(p.x) + p.a_col0;
-
-  auto set_tap = [&](int tap) {
-    const int delta = (tap - half) * p.dil;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int tt = a_t[i] + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
-      aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
-    }
-  };
-
-  // Two register stages: the fetch runs TWO K steps ahead of the MFMAs (one step is only ~0.2 us of
-  // matrix work, far less than an HBM/L2 round trip), the LDS stage one step ahead.
-  struct Stage { h8 a[4], b[4]; };
-  Stage s0, s1;
-  int ld_tap = 0, ld_c0 = 0;
-  set_tap(0);
-  auto gload = [&](Stage& st) {
-    const int col = ld_c0 + c8 * 8;
-    const int acol = col < p.cin ? col : 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      st.a[i] = load_a8<TA>(aptr[i] + acol);
-      st.b[i] = *reinterpret_cast<const h8*>(wptr[i]);
-      wptr[i] += BK;
-    }
-    ld_c0 += BK;
-    if (ld_c0 >= p.cin_pad) {
-      ld_c0 = 0;
-      ++ld_tap;
-      if (ld_tap < p.taps) set_tap(ld_tap);
-    }
-  };
-  auto lstore = [&](const Stage& st, int buf) {
-    _Float16* a = As + buf * BM * LDP;
-    _Float16* b = Bs + buf * BN * LDP;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      *reinterpret_cast<h8*>(a + (r0 + 32 * i) * LDP + c8 * 8) = st.a[i];
-      *reinterpret_cast<h8*>(b + (r0 + 32 * i) * LDP + c8 * 8) = st.b[i];
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int frag_row = lane & 31;
-  const int frag_k = (lane >> 5) * 8;
-
-  struct Frag { h8 a0, a1, b0, b1; };
-  auto fread = [&](const _Float16* a, const _Float16* b, int kk) {
-    Frag f;
-    f.a0 = *reinterpret_cast<const h8*>(a + kk * 16);
-    f.a1 = *reinterpret_cast<const h8*>(a + 32 * LDP + kk * 16);
-    f.b0 = *reinterpret_cast<const h8*>(b + kk * 16);
-    f.b1 = *reinterpret_cast<const h8*>(b + 32 * LDP + kk * 16);
-    return f;
-  };
-  auto mma = [&](const Frag& f) {
-    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a0, f.b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a0, f.b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a1, f.b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a1, f.b1, acc[1][1], 0, 0, 0);
-  };
-
-  gload(s0);                 // K step 0
-  if (nk > 1) gload(s1);     // K step 1
-  lstore(s0, 0);
-  if (nk > 2) gload(s0);     // K step 2
-  __syncthreads();
-
-  int cur = 0;
-  // one K step: MFMAs on LDS stage `cur`; `st` holds step kt+1 -> written to the other LDS stage,
-  // then refilled with step kt+3
-  auto kstep = [&](int kt, Stage& st) {
-    const _Float16* a = As + cur * BM * LDP + (wm * 64 + frag_row) * LDP + frag_k;
-    const _Float16* b = Bs + cur * BN * LDP + (wn * 64 + frag_row) * LDP + frag_k;
-    Frag f0 = fread(a, b, 0);
-    Frag f1 = fread(a, b, 1);
-    mma(f0);
-    f0 = fread(a, b, 2);
-    mma(f1);
-    f1 = fread(a, b, 3);
-    if (kt + 1 < nk) lstore(st, cur ^ 1);
-    if (kt + 3 < nk) gload(st);
-    mma(f0);
-    mma(f1);
-    __syncthreads();
-    cur ^= 1;
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    kstep(kt, s1);
-    if (kt + 1 < nk) kstep(kt + 1, s0);
-  }
-
-  // ---- epilogue: raw accumulators -> LDS C tile -> sd_store_tile (sd_epilogue.h)
-  float* Cs = reinterpret_cast<float*>(smem_raw);
-  const int hrow = (lane >> 5) * 4;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int cl = wn * 64 + ni * 32 + (lane & 31);
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + hrow;
-        Cs[rl * LDC + cl] = acc[mi][ni][r];
-      }
-    }
-  }
-  __syncthreads();
-  sd_store_tile<TO, BM, BN, 256>(p, Cs, LDC, m0, n0, tid, vec);
+  using P = RegF16<TA>;
+#include "sd_conv_tile_reg16_body.h"
 }
 
 // ------------------------------------------------------------------------------------------
-// f32-split16x3 for the NARROW outputs (Res2Net 128 -> 128 k = 3, attention TDNN 3C -> 128): the 128x128 register-staged kernel
-// above with the split done WHILE STAGING.  Activations arrive as plain f32 (no pack pass, any lda / a_col0 slice, the tee /
+// f32-split16x3 for the NARROW outputs (Res2Net 128 -> 128 k = 3, attention TDNN 3C -> 128): the 128x128 register-staged tile
+// with the split done WHILE STAGING.  Activations arrive as plain f32 (no pack pass, any lda / a_col0 slice, the tee /
 // tee_add epilogue of the Res2Net chain); a thread loads 4 values (16 bytes), splits them hi = f16(v), lo = f16(v - hi) and
 // stores both halves into the LDS row of its K step: [hi x 32 | lo x 32], the layout of the SD_DT_SPLIT16 weights, which are
 // fetched as they lie.  A K step of 32 values = the four 16-half fragment slices hi0, hi1, lo0, lo1 and six MFMA groups,
@@ -226,176 +87,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_f16_kernel(const sd_conv_arg
 template <typename TO>
 __global__ __launch_bounds__(256, 2) void conv_gemm_split16_n128_kernel(const sd_conv_args p, const int vec) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  _Float16* As = reinterpret_cast<_Float16*>(smem_raw);  // [2][BM][LDP]
-  _Float16* Bs = As + 2 * BM * LDP;                       // [2][BN][LDP]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-  const int n_tiles = (p.cout + BN - 1) / BN;
-  int wg;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
-  const int tile_n = wg % n_tiles;
-  const int tile_m = wg / n_tiles;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  // staging role: 8 threads per row, 4 rows per thread.  A: thread c8 owns VALUES 4 c8 .. 4 c8 + 3 of the step's 32 (one 16-byte
-  // f32 load); B: halfs 8 c8 .. 8 c8 + 7 of the 64 (one 16-byte load of the packed weights)
-  const int c8 = tid & 7;
-  const int r0 = tid >> 3;
-  int a_seg[4], a_t[4];
-  const _Float16* wptr[4];
-  const float* aptr[4];
-  const int kvals = p.taps * p.cin_pad;                   // values per output channel; 2 halfs each
-  const _Float16* W = static_cast<const _Float16*>(p.w);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int m = m0 + r0 + 32 * i;
-    m = m < p.M ? m : p.M - 1;
-    const int seg = (m / p.T) * p.T;
-    a_seg[i] = seg;
-    a_t[i] = m - seg;
-    int n = n0 + r0 + 32 * i;
-    n = n < p.cout ? n : p.cout - 1;
-    wptr[i] = W + (size_t)n * 2 * kvals + c8 * 8;
-  }
-  const int nk = p.taps * (p.cin_pad / 32);
-  const int half = p.taps / 2;
-  const float* X = static_cast<const float*>(p.x) + p.a_col0;
-  auto set_tap = [&](int tap) {
-    const int delta = (tap - half) * p.dil;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int tt = a_t[i] + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
-      aptr[i] = X + (size_t)(a_seg[i] + tt) * p.lda;
-    }
-  };
-  struct Stage { f32x4 a[4]; h8 b[4]; };
-  Stage s0, s1;
-  int ld_tap = 0, ld_c0 = 0;
-  set_tap(0);
-  auto gload = [&](Stage& st) {
-    const int col = ld_c0 + c8 * 4;
-    const int acol = col < p.cin ? col : 0;               // columns past cin meet the zero-filled weight padding
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      st.a[i] = *reinterpret_cast<const f32x4*>(aptr[i] + acol);
-      st.b[i] = *reinterpret_cast<const h8*>(wptr[i]);
-      wptr[i] += BK;
-    }
-    ld_c0 += 32;
-    if (ld_c0 >= p.cin_pad) {
-      ld_c0 = 0;
-      ++ld_tap;
-      if (ld_tap < p.taps) set_tap(ld_tap);
-    }
-  };
-  auto lstore = [&](const Stage& st, int buf) {
-    _Float16* a = As + buf * BM * LDP;
-    _Float16* b = Bs + buf * BN * LDP;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      h4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float w = sd_split16_clamp(st.a[i][e]);
-        hi[e] = (_Float16)w;
-        lo[e] = (_Float16)(w - (float)hi[e]);
-      }
-      *reinterpret_cast<h4*>(a + (r0 + 32 * i) * LDP + c8 * 4) = hi;
-      *reinterpret_cast<h4*>(a + (r0 + 32 * i) * LDP + 32 + c8 * 4) = lo;
-      *reinterpret_cast<h8*>(b + (r0 + 32 * i) * LDP + c8 * 8) = st.b[i];
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int frag_row = lane & 31;
-  const int frag_k = (lane >> 5) * 8;
-  struct Frag { h8 a0, a1, b0, b1; };
-  auto fread = [&](const _Float16* a, const _Float16* b, int kk) {
-    Frag f;
-    f.a0 = *reinterpret_cast<const h8*>(a + kk * 16);
-    f.a1 = *reinterpret_cast<const h8*>(a + 32 * LDP + kk * 16);
-    f.b0 = *reinterpret_cast<const h8*>(b + kk * 16);
-    f.b1 = *reinterpret_cast<const h8*>(b + 32 * LDP + kk * 16);
-    return f;
-  };
-  auto mma = [&](const Frag& fa, const Frag& fb) {        // A fragments of fa against B fragments of fb
-    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa.a0, fb.b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa.a0, fb.b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa.a1, fb.b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa.a1, fb.b1, acc[1][1], 0, 0, 0);
-  };
-
-  gload(s0);                 // K step 0
-  if (nk > 1) gload(s1);     // K step 1
-  lstore(s0, 0);
-  if (nk > 2) gload(s0);     // K step 2
-  __syncthreads();
-  int cur = 0;
-  auto kstep = [&](int kt, Stage& st) {
-    const _Float16* a = As + cur * BM * LDP + (wm * 64 + frag_row) * LDP + frag_k;
-    const _Float16* b = Bs + cur * BN * LDP + (wn * 64 + frag_row) * LDP + frag_k;
-    const Frag h0 = fread(a, b, 0);           // hi, values 0-15
-    const Frag l0 = fread(a, b, 2);           // lo, values 0-15
-    mma(h0, h0);
-    const Frag h1 = fread(a, b, 1);           // hi, values 16-31
-    mma(h0, l0);
-    mma(l0, h0);
-    const Frag l1 = fread(a, b, 3);           // lo, values 16-31
-    if (kt + 1 < nk) lstore(st, cur ^ 1);
-    if (kt + 3 < nk) gload(st);
-    mma(h1, h1);
-    mma(h1, l1);
-    mma(l1, h1);
-    __syncthreads();
-    cur ^= 1;
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    kstep(kt, s1);
-    if (kt + 1 < nk) kstep(kt + 1, s0);
-  }
-
-  // ---- epilogue: accumulators x 2^-s -> LDS C tile -> sd_store_tile (sd_epilogue.h)
-  float* Cs = reinterpret_cast<float*>(smem_raw);
-  const float alpha = p.w_scale_inv != 0.f ? p.w_scale_inv : 1.f;
-  const int hrow = (lane >> 5) * 4;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int cl = wn * 64 + ni * 32 + (lane & 31);
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + hrow;
-        Cs[rl * LDC + cl] = acc[mi][ni][r] * alpha;
-      }
-    }
-  }
-  __syncthreads();
-  sd_store_tile<TO, BM, BN, 256, 2, 3, true>(p, Cs, LDC, m0, n0, tid, vec);      // (the only kernel that may write y as SD_DT_SPLIT16)
+  using P = RegSplit16;
+#include "sd_conv_tile_reg16_body.h"
 }
 
 #ifdef SD_STAMP
 // diagnostic build only (build_native.py --stamp): per-workgroup cycle counters, read by tools/stamp_t256.py
 __device__ unsigned long long sd_stamp_buf[8192 * 8];
 #endif
-
-#define SD_GLDS16(gptr, lptr)                                                              \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 constexpr int TBM = 256;
 constexpr int TBN = 256;
@@ -605,9 +304,9 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f16_t256_kernel(const sd_con
     const int m_tiles = (p.M + TBM - 1) / TBM;
     const int n_cg = n_tiles >> 2, n_rg = (m_tiles + 7) >> 3;
     const int nst = n_cg * n_rg, b = blockIdx.x;
-    const int q = nst >> 3, r = nst & 7, xcd = b & 7, slot = b >> 3;
-    const int s_lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const int s_cnt = q + (xcd < r ? 1 : 0);
+    const int slot = b >> 3;
+    const int s_lo = sd_xcd_first(b, nst);
+    const int s_cnt = sd_xcd_count(b, nst);
     if (pass >= s_cnt) break;
     const int st = s_lo + pass;
     tile_m = 8 * (st / n_cg) + (slot >> 2);
@@ -616,9 +315,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f16_t256_kernel(const sd_con
   } else {
     // the hardware's dispatch, one workgroup per tile: XCD x (= blockIdx % 8) owns a contiguous range of the tile list
     if (pass > 0) break;
-    const int nwg = (int)gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+    const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
     tile_n = wg % n_tiles;
     tile_m = wg / n_tiles;
   }
@@ -655,8 +352,7 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f16_t256_kernel(const sd_con
       m = m < p.M ? m : p.M - 1;
       const int seg = (m / p.T) * p.T;
       int tt = m - seg + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+      tt = sd_reflect(tt, p.T);
       ptr[i] = X + (size_t)(seg + tt) * p.lda;
     }
   };
@@ -887,12 +583,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int n_tiles = (p.cout + TBN - 1) / TBN;
-  int wg;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-  }
+  const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
   const int tile_n = wg % n_tiles, tile_m = wg / n_tiles;
   const int m0 = tile_m * TBM, n0 = tile_n * TBN;
 
@@ -916,8 +607,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       m = m < p.M ? m : p.M - 1;
       const int seg = (m / p.T) * p.T;
       int tt = m - seg + delta;
-      tt = tt < 0 ? -tt : tt;
-      tt = tt >= p.T ? 2 * (p.T - 1) - tt : tt;
+      tt = sd_reflect(tt, p.T);
       pa[i] = (seg + tt - m0c) * p.lda;                 // |rows| < 256 + T: fits 32 bits for any lda this library accepts
     }
   };
@@ -1064,12 +754,7 @@ template <typename TO>
 int launch_w4(const sd_conv_args* a, int vec, hipStream_t stream) {
   const long tiles_m = (a->M + TBM - 1) / TBM;
   const long tiles_n = (a->cout + TBN - 1) / TBN;
-  auto kern = conv_gemm_f16_w4_kernel<TO>;
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), R3_LDS_BYTES));
-  {
-    SdProfScope prof(SD_PROF_CONV_WIDE, stream, 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), R3_LDS_BYTES, stream, *a, vec);
-  }
+  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_w4_kernel<TO>, SD_PROF_CONV_WIDE, sd_conv_flops(a), tiles_m * tiles_n, 256, R3_LDS_BYTES, stream, *a, vec));
   SD_CHECK_LAUNCH(sizeof(TO) == 2 ? "conv_gemm_f16_w4_kernel<f16>" : "conv_gemm_f16_w4_kernel<f32>");
   return SD_OK;
 }
@@ -1094,8 +779,6 @@ template <typename TO, bool DIRECT, bool SPLIT = false>
 int launch_t256(const sd_conv_args* a, int vec, hipStream_t stream) {
   const long tiles_m = (a->M + TBM - 1) / TBM;
   const long tiles_n = (a->cout + TBN - 1) / TBN;
-  auto kern = conv_gemm_f16_t256_kernel<TO, DIRECT, SPLIT>;
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), R3_LDS_BYTES));
   // the super-tile walk (256 persistent workgroups, 8 x 4 tiles per XCD and pass) when the tile list is several rounds long, the chip has 8 x 32
   // CUs and the column tiles come in fours (sd_set_tuning(SD_TUNE_T256_LOCKSTEP_TILES): from how many tiles; default 4 x the CU count)
   static const int n_cu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
@@ -1103,12 +786,9 @@ int launch_t256(const sd_conv_args* a, int vec, hipStream_t stream) {
   long from = sd_t256_lockstep_tiles().load(std::memory_order_relaxed);
   if (from < 0) from = 4L * 256;
   const bool super = DIRECT && n_cu == 256 && tiles_n % 4 == 0 && total < (1L << 30) && total >= from;
-  {
-    // work = the algorithmic (f32-equivalent) flops: a split row carries cin / 2 values
-    SdProfScope prof(SD_PROF_CONV_WIDE, stream, (SPLIT ? 1.0 : 2.0) * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    if (super) hipLaunchKernelGGL(kern, dim3(256), dim3(512), R3_LDS_BYTES, stream, *a, vec, 1);
-    else hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(512), R3_LDS_BYTES, stream, *a, vec, 0);
-  }
+  // work = the algorithmic (f32-equivalent) flops: a split row carries cin / 2 values
+  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_t256_kernel<TO, DIRECT, SPLIT>, SD_PROF_CONV_WIDE, (SPLIT ? 0.5 : 1.0) * sd_conv_flops(a), super ? 256L : total, 512,
+                              R3_LDS_BYTES, stream, *a, vec, super ? 1 : 0));
   SD_CHECK_LAUNCH((t256_label<TO, DIRECT, SPLIT>(super)));
   return SD_OK;
 }
@@ -1117,12 +797,7 @@ template <typename TA, typename TO>
 int launch(const sd_conv_args* a, int vec, hipStream_t stream) {
   const long tiles_m = (a->M + BM - 1) / BM;
   const long tiles_n = (a->cout + BN - 1) / BN;
-  auto kern = conv_gemm_f16_kernel<TA, TO>;
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), STAGE_BYTES));
-  {
-    SdProfScope prof(SD_PROF_CONV_GEMM, stream, 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), STAGE_BYTES, stream, *a, vec);
-  }
+  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_kernel<TA, TO>, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles_m * tiles_n, 256, STAGE_BYTES, stream, *a, vec));
   SD_CHECK_LAUNCH(sizeof(TA) == 2 ? (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f16,f16>" : "conv_gemm_f16_kernel<f16,f32>")
                                   : (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f32,f16>" : "conv_gemm_f16_kernel<f32,f32>"));      // <x, y>
   return SD_OK;
@@ -1259,12 +934,7 @@ static int conv1d_cl_split16_narrow(const sd_conv_args* a, hipStream_t stream) {
   if (a->y_dtype == SD_DT_SPLIT16)      // y written as split halves by the shared epilogue's vector path (ldo in VALUE columns)
     SD_CHECK_ARG(vec && a->ldo % 32 == 0, "sd_conv1d_cl_split16: an SD_DT_SPLIT16 output needs ldo %% 32 == 0 and the aligned (vector) epilogue (ldo=%d o_col0=%d cout=%d)",
                  a->ldo, a->o_col0, a->cout);
-  auto kern = conv_gemm_split16_n128_kernel<float>;
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kern), STAGE_BYTES));
-  {
-    SdProfScope prof(SD_PROF_CONV_GEMM, stream, 2.0 * (double)a->M * (double)a->cout * (double)a->taps * (double)a->cin);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(256), STAGE_BYTES, stream, *a, vec);
-  }
+  SD_CHECK_HIP(sd_launch_conv(conv_gemm_split16_n128_kernel<float>, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles_m * tiles_n, 256, STAGE_BYTES, stream, *a, vec));
   SD_CHECK_LAUNCH("conv_gemm_split16_n128_kernel");
   return SD_OK;
 }

@@ -42,6 +42,7 @@
 // loads become branches with a wait each; the staging loop therefore loads unconditionally from a clamped index and
 // selects the zero padding afterwards.
 #include "sd_fbank_internal.h"
+#include "sd_conv_tile.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -121,10 +122,6 @@ struct Fbank2Args {
   const int* lens; const int* frame_start; const int* tile_start; int n_lo; int M;
 };
 
-#define FB2_GLDS16(gptr, lptr)                                                             \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-
 // one pass over NTILE bin tiles starting at tile Q0: DFT into acc, then their power spectra into the mel accumulators
 template <int NTILE, int Q0, int PASS, bool ZERO_MEL>
 __device__ __forceinline__ void fbank2_pass(const Fbank2Args& p, const float* xs, int base, char* stage, int lane, int wid,
@@ -142,7 +139,7 @@ __device__ __forceinline__ void fbank2_pass(const Fbank2Args& p, const float* xs
 #pragma unroll
     for (int pc = 0; pc < NTILE; ++pc) {
       const int piece = pc * WAVES + wid;
-      FB2_GLDS16(gsrc + (size_t)s * STAGE + piece * 1024 + lane * 16, stage + buf * STAGE + piece * 1024);
+      SD_GLDS16(gsrc + (size_t)s * STAGE + piece * 1024 + lane * 16, stage + buf * STAGE + piece * 1024);
     }
   };
   dma(0, 0);
@@ -307,8 +304,7 @@ __global__ __launch_bounds__(256 * V2_GROUPS, 1) void fbank_logmel_kernel(const 
           int sidx = s0 + rel;
           bool ok = true;
           if (p.pad_mode == SD_PAD_REFLECT) {
-            sidx = sidx < 0 ? -sidx : sidx;
-            sidx = sidx >= p.n ? 2 * (p.n - 1) - sidx : sidx;
+            sidx = sd_reflect(sidx, p.n);
           } else {
             ok = sidx >= 0 && sidx < p.n;
           }

@@ -38,6 +38,7 @@
 //    round) pass through a 16 KB LDS ring once per round (see the kernel): read per wave from L2 they were the bottleneck.
 // Per 16-frame tile: 50 + 192 + 120 MFMAs of 16 cycles.  Measured: DESIGN.md section 4.
 #include "sd_fbank_internal.h"
+#include "sd_conv_tile.h"
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -109,22 +110,12 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 __host__ __device__ constexpr int img_words(int n) { return (n + NFFT) + (n + NFFT) / HOP + 1; }
 
-__device__ __forceinline__ void swap16(unsigned& a, unsigned& b) {      // 16-lane rows 1, 3 of a <-> rows 0, 2 of b
-  const auto w = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-  const unsigned w0 = w[0], w1 = w[1];
-  a = w0; b = w1;
-}
-__device__ __forceinline__ void swap32(unsigned& a, unsigned& b) {      // rows 2, 3 of a <-> rows 0, 1 of b
-  const auto w = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-  const unsigned w0 = w[0], w1 = w[1];
-  a = w0; b = w1;
-}
 // r[i] holds in lane group g the value (i, g)  ->  r[i] holds in lane group g the value (g, i)
 __device__ __forceinline__ void transpose4(unsigned (&r)[4]) {
-  swap16(r[0], r[1]);
-  swap16(r[2], r[3]);
-  swap32(r[0], r[2]);
-  swap32(r[1], r[3]);
+  sd_swap16(r[0], r[1]);      // 16-lane rows 1, 3 of a <-> rows 0, 2 of b
+  sd_swap16(r[2], r[3]);
+  sd_swap32(r[0], r[2]);      // rows 2, 3 of a <-> rows 0, 1 of b
+  sd_swap32(r[1], r[3]);
 }
 
 __device__ __forceinline__ unsigned pk_rtz(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b)); }
@@ -290,8 +281,8 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
       int sidx = i - NFFT / 2;
       bool ok = true;
       if (p.pad_mode == SD_PAD_REFLECT) {
-        sidx = sidx < 0 ? -sidx : sidx;
-        sidx = sidx >= p.n ? 2 * (p.n - 1) - sidx : sidx;
+        sidx = sidx < 0 ? -sidx : sidx;                              // sd_reflect(sidx, p.n) (sd_conv_tile.h), kept as this kernel's own text:
+        sidx = sidx >= p.n ? 2 * (p.n - 1) - sidx : sidx;            // through the helper both instantiations compile differently (tools/isa_diff.py)
       } else {
         ok = sidx >= 0 && sidx < p.n;
       }
@@ -360,8 +351,7 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
   // Waves without a tile in a round still fetch and join the barriers.
   const gptr_t stream = tab + (size_t)T_STREAM * 1024 + (size_t)wid * 1024 + lane16;
   auto dma = [&](int q) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(stream + (size_t)q * 8192),
-                                     (__attribute__((address_space(3))) void*)(ring + ((q & 1) * 8 + wid) * 1024), 16, 0, 0);
+    SD_GLDS16(stream + (size_t)q * 8192, ring + ((q & 1) * 8 + wid) * 1024);
   };
   auto chunk_sync = [&](int q) {                      // in front of the first use of chunk q
 #ifdef SD_U16_DIAG_NOWAIT      // timing-only diagnostic build (results wrong): what the wait for the chunk's own DMA costs

@@ -41,6 +41,7 @@
 #include <cstdlib>
 
 #include "sd_common.h"
+#include "sd_conv_tile.h"
 
 namespace {
 
@@ -65,10 +66,6 @@ struct ChainArgs {
   const float* scale[RC_MAXN];
   const float* shift[RC_MAXN];
 };
-
-#define RC_GLDS16(gptr, lptr)                                                              \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 __device__ __forceinline__ void rc_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(RC_THREADS) void res2net_chain_f16_kernel(const Cha
       for (int i = 0; i < rows4; i += 4) {
         int row = i + lrow;
         row = row < T ? row : T - 1;
-        RC_GLDS16(R + (size_t)row * a.ld + chunk * RC_CH + ((lq ^ (row & 15)) << 3), buf + i * RC_ROWB);
+        SD_GLDS16(R + (size_t)row * a.ld + chunk * RC_CH + ((lq ^ (row & 15)) << 3), buf + i * RC_ROWB);
       }
     };
     // u_1 = c_1 -> buffer 1: a third of the rows each by this wave and the two copy-out waves (one wave issues a 1 KB
@@ -120,7 +117,7 @@ __global__ __launch_bounds__(RC_THREADS) void res2net_chain_f16_kernel(const Cha
     for (int i = 0; i < rows4; i += 12) {
       int row = i + lrow;
       row = row < T ? row : T - 1;
-      RC_GLDS16(R + (size_t)row * a.ld + 1 * RC_CH + ((lq ^ (row & 15)) << 3), smem + BUF + i * RC_ROWB);
+      SD_GLDS16(R + (size_t)row * a.ld + 1 * RC_CH + ((lq ^ (row & 15)) << 3), smem + BUF + i * RC_ROWB);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     rc_barrier();                                      // S
@@ -142,7 +139,7 @@ __global__ __launch_bounds__(RC_THREADS) void res2net_chain_f16_kernel(const Cha
     for (int i = 4 * (part + 1); i < rows4; i += 12) {  // this wave's third of c_1 (see the DMA wave)
       int row = i + lrow;
       row = row < T ? row : T - 1;
-      RC_GLDS16(R + (size_t)row * a.ld + 1 * RC_CH + ((lq ^ (row & 15)) << 3), smem + BUF + i * RC_ROWB);
+      SD_GLDS16(R + (size_t)row * a.ld + 1 * RC_CH + ((lq ^ (row & 15)) << 3), smem + BUF + i * RC_ROWB);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     rc_barrier();                                      // S
@@ -213,8 +210,7 @@ __global__ __launch_bounds__(RC_THREADS) void res2net_chain_f16_kernel(const Cha
       for (int tt = 0; tt < NTW; ++tt) {
         int tr = tt * 32 + fnq;
         tr = (tr < T ? tr : T - 1) + delta;
-        tr = tr < 0 ? -tr : tr;
-        tr = tr >= T ? 2 * (T - 1) - tr : tr;
+        tr = sd_reflect(tr, T);
         base[tt] = tr * RC_ROWB + (((2 * fh) ^ (tr & 15)) << 4);
       }
     };
