@@ -197,12 +197,13 @@ HDBSCAN_PROTOTYPES = {
     "sd_hdb_outgoing_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
-# include/sd_hip_trace.h: the launch log, same shared object, a table and a version of its own
-SD_TRACE_ABI_VERSION = 1
+# include/sd_hip_trace.h: the launch log and the ECAPA plan, same shared object, a table and a version of its own
+SD_TRACE_ABI_VERSION = 2
 TRACE_PROTOTYPES = {
     "sd_trace_abi_version": (_I, []),
     "sd_launch_log_enable": (_I, [_I]),
     "sd_launch_log_read": (_Z, [C.c_char_p, _Z]),
+    "sd_ecapa_plan_read": (_Z, [_P, _I, _I, _I, _I, C.c_char_p, _Z]),
 }
 
 _lib = None
@@ -273,6 +274,25 @@ def launch_log_read() -> dict:
         label, _, count = line.rpartition("\t")
         out[label] = int(count)
     return out
+
+
+PLAN_MAPS = {"uniform": 0, "lengths": 1, "packed": 2}
+
+
+def ecapa_plan_read(weights, B: int, T: int = 0, M: int = 0, map_kind: str = "uniform") -> list:
+    """The plan of one ECAPA forward (include/sd_hip_trace.h; no device): [(step, route, [reads], [writes])], the "carve" line first.
+    `weights`: an sd_ecapa_weights.  Tensors are "buffer[col0:col1]:form"."""
+    lib = load()
+    need = 1 << 14
+    while True:
+        buf = C.create_string_buffer(need)
+        got = lib.sd_ecapa_plan_read(C.byref(weights), B, T, M, PLAN_MAPS[map_kind], buf, need)
+        if got == 0:
+            raise SdError(f"sd_ecapa_plan_read refused: {last_error()}")
+        if got <= need:
+            break
+        need = got
+    return [(s, r, rd.split(), wr.split()) for s, r, rd, wr in (line.split("\t") for line in buf.value.decode().splitlines())]
 
 
 def last_error() -> str:

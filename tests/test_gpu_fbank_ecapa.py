@@ -211,6 +211,50 @@ def test_ecapa_full_geometry_matches_oracle(dev, conv_kernel, B, n):
     assert np.abs(got - ref).max() < 1e-3 * np.abs(ref).max()
 
 
+@pytest.fixture(scope="module")
+def plan_engines(dev):
+    """One engine per (geometry, precision) of the plan cases, built on first use"""
+    import ecapa_plan as P
+    from speech_diarization_amd.engine import EmbeddingEngine
+    engines = {}
+
+    def get(geom, precision):
+        if (geom, precision) not in engines:
+            engines[geom, precision] = EmbeddingEngine(P.state_dict(geom), dev, precision=precision)
+        return engines[geom, precision]
+    return get
+
+
+def _plan_case_ids():
+    import ecapa_plan as P
+    return [c.id for c in P.gpu_cases()]
+
+
+@pytest.mark.parametrize("case_id", _plan_case_ids())
+def test_the_plan_is_what_ran(dev, plan_engines, case_id):
+    """sd_ecapa_plan_read (no device) against the launch log of the same forward: route by route the plan has as many steps as the
+    forward launched kernels of that route (ecapa_plan.count_mismatches).  The cases are the smallest at which a route can still go
+    wrong: below, between and above the two column-statistics floors, past the small-launch routing, relative lengths, packed spans,
+    the narrow packing on wide-role layers (width 256), no packing on them (width 512), f16 on either side of the fused chain's T."""
+    import ecapa_plan as P
+    from launch_log import launches
+    case = next(c for c in P.gpu_cases() if c.id == case_id)
+    eng = plan_engines(case.geom, case.precision)
+    P.set_tiles(case.tiles)
+    try:
+        _, steps = P.case_plan(case, eng.weights.struct)
+        with launches() as log:
+            emb = P.run_case(case, eng)
+        torch.cuda.synchronize()
+    finally:
+        P.set_tiles("auto")
+    assert bool(torch.isfinite(emb).all())
+    print({r: sum(s.route == r for s in steps) for r in sorted({s.route for s in steps})}, {k: v for k, v in log.items() if "fbank" not in k})
+    assert not P.count_mismatches(steps, log), P.count_mismatches(steps, log)
+    chain = case.precision == "f16" and case.kind != "packed" and P.frames(case.n) <= 212
+    assert any(s.route == "chain" for s in steps) == chain, "the fused chain runs up to T = 212"
+
+
 def test_ecapa_zero_padding_counts_as_signal(dev):
     """Zero-padded tails participate in mean-norm / SE / ASP exactly as in the reference
     (no lengths are passed, [REF anti_stick_diarize.py:163-168])."""

@@ -28,7 +28,7 @@ def test_header_and_binding_table_name_the_same_exported_entries():
     header = open(N.PKG_DIR.parent / "include" / "sd_hip_trace.h").read()
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     names = set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-    assert names == set(N.TRACE_PROTOTYPES) == {"sd_trace_abi_version", "sd_launch_log_enable", "sd_launch_log_read"}
+    assert names == set(N.TRACE_PROTOTYPES) == {"sd_trace_abi_version", "sd_launch_log_enable", "sd_launch_log_read", "sd_ecapa_plan_read"}
     assert not names & (set(N.PROTOTYPES) | set(N.SPECTRAL_PROTOTYPES) | set(N.AHC_PROTOTYPES) | set(N.HDBSCAN_PROTOTYPES))
     lib = N.load()
     for name, (res, args) in N.TRACE_PROTOTYPES.items():
@@ -41,7 +41,7 @@ def test_header_and_binding_table_name_the_same_exported_entries():
 @needs_lib
 def test_versions_and_struct_sizes_are_untouched():
     lib = N.load()
-    assert lib.sd_trace_abi_version() == 1 == N.SD_TRACE_ABI_VERSION
+    assert lib.sd_trace_abi_version() == 2 == N.SD_TRACE_ABI_VERSION
     assert lib.sd_abi_version() == 11 and lib.sd_spectral_abi_version() == 1 and lib.sd_ahc_abi_version() == 1 and lib.sd_hdbscan_abi_version() == 1
     assert [int(lib.sd_sizeof(i)) for i in range(5)] == [184, 88, 1672, 13944, 0]       # the committed layouts of ABI 11
     header = open(N.PKG_DIR.parent / "include" / "sd_hip.h").read()
