@@ -110,7 +110,10 @@ size_t sd_fbank_workspace_bytes(const sd_fbank_plan* plan, int B, int n);
  * path); larger magnitudes are clipped to +-16 (the split-f16 DFT scales the folded sums by 2^10 and they must
  * stay inside the f16 range), so any finite input gives finite features; an infinite sample saturates like any
  * other magnitude above 16.  A NaN sample makes every feature of ITS row NaN (what the reference's utterance-level
- * floor and mean over T do with it; the row's embedding is then NaN as well); other rows are unaffected. */
+ * floor and mean over T do with it; the row's embedding is then NaN as well); other rows are unaffected.
+ * Along the weight axis (profiles/weight_axis.json, "spans"): the features hold their bars, but miss float64 in other bins than an
+ * f32 STFT does, and a trained-like network is 1000 times more sensitive to them than the init: on one 2 s span the embedding sits
+ * 26.7 times the f32 oracle's own distance from float64, all of it from the features (the float64 network on them gives the same). */
 int sd_fbank_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n,
                  int mean_norm, float* out_dev, int ld_out,
                  void* ws_dev, size_t ws_bytes, sd_stream_t stream);
@@ -277,7 +280,13 @@ int sd_set_tuning(int key, long value);
 size_t sd_colstat_floats(int M, int cout);
 /* colstat -> out [B][C] = mean (want_std = 0) or
  * [B][2*C] = [mean | sqrt(clamp(var, eps))]; pivot = the conv's shift vector (NULL = 0); y [B*T][ldy]
- * of y_dtype at column y_col0 is the conv's output */
+ * of y_dtype at column y_col0 is the conv's output.
+ * The variance is the one-pass form about the pivot, q / T - m^2 with m the mean of y - pivot: it loses m^2 2^-24 T-fold sums' worth of
+ * the variance, harmless while |m| is about the std (a calibrated network: median 0.8).  On the MFA layer of a trained-like dict the std
+ * misses the stored output's by up to 4.5e-5 (always-on channels, m several times the std), 2.25 times the 2e-5 it holds at the init
+ * weights (profiles/weight_axis.json, "operators").  A channel that is exactly constant must sum exact zeros to reach the clamp: always
+ * off behind the ReLU it does; a row without weights does once the host has moved its constant into the shift (engine.py,
+ * fold_constant_rows). */
 int sd_colstat_finish_dt(const float* colstat, const float* pivot, const void* y, int y_dtype, int ldy, int y_col0,
                          int B, int T, int C, int want_std, float eps, float* out, sd_stream_t stream);
 

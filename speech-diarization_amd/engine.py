@@ -149,6 +149,23 @@ def bn_affine(sd: dict, prefix: str):
     return scale.astype(np.float32), shift.astype(np.float32)
 
 
+def fold_constant_rows(w: np.ndarray, bias: np.ndarray, affine):
+    """A conv + ReLU + BatchNorm layer whose output row r has no weight at all (a pruned or dead channel of a trained checkpoint) stores
+    the constant relu(bias[r]) * scale[r] + shift[r] on every frame.  The column statistics of the conv epilogues sum y - shift
+    (sd_hip.h: the one-pass form about the pivot), which for such a row is the constant relu(bias) * scale: its variance
+    q / T - m^2 then cancels to about 1e-7 m^2 instead of 0, and the pooling's global std came out as 3e-4 |m| where speechbrain
+    clamps to 1e-6.  Moving the constant into the shift (bias 0, shift + relu(bias) * scale, float64 on the host) stores the same
+    value and makes every term of the sums exactly 0.  -> (bias, (scale, shift)); the inputs when no row is empty."""
+    dead = ~np.any(w.reshape(w.shape[0], -1) != 0, axis=1)
+    if not dead.any():
+        return bias, affine
+    scale, shift = affine
+    bias, shift = bias.astype(np.float32, copy=True), shift.astype(np.float64)
+    shift[dead] += np.maximum(bias[dead].astype(np.float64), 0.0) * scale[dead].astype(np.float64)
+    bias[dead] = 0.0
+    return bias, (scale, shift.astype(np.float32))
+
+
 class EcapaWeights:
     """ECAPA-TDNN weights packed for the HIP kernels and resident on one device."""
 
@@ -218,8 +235,14 @@ class EcapaWeights:
         """Frame-level layers (M = B*T rows) follow the engine precision; per-segment layers
         (M = B rows: SE gate, global-context bias, FC) always stay f32."""
         cout, cin, k = w.shape
+        if affine is not None and bias is not None:        # the conv + ReLU + BatchNorm layers (every layer the forward runs with an affine and its own bias)
+            bias, affine = fold_constant_rows(w, bias, affine)
         half = self.precision == "f16" and not per_segment
         wdt = np.float16 if half else np.float32
+        if half and not float(np.abs(w).max()) < 65520.0:        # 65520 and above round to inf
+            # the f16 mode casts the weights unscaled: beyond the f16 range they would reach the matrix cores as inf (NaN keeps refusing too)
+            raise ValueError(f"precision 'f16': a frame-level conv weight {cout}x{cin}x{k} holds max |w| = {float(np.abs(w).max()):.4g}, which "
+                             f"f16 cannot hold (65504); use precision 'f32', 'f32s' or 'f32ns' for this checkpoint")
         packed = pack_conv_weight(w, wdt)
         L.w = self._dev(packed, wdt)
         L.w_dtype = N.SD_DT_F16 if half else N.SD_DT_F32

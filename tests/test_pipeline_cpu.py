@@ -17,10 +17,10 @@ def conversation(tmp_path_factory):
     return conv, path
 
 
-def cpu_oracle_encoder(width=128, seed=1234):
+def cpu_oracle_encoder(width=128, seed=1234, sd=None):
     from oracle.ecapa_ref import EcapaRef
     from oracle.pipeline_ref import encode_batch_ref
-    sd = synth.make_ecapa_state_dict(seed, synth.EcapaConfig.small(width))
+    sd = synth.make_ecapa_state_dict(seed, synth.EcapaConfig.small(width)) if sd is None else sd
     net = EcapaRef(sd, torch.float32)
     return lambda wavs: encode_batch_ref(sd, np.asarray(wavs, np.float32), torch.float32, net).astype(np.float32)
 
