@@ -1,6 +1,6 @@
 /*
- * sd_hip_trace.h — the launch log of libsd_hip.so and the plan of its ECAPA forward (same shared object as sd_hip.h, a binding table
- * of its own: `_native.TRACE_PROTOTYPES`, version `sd_trace_abi_version()`).
+ * sd_hip_trace.h — the launch log of libsd_hip.so, the plan of its ECAPA forward and the choice of its conv entries (same shared object
+ * as sd_hip.h, a binding table of its own: `_native.TRACE_PROTOTYPES`, version `sd_trace_abi_version()`).
  *
  * The library chooses among its kernels, their template instantiations and their tile walks on the host, by cost rules, the CU count,
  * sd_set_tuning keys and alignment.  The log makes the choice observable: every kernel launch that succeeded is counted under its
@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SD_TRACE_ABI_VERSION 2
+#define SD_TRACE_ABI_VERSION 3
 
 int sd_trace_abi_version(void);
 
@@ -48,7 +48,7 @@ size_t sd_launch_log_read(char* buf, size_t cap);
  *     step \t route \t reads \t writes
  * step    [b<block>.]<layer>[.<Res2Net step>] with layer one of: cast stem tdnn1 res2 chain tdnn2 squeeze se1 se2 scale mfa stats asp_g
  *         asp_h asp_conv pool fc, or <layer>.pack: the pack pass in front of that layer
- * route   f32              the exact-f32 conv operator (sd_conv1d_cl_f32), whatever kernel it picks
+ * route   f32              the exact-f32 conv operator (sd_conv1d_cl_f32); which kernel it picks: sd_conv_choice_read
  *         split128         128x128 split kernel, f32 input split while staged, the layer's own bias / scale (w_scale_inv)
  *         split128_folded  the same kernel with the wide packing's folded 2^s vectors (small launches of the C-wide layers)
  *         split256_pack    256x256 split kernel over xs, which the pack step before it wrote
@@ -63,6 +63,22 @@ size_t sd_launch_log_read(char* buf, size_t cap);
  *         semean seh gate stats gbias pooled (per segment), wpk (the fused chain's weights), feats, emb; a1 aliases x0 and e aliases xcat; forms f32 f16 split (SD_DT_SPLIT16)
  *         stat (a conv epilogue's per-tile column sums, parked in a dead buffer) scratch */
 size_t sd_ecapa_plan_read(const sd_ecapa_weights* w, int B, int T, int M, int map_kind, char* buf, size_t cap);
+
+/* What a conv entry would launch for these arguments (csrc/sd_conv_choice.h), without touching a device and
+ * without dereferencing any pointer of *a: a test may pass any 16-byte aligned non-null addresses.  `op` names the entry: */
+#define SD_CONV_OP_F32 0            /* sd_conv1d_cl_f32 */
+#define SD_CONV_OP_F32_SYMMETRIC 1  /* the affinity's symmetric product (x == w) */
+#define SD_CONV_OP_F32_STAT_ROWS 2  /* sd_conv1d_cl_f32 for a caller that takes column statistics in units of stat_rows rows (the ECAPA forward) */
+#define SD_CONV_OP_F16 3            /* sd_conv1d_cl_f16 */
+#define SD_CONV_OP_SPLIT16 4        /* sd_conv1d_cl_split16 */
+#define SD_CONV_OP_PACKED 5         /* sd_conv1d_cl_packed_f32 (any span table) */
+#define SD_CONV_OP_SEG_GEMM 6       /* sd_seg_gemm_f32 with an aligned scratch of scratch_bytes (0: none) */
+/* One line per launch (sd_seg_gemm_f32: one or two):
+ *     label \t grid \t block \t lds_bytes \t stat_rows
+ * The same check and the same choice as the launching entry makes, with the sd_set_tuning values and experiment switches as a call
+ * would read them now and a device of n_cu compute units (the MI355X: 256; 0: unknown).  Buffer and return convention of
+ * sd_launch_log_read; 0, with sd_last_error() set, where the entry itself would refuse the arguments. */
+size_t sd_conv_choice_read(const sd_conv_args* a, int op, int n_cu, size_t scratch_bytes, char* buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -198,12 +198,13 @@ HDBSCAN_PROTOTYPES = {
 }
 
 # include/sd_hip_trace.h: the launch log and the ECAPA plan, same shared object, a table and a version of its own
-SD_TRACE_ABI_VERSION = 2
+SD_TRACE_ABI_VERSION = 3
 TRACE_PROTOTYPES = {
     "sd_trace_abi_version": (_I, []),
     "sd_launch_log_enable": (_I, [_I]),
     "sd_launch_log_read": (_Z, [C.c_char_p, _Z]),
     "sd_ecapa_plan_read": (_Z, [_P, _I, _I, _I, _I, C.c_char_p, _Z]),
+    "sd_conv_choice_read": (_Z, [C.POINTER(sd_conv_args), _I, _I, _Z, C.c_char_p, _Z]),
 }
 
 _lib = None
@@ -293,6 +294,18 @@ def ecapa_plan_read(weights, B: int, T: int = 0, M: int = 0, map_kind: str = "un
             break
         need = got
     return [(s, r, rd.split(), wr.split()) for s, r, rd, wr in (line.split("\t") for line in buf.value.decode().splitlines())]
+
+
+CONV_OPS = {"f32": 0, "f32_symmetric": 1, "f32_stat_rows": 2, "f16": 3, "split16": 4, "packed": 5, "seg_gemm": 6}
+
+
+def conv_choice_read(args, op: str, n_cu: int = 256, scratch_bytes: int = 0) -> list:
+    """What entry `op` (CONV_OPS) would launch for the sd_conv_args `args` on a device of n_cu compute units (include/sd_hip_trace.h; no
+    device, no pointer is read): [(label, grid, block, lds_bytes, stat_rows)], one per launch.  SdError where the entry refuses."""
+    buf = C.create_string_buffer(512)
+    if load().sd_conv_choice_read(C.byref(args), CONV_OPS[op], n_cu, scratch_bytes, buf, 512) == 0:
+        raise SdError(f"sd_conv_choice_read refused: {last_error()}")
+    return [(f[0], *(int(v) for v in f[1:])) for f in (line.split("\t") for line in buf.value.decode().splitlines())]
 
 
 def last_error() -> str:

@@ -10,13 +10,18 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 int sd_set_error(int code, const char* fmt, ...);
-// SD_TUNE_F16_NARROW_TILES (sd_set_tuning): C-wide f16 / split16 layers with at most this many 256x256 tiles take the 128x128 kernel
 #include <atomic>
-std::atomic<long>& sd_f16_narrow_tiles();
-std::atomic<long>& sd_t256_lockstep_tiles();     // SD_TUNE_T256_LOCKSTEP_TILES (negative: 4 x the CU count)
+#include "sd_conv_choice.h"
 // library-internal entry points
+// The conv operators with the caller's tuning snapshot (sd_conv_choice.h; the public entries take their own): one ECAPA forward hands
+// one snapshot to its plan and to every conv it launches.  sd_conv_gemm.hip, sd_conv_gemm_f16.hip.
+int sd_conv1d_cl_f32_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t, int* stat_rows);   // stat_rows: may be null
+int sd_conv1d_cl_packed_f32_with(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream, const SdConvTuning& t);
+int sd_seg_gemm_f32_with(const sd_conv_args* a, void* scratch, size_t scratch_bytes, sd_stream_t stream, const SdConvTuning& t);
+int sd_conv1d_cl_f16_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t);
+int sd_conv1d_cl_split16_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t);
+int sd_conv_f16_decide(const sd_conv_args* a, int op, const SdConvTuning& t, SdConvChoice c[2], int* n, int* vec);   // check + choose of the two above
 int sd_conv1d_cl_f32_symmetric(const sd_conv_args* a, sd_stream_t stream);   // sd_conv_gemm.hip: x == w, upper triangle + mirror
-int sd_conv1d_cl_f32_rows(const sd_conv_args* a, sd_stream_t stream, int* stat_rows);   // sd_conv_gemm.hip: sd_conv1d_cl_f32 that may write colstat in units of *stat_rows rows
 int sd_colstat_finish_rows(const float* colstat, const float* pivot, const void* y, int y_dtype, int ldy, int y_col0, int B, int T, int C, int want_std,
                            float eps, float* out, int unit_rows, sd_stream_t stream);              // sd_pool.hip: sd_colstat_finish_dt for such units
 int sd_affinity_sym_f32(const float* xn, int ldx, int N, int groups, float* out, long ldo, sd_stream_t stream);                          // sd_affinity.hip
@@ -57,7 +62,7 @@ struct SdConvRule {
   int store;                  // store granularity of the vector epilogue (ldo, o_col0, ldt, ld_ta, ta_col0): 4 exact f32, 8 f16 / split
   bool packed;                // packed spans: neither M % T nor the reflect check (a->T is ignored)
   bool tee_add;               // the kernel has the tee_add epilogue
-  int colstat_T;              // column statistics need T >= this (64, 128); 0: refused (SD_ERR_UNSUPPORTED)
+  int colstat_T;              // column statistics need T >= this (SD_COLSTAT_T_128 / _256); 0: refused (SD_ERR_UNSUPPORTED)
 };
 int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec);
 
@@ -100,7 +105,7 @@ struct SdProfScope {
 // (the reference's web UI calls the pipeline from a worker thread) both get the attribute set before the launch.
 hipError_t sd_func_max_lds(const void* func, int bytes);
 
-// A/B switches (SD_F32_WIDE, SD_RES2_FUSED, ...) re-route kernels and exist for measurements only: they are read ONLY when the
+// A/B switches (SD_F16_KERNEL, SD_RES2_FUSED, ...) re-route kernels and exist for measurements only: they are read ONLY when the
 // process also sets SD_EXPERIMENT=1, so a stray SD_* variable cannot change which kernels a product run uses.
 static inline const char* sd_experiment_env(const char* name) {
   static const bool on = [] { const char* e = getenv("SD_EXPERIMENT"); return e && e[0] == '1' && e[1] == 0; }();

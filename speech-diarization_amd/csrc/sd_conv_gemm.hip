@@ -19,9 +19,11 @@
 // same permutation, and the sum over k is order independent up to rounding.
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 
 #include "sd_common.h"
 #include "sd_conv_tile.h"
+#include "sd_hip_trace.h"
 #include "sd_epilogue.h"
 
 namespace {
@@ -31,9 +33,6 @@ constexpr int BN = 128;
 constexpr int BK = 32;
 constexpr int LDP = BK + 4;  // padded LDS row, floats
 constexpr int LDC = BN + 4;  // padded row of the epilogue's C tile in LDS
-#ifndef SD_F32_DMA_DEFAULT
-#define SD_F32_DMA_DEFAULT 1
-#endif
 static_assert(BM * LDC <= 2 * (BM + BN) * LDP, "C tile must fit in the operand stage");
 
 #ifdef SD_STAMP
@@ -317,7 +316,7 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
 #endif
 }
 
-// One workgroup per tile (the grid may be smaller, SD_PERSIST: the workgroups then walk the tile list).
+// One workgroup per tile (the host launches grid = ntiles; the kernel keeps the walk of a smaller grid over the tile list).
 //
 // Workgroups are dealt round-robin over the eight XCDs (one 4 MB L2 each).  Every XCD owns a
 // contiguous range of logical tiles, laid out in bands of 8 row tiles, n-major inside a band, so
@@ -325,7 +324,7 @@ __device__ __forceinline__ void conv_tile_f32(const sd_conv_args& p, const int v
 // weight column panel it touches is shared by 8 workgroups.  Measured: L2 fill traffic of the C->C
 // layers 13.6 -> 8.8 GB per launch (A alone is 1.7 GB; workgroups drift apart in K, so whole panels
 // would have to stay resident for more), throughput unchanged within the box-to-box noise (the
-// kernel is MFMA bound).  SD_TILE_ORDER=0 (host, diagnostic) keeps the launch order.
+// kernel is MFMA bound).  The host passes order 1 (2: the symmetric band list); order 0 keeps the launch order.
 template <bool DMA>
 __global__ __launch_bounds__(256, 2) void conv_gemm_f32_kernel(const sd_conv_args p, const int vec, const int order, const int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1038,74 +1037,40 @@ extern "C" int sd_debug_read_c32_stamps(unsigned long long* out, int n) {
 }
 #endif
 
-namespace {
-long tune_env(const char* name, long dflt) {
-  const char* e = sd_experiment_env(name);
-  return e ? atol(e) : dflt;
-}
-std::atomic<long> g_skinny_below{tune_env("SD_SKINNY_TILES", 128L)};     // measured at 16 / 32 / 64 / 128 segments: 128 beats 256 and 512
-std::atomic<long> g_wide_from{1024L};
-// measured (tools/probe_small_shapes.py): Res2Net conv at 64 segments (101 tiles of 128x128) 19 us against 31 on the 128x128 kernel, at 128
-// segments (201 tiles) 37 against 34
-constexpr long S64_DEFAULT = 128L;
-std::atomic<long> g_s64_below{tune_env("SD_S64_TILES", S64_DEFAULT)};
-std::atomic<long> g_half_tiles{tune_env("SD_F32_N64", -1L)};     // -1: by the rule; 0 never; 1 whenever possible
-std::atomic<long> g_tile_rows{tune_env("SD_F32_TILE_ROWS", -1L)};  // -1: by the rule; 0: 128-row tiles only; 80 / 96 / 112: that height whenever possible
+// ---------------------------------------------------------------------------------------------- host: check, choose, launch
+// (the choice: sd_conv_choice.h, whose geometry must be this file's)
+static_assert(SD_T128 == BM && SD_T128 == BN && SD_F32_BK == BK && SD_T256 == WBM && SD_T256 == WBN && SD_S64 == S64_T && SD_SKINNY == SK_T, "sd_conv_choice.h: tile sizes");
+static_assert(SD_LDS_F32_128 == (size_t)2 * (BM + BN) * LDP * sizeof(float) && SD_LDS_T256 == (size_t)W_LDS_BYTES &&
+              SD_LDS_F32_S64 == (size_t)S64_ST * S64_STAGE * sizeof(float), "sd_conv_choice.h: LDS bytes");
 
-// conv_gemm_f32_vh_kernel<J> by J - 5: tiles of 16 J = 80 / 96 / 112 rows, two stages of (16 J + BN) staged rows
-struct VhKernel { void (*fn)(sd_conv_args, int); const char* label; size_t lds; };
-constexpr size_t vh_lds(int j) { return (size_t)2 * (16 * j + BN) * BK * sizeof(float); }
-const VhKernel g_vh_kernels[3] = {{conv_gemm_f32_vh_kernel<5>, "conv_gemm_f32_vh_kernel<5>", vh_lds(5)},
-                                  {conv_gemm_f32_vh_kernel<6>, "conv_gemm_f32_vh_kernel<6>", vh_lds(6)},
-                                  {conv_gemm_f32_vh_kernel<7>, "conv_gemm_f32_vh_kernel<7>", vh_lds(7)}};
+namespace {
+// the values of sd_set_tuning by key (index 0 unused)
+std::atomic<long> g_tune[SD_TUNE_T256_LOCKSTEP_TILES + 1] = {
+    {0L}, {sd_tune_default(1)}, {sd_tune_default(2)}, {sd_tune_default(3)}, {sd_tune_default(4)}, {sd_tune_default(5)}, {sd_tune_default(6)}, {sd_tune_default(7)}};
 }  // namespace
 
 extern "C" int sd_set_tuning(int key, long value) {
-  if (key == SD_TUNE_SKINNY_TILES) {
-    g_skinny_below.store(value < 0 ? 128L : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_WIDE_TILES) {
-    g_wide_from.store(value < 0 ? 1024L : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_S64_TILES) {
-    g_s64_below.store(value < 0 ? S64_DEFAULT : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_TILE_ROWS) {
-    g_tile_rows.store(value < 0 ? -1L : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_HALF_TILES) {
-    g_half_tiles.store(value < 0 ? -1L : (value ? 1L : 0L), std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_F16_NARROW_TILES) {
-    sd_f16_narrow_tiles().store(value < 0 ? 128L : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  if (key == SD_TUNE_T256_LOCKSTEP_TILES) {
-    sd_t256_lockstep_tiles().store(value < 0 ? -1L : value, std::memory_order_relaxed);
-    return SD_OK;
-  }
-  return sd_set_error(SD_ERR_ARG, "sd_set_tuning: unknown key %d", key);
+  if (key < 1 || key > SD_TUNE_T256_LOCKSTEP_TILES) return sd_set_error(SD_ERR_ARG, "sd_set_tuning: unknown key %d", key);
+  g_tune[key].store(sd_tune_stored(key, value), std::memory_order_relaxed);
+  return SD_OK;
 }
 
-static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream, bool symmetric, int* stat_rows = nullptr);
-
-extern "C" int sd_conv1d_cl_f32(const sd_conv_args* a, sd_stream_t stream) { return conv1d_cl_f32_impl(a, stream, false); }
-
-// The same for a caller that can take the column statistics in units other than 128 rows (internal, sd_common.h: the ECAPA schedule):
-// *stat_rows receives the unit the launch used (128, or the 80 / 96 / 112 rows of the variable-height kernel), for sd_colstat_finish_rows.
-int sd_conv1d_cl_f32_rows(const sd_conv_args* a, sd_stream_t stream, int* stat_rows) {
-  if (stat_rows) *stat_rows = 128;
-  return conv1d_cl_f32_impl(a, stream, false, stat_rows);
+SdConvTuning sd_conv_tuning_now(int n_cu) {
+  static const SdConvTuning env = [] {        // the two A/B switches, read once per process
+    SdConvTuning t = sd_conv_tuning_default(0);
+    if (const char* e = sd_experiment_env("SD_F16_KERNEL")) t.f16_kernel = e[0] == 'r' ? 0 : e[0] == 't' ? 2 : -1;
+    if (const char* e = sd_experiment_env("SD_T256_DIRECT")) t.t256_direct = e[0] != '0';
+    return t;
+  }();
+  SdConvTuning t = env;
+  for (int k = 1; k <= SD_TUNE_T256_LOCKSTEP_TILES; ++k) t.tune[k] = g_tune[k].load(std::memory_order_relaxed);
+  if (n_cu < 0) {
+    static const int device_cu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
+    n_cu = device_cu;
+  }
+  t.n_cu = n_cu;
+  return t;
 }
-
-// x == w, M == cout, no epilogue arithmetic: only the tiles on and above the diagonal are computed, each is stored
-// twice (as is and transposed).  Internal (sd_common.h): the affinity's full-matrix call.
-int sd_conv1d_cl_f32_symmetric(const sd_conv_args* a, sd_stream_t stream) { return conv1d_cl_f32_impl(a, stream, true); }
 
 int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec) {
   const char* fn = r.fn;
@@ -1149,174 +1114,131 @@ int sd_check_conv(const sd_conv_args* a, const SdConvRule& r, int* vec) {
   return SD_OK;
 }
 
-static int conv1d_cl_f32_impl(const sd_conv_args* a, sd_stream_t stream_, bool symmetric, int* stat_rows) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f32: null args");
-  SD_CHECK_ARG(a->w_dtype == SD_DT_F32, "sd_conv1d_cl_f32: w_dtype %d not supported by the f32 operator", a->w_dtype);
-  SD_CHECK_ARG(a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_f32: x/y must be f32 (use sd_conv1d_cl_f16 for f16 activations)");
-  int vec;
-  if (int e = sd_check_conv(a, {"sd_conv1d_cl_f32", 4, BK, 4, false, true, 64}, &vec)) return e;
-  const long tiles_m = (a->M + BM - 1) / BM;
-  const long tiles_n = (a->cout + BN - 1) / BN;
-  SD_CHECK_ARG(tiles_m * tiles_n < (1L << 31), "sd_conv1d_cl_f32: grid too large");
-  // fewer 128x128 tiles than half the CUs: 32x32 tiles with in-workgroup split-K (sd_set_tuning / SD_SKINNY_TILES)
-  if (symmetric)
-    SD_CHECK_ARG(a->M == a->cout && a->T == 1 && a->taps == 1 && !a->bias && !a->scale && !a->shift && !a->tee && !a->colstat &&
-                 a->act == SD_ACT_NONE && a->act2 == SD_ACT_NONE && a->cout <= a->ldo - a->o_col0,
-                 "sd_conv1d_cl_f32_symmetric: needs a square plain product (M=%d cout=%d)", a->M, a->cout);
-  // time-axis convs of small launches: 64x64 tiles through a 4-stage LDS-DMA ring (SD_TUNE_S64_TILES)
-  if (!a->colstat && !symmetric && a->T > 1 && a->M >= S64_T && tiles_m * tiles_n < g_s64_below.load(std::memory_order_relaxed)) {
-    const long nt64 = (a->cout + S64_T - 1) / S64_T;
-    const long g = (long)((a->M + S64_T - 1) / S64_T) * nt64;
-    const size_t lds64 = (size_t)S64_ST * S64_STAGE * sizeof(float);
-    static const int s32 = [] { const char* e = sd_experiment_env("SD_S64_HALF"); return e ? atoi(e) : -1; }();   // 0 | 1: never / always 32-row tiles
-    const bool half = s32 != 0 && (s32 == 1 || g < 128);
-    if (half) SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_s64_kernel<32>, -1, 0.0, ((a->M + 31) / 32) * nt64, 256, lds64, stream, *a, vec));
-    else SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_s64_kernel<64>, -1, 0.0, g, 256, lds64, stream, *a, vec));
-    SD_CHECK_LAUNCH(half ? "conv_gemm_f32_s64_kernel<32>" : "conv_gemm_f32_s64_kernel<64>");
-    return SD_OK;
+namespace {
+
+// Check and choose for the entries of this file (SD_CONV_OP_*, sd_hip_trace.h): what the launching entry and sd_conv_choice_read share.
+// The symmetric form: x == w, M == cout, no epilogue arithmetic; only the tiles on and above the diagonal are computed, each is stored
+// twice (as is and transposed).  SD_CONV_OP_SEG_GEMM: a per-segment layer with caller-provided scratch (scratch_ok: non-null, aligned).
+int decide(const sd_conv_args* a, int op, bool scratch_ok, size_t scratch_bytes, const SdConvTuning& t, SdConvChoice c[2], int* n, int* vec) {
+  if (op == SD_CONV_OP_PACKED) {
+    SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_packed_f32: null args");
+    SD_CHECK_ARG(a->w_dtype == SD_DT_F32 && a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_packed_f32: x / w / y must be f32");
+    if (int e = sd_check_conv(a, {"sd_conv1d_cl_packed_f32", 4, BK, 4, true, true, 0}, vec)) return e;
+    *n = sd_choose_conv_packed(*a, *vec, t, &c[0]) ? 1 : 0;
+  } else {
+    SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f32: null args");
+    SD_CHECK_ARG(a->w_dtype == SD_DT_F32, "sd_conv1d_cl_f32: w_dtype %d not supported by the f32 operator", a->w_dtype);
+    SD_CHECK_ARG(a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_f32: x/y must be f32 (use sd_conv1d_cl_f16 for f16 activations)");
+    if (int e = sd_check_conv(a, {"sd_conv1d_cl_f32", 4, BK, 4, false, true, SD_COLSTAT_T_128}, vec)) return e;
+    if (op == SD_CONV_OP_F32_SYMMETRIC)
+      SD_CHECK_ARG(a->M == a->cout && a->T == 1 && a->taps == 1 && !a->bias && !a->scale && !a->shift && !a->tee && !a->colstat &&
+                   a->act == SD_ACT_NONE && a->act2 == SD_ACT_NONE && a->cout <= a->ldo - a->o_col0,
+                   "sd_conv1d_cl_f32_symmetric: needs a square plain product (M=%d cout=%d)", a->M, a->cout);
+    if (op == SD_CONV_OP_SEG_GEMM) *n = sd_choose_seg_gemm(*a, *vec, scratch_ok, scratch_bytes, t, c);
+    else *n = sd_choose_conv_f32(*a, *vec, op == SD_CONV_OP_F32_SYMMETRIC, op == SD_CONV_OP_F32_STAT_ROWS, t, &c[0]) ? 1 : 0;
   }
-  const long skinny_below = g_skinny_below.load(std::memory_order_relaxed);
-  if (!a->colstat && tiles_m * tiles_n < skinny_below) {
-    const long g = (long)((a->M + SK_T - 1) / SK_T) * ((a->cout + SK_T - 1) / SK_T);
-    // (not counted in the SD_PROF_CONV_GEMM roofline figures: a different kernel, 0.2 % of the flops)
-    SD_CHECK_HIP(sd_launch_conv(skinny_gemm_f32_kernel, -1, 0.0, g, 256, 0, stream, *a));
-    SD_CHECK_LAUNCH("skinny_gemm_f32_kernel");
-    return SD_OK;
-  }
-  // wide outputs of large launches: the 256x256 ring kernel (SD_F32_WIDE=0: A/B switch; no tee_add epilogue, column
-  // statistics only for tiles that span <= 2 segments, at least four rounds of tiles over the CUs)
-  static const bool wide_ok = [] { const char* e = sd_experiment_env("SD_F32_WIDE"); return !(e && e[0] == '0'); }();
-  {
-    const long t256 = ((a->M + WBM - 1) / WBM) * ((a->cout + WBN - 1) / WBN);
-    if (wide_ok && !symmetric && a->cout >= 1024 && t256 >= g_wide_from.load(std::memory_order_relaxed) && t256 > 0 && !(a->tee && a->tee_add) && !(a->colstat && a->T < 128)) {
-      SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_t256_kernel, SD_PROF_CONV_WIDE, sd_conv_flops(a), t256, 512, W_LDS_BYTES, stream, *a, vec));
-      SD_CHECK_LAUNCH("conv_gemm_f32_t256_kernel");
-      return SD_OK;
-    }
-  }
-  // half-width tiles when they shorten the busiest CU's share (SD_TUNE_HALF_TILES / SD_F32_N64=0|1: never / whenever possible).  Measured
-  // (tools/probe_tile_alone.py): a launch takes ~15 us + (tiles on the busiest CU) x 62 us per unit of K = 1024, whether the CU's
-  // tiles run side by side or one after the other; a half tile costs 0.52 of a tile
-  {
-    const long n64 = g_half_tiles.load(std::memory_order_relaxed);
-    const long t128 = tiles_m * tiles_n, t64 = tiles_m * ((a->cout + 63) / 64);
-    const long c128 = (t128 + 255) / 256, c64 = (t64 + 255) / 256;
-    const double cost128 = (double)c128, cost64 = 0.52 * (double)c64;
-    const bool can = !symmetric && (!a->colstat || (a->T >= 128 && a->cout % 64 == 0)) && t64 < (1L << 31);
-    // tiles of 80 / 96 / 112 rows (SD_TUNE_TILE_ROWS): a tile of 16 J rows costs J / 8 of a 128-row tile
-    {
-      const long rows = g_tile_rows.load(std::memory_order_relaxed);
-      int best = 0;
-      double best_cost = 0.97 * (n64 != 0 && can && cost64 < cost128 ? cost64 : cost128);
-      // (column statistics in units of 16 J rows: only for a caller that asked for the unit)
-      // (T > 1: the time-axis convs.  The 16x16x4 MFMA sums four products per step where the 32x32x2 one sums two, so its results differ
-      // from the other kernels' in the last bit; plain products such as the affinity's row blocks (T = 1) keep the bits of the 128x128 kernel)
-      if (!symmetric && a->T > 1 && (!a->colstat || stat_rows) && rows != 0)
-        for (int j = 5; j <= 7; ++j) {
-          if (a->colstat && a->T < (j == 5 ? 80 : 8 * j)) continue;      // a tile may span two (J = 5) / three segments
-          const long tj = ((a->M + 16 * j - 1) / (16 * j)) * tiles_n;
-          const double cj = (double)((tj + 255) / 256) * (double)j / 8.0 * 1.02;
-          if (rows == 16 * j || (rows < 0 && cj < best_cost)) { best = j; best_cost = cj; }
-        }
-      if (best) {
-        const long tj = ((a->M + 16 * best - 1) / (16 * best)) * tiles_n;
-        const VhKernel& k = g_vh_kernels[best - 5];
-        SD_CHECK_HIP(sd_launch_conv(k.fn, SD_PROF_CONV_GEMM, sd_conv_flops(a), tj, 256, k.lds, stream, *a, vec));
-        SD_CHECK_LAUNCH(k.label);
-        if (stat_rows) *stat_rows = 16 * best;
-        return SD_OK;
-      }
-    }
-    if (can && n64 != 0 && (n64 == 1 || cost64 < 0.97 * cost128)) {
-      const size_t lds64 = (size_t)2 * (BM + 64) * BK * sizeof(float);
-      SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_n64_kernel, SD_PROF_CONV_GEMM, sd_conv_flops(a), t64, 256, lds64, stream, *a, vec));
-      SD_CHECK_LAUNCH("conv_gemm_f32_n64_kernel");
-      return SD_OK;
-    }
-  }
-  // SD_F32_DMA=0|1 (diagnostic): operand staging through registers or by LDS-DMA
-  static const int dma = [] {
-    const char* e = sd_experiment_env("SD_F32_DMA");
-    return e ? atoi(e) : SD_F32_DMA_DEFAULT;
-  }();
-  const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);   // the C tile of the epilogue needs BM * LDC <= this
-  static const int order = [] {
-    const char* e = sd_experiment_env("SD_TILE_ORDER");
-    return e ? atoi(e) : 1;
-  }();
-  // SD_PERSIST=<n> (diagnostic): at most n workgroups walk the tile list instead of one workgroup per
-  // tile.  Measured with n = 2 per CU: 2.3 % SLOWER (the dispatcher's dynamic placement beats a static
-  // share of the tiles; dispatch gaps are not what separates the kernel from its K-loop rate).
-  static const int persist = [] {
-    const char* e = sd_experiment_env("SD_PERSIST");
-    return e ? atoi(e) : 0;
-  }();
-  long ntiles = tiles_m * tiles_n;
-  int ord = order;
-  if (symmetric && tiles_n >= 2) {                        // the list of band entries (see the kernel)
-    ntiles = 0;
-    for (long b = 0; 8 * b < tiles_n; ++b) ntiles += (tiles_n - 8 * b < 8 ? tiles_n - 8 * b : 8) * (tiles_n - 8 * b);
-    ord = 2;
-  }
-  const long grid = (persist > 0 && ntiles > persist) ? persist : ntiles;
-  SD_CHECK_HIP(sd_launch_conv(dma ? conv_gemm_f32_kernel<true> : conv_gemm_f32_kernel<false>, SD_PROF_CONV_GEMM, sd_conv_flops(a), grid, 256, lds, stream, *a, vec,
-                              ord, (int)ntiles));
-  // (the register-staged form only under SD_F32_DMA=0, read through sd_experiment_env above)
-  SD_CHECK_LAUNCH(dma ? (symmetric ? "conv_gemm_f32_kernel<dma>/symmetric" : "conv_gemm_f32_kernel<dma>")
-                      : (symmetric ? "conv_gemm_f32_kernel<reg>/symmetric" : "conv_gemm_f32_kernel<reg>"));
+  SD_CHECK_ARG(*n > 0, "%s", c[0].refuse);
   return SD_OK;
 }
 
-// Packed spans: the position-dependent layers (taps > 1: reflect padding inside the span; a per-segment bias: the span's row) on the
-// 128x128 kernel's packed form, whatever sd_set_tuning selects for uniform launches (no other kernel has the span map).  a->T is ignored.
-extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+struct Extra { const int* frame_start; int B; float* part; };     // what the packed kernel and the seg_gemm pair take beside the args
+
+int launch(const sd_conv_args* a, const SdConvChoice& c, int vec, const Extra& x, hipStream_t stream) {
+  const double work = sd_conv_flops(a);
+#define SD_GO(kern, ...) SD_CHECK_HIP(sd_launch_conv(kern, c.prof, work, c.grid, c.block, c.lds, stream, __VA_ARGS__)); break
+  switch (c.kernel) {
+    case SD_K_F32_S64_32: SD_GO(conv_gemm_f32_s64_kernel<32>, *a, vec);
+    case SD_K_F32_S64_64: SD_GO(conv_gemm_f32_s64_kernel<64>, *a, vec);
+    case SD_K_F32_SKINNY: SD_GO(skinny_gemm_f32_kernel, *a);
+    case SD_K_F32_T256: SD_GO(conv_gemm_f32_t256_kernel, *a, vec);
+    case SD_K_F32_VH5: SD_GO(conv_gemm_f32_vh_kernel<5>, *a, vec);
+    case SD_K_F32_VH6: SD_GO(conv_gemm_f32_vh_kernel<6>, *a, vec);
+    case SD_K_F32_VH7: SD_GO(conv_gemm_f32_vh_kernel<7>, *a, vec);
+    case SD_K_F32_N64: SD_GO(conv_gemm_f32_n64_kernel, *a, vec);
+    case SD_K_F32_128: case SD_K_F32_128_SYMMETRIC: SD_GO(conv_gemm_f32_kernel<true>, *a, vec, c.order, c.ntiles);
+    case SD_K_F32_PACKED: SD_GO(conv_gemm_f32_packed_kernel, *a, vec, x.frame_start, x.B);
+    case SD_K_SEG_PARTIAL: SD_CHECK_HIP(sd_launch_conv(seg_gemm_partial_f32_kernel, -1, 0.0, c.grid, c.block, c.lds, stream, *a, c.nsplit, c.groups, x.part)); break;
+    case SD_K_SEG_REDUCE: SD_GO(seg_gemm_reduce_f32_kernel, *a, c.nsplit, static_cast<const float*>(x.part));
+    default: return sd_set_error(SD_ERR_ARG, "sd_conv1d_cl_f32: no kernel %d in this operator", c.kernel);
+  }
+#undef SD_GO
+  SD_CHECK_LAUNCH(c.label);
+  return SD_OK;
+}
+
+}  // namespace
+
+// stat_rows != nullptr: a caller that can take the column statistics in units other than 128 rows (the ECAPA schedule); it receives
+// the unit the launch used (128, or the 80 / 96 / 112 rows of the variable-height kernel), for sd_colstat_finish_rows.
+int sd_conv1d_cl_f32_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t, int* stat_rows) {
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = decide(a, stat_rows ? SD_CONV_OP_F32_STAT_ROWS : SD_CONV_OP_F32, false, 0, t, c, &n, &vec)) return e;
+  if (stat_rows) *stat_rows = c[0].stat_rows;
+  return launch(a, c[0], vec, {}, static_cast<hipStream_t>(stream));
+}
+extern "C" int sd_conv1d_cl_f32(const sd_conv_args* a, sd_stream_t stream) { return sd_conv1d_cl_f32_with(a, stream, sd_conv_tuning_now(), nullptr); }
+
+// Internal (sd_common.h): the affinity's full-matrix call.
+int sd_conv1d_cl_f32_symmetric(const sd_conv_args* a, sd_stream_t stream) {
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = decide(a, SD_CONV_OP_F32_SYMMETRIC, false, 0, sd_conv_tuning_now(), c, &n, &vec)) return e;
+  return launch(a, c[0], vec, {}, static_cast<hipStream_t>(stream));
+}
+
+// Packed spans: the position-dependent layers (taps > 1: reflect padding inside the span; a per-segment bias: the span's row).  a->T is ignored.
+int sd_conv1d_cl_packed_f32_with(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream, const SdConvTuning& t) {
   SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_packed_f32: null args");
   SD_CHECK_ARG(B >= 1 && frame_start_dev != nullptr, "sd_conv1d_cl_packed_f32: B=%d, frame_start %p", B, (const void*)frame_start_dev);
-  SD_CHECK_ARG(a->w_dtype == SD_DT_F32 && a->x_dtype == SD_DT_F32 && a->y_dtype == SD_DT_F32, "sd_conv1d_cl_packed_f32: x / w / y must be f32");
-  int vec;
-  if (int e = sd_check_conv(a, {"sd_conv1d_cl_packed_f32", 4, BK, 4, true, true, 0}, &vec)) return e;
-  const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
-  SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_packed_f32: grid too large");
-  const size_t lds = (size_t)2 * (BM + BN) * LDP * sizeof(float);     // as the uniform launch: the epilogue's C tile needs BM * LDC
-  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f32_packed_kernel, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles, 256, lds, stream, *a, vec, frame_start_dev, B));
-  SD_CHECK_LAUNCH("conv_gemm_f32_packed_kernel");
-  return SD_OK;
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = decide(a, SD_CONV_OP_PACKED, false, 0, t, c, &n, &vec)) return e;
+  return launch(a, c[0], vec, {frame_start_dev, B, nullptr}, static_cast<hipStream_t>(stream));
 }
-
-// a split = 4 waves x `groups` k-groups of 8: 256 values of K for the long layers, 128 below 2048
-static int seg_gemm_shape(int M, int cin_pad, int cout, int* groups, int* nsplit, long* tiles) {
-  if (M <= 0 || M > 256 || cin_pad < 512 || cin_pad % 32 != 0 || cout <= 0) return 0;
-  *groups = cin_pad >= 2048 ? 8 : 4;
-  *nsplit = (int)(((long)cin_pad + 32 * *groups - 1) / (32 * *groups));
-  *tiles = (long)((M + SK_T - 1) / SK_T) * (((long)cout + SK_T - 1) / SK_T);
-  return *nsplit >= 2;
+extern "C" int sd_conv1d_cl_packed_f32(const sd_conv_args* a, const int* frame_start_dev, int B, sd_stream_t stream) {
+  return sd_conv1d_cl_packed_f32_with(a, frame_start_dev, B, stream, sd_conv_tuning_now());
 }
 
 extern "C" size_t sd_seg_gemm_scratch_bytes(int M, int cin_pad, int cout) {
   int groups, nsplit; long tiles;
-  if (!seg_gemm_shape(M, cin_pad, cout, &groups, &nsplit, &tiles)) return 0;
-  return (size_t)tiles * nsplit * SK_T * SK_T * sizeof(float);
+  return sd_seg_gemm_shape(M, cin_pad, cout, &groups, &nsplit, &tiles) ? sd_seg_gemm_scratch(tiles, nsplit) : 0;
 }
 
-// Per-segment layer (T == 1) with caller-provided scratch: K split over the grid when the launch is small and K long (the two kernels
-// above), otherwise sd_conv1d_cl_f32: the ECAPA schedule's SE squeeze FC, global-context bias and final FC.
+// Per-segment layer (T == 1): the ECAPA schedule's SE squeeze FC, global-context bias and final FC.  One record of SD_PROF_SEG_SPLITK
+// spans the pair of launches.
+int sd_seg_gemm_f32_with(const sd_conv_args* a, void* scratch, size_t scratch_bytes, sd_stream_t stream_, const SdConvTuning& t) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = decide(a, SD_CONV_OP_SEG_GEMM, scratch && sd_aligned16(scratch), scratch_bytes, t, c, &n, &vec)) return e;
+  if (n == 1) return launch(a, c[0], vec, {}, stream);
+  SdProfScope prof(c[0].prof, stream, sd_conv_flops(a));
+  const Extra x = {nullptr, 0, static_cast<float*>(scratch)};
+  if (int e = launch(a, c[0], vec, x, stream)) return e;
+  return launch(a, c[1], vec, x, stream);
+}
 extern "C" int sd_seg_gemm_f32(const sd_conv_args* a, void* scratch, size_t scratch_bytes, sd_stream_t stream) {
-  static const bool on = [] { const char* e = sd_experiment_env("SD_SEG_SPLITK"); return !(e && e[0] == '0'); }();
-  if (!on || !a || !scratch || a->T != 1 || a->taps != 1 || a->tee || a->colstat || a->w_dtype != SD_DT_F32 || a->x_dtype != SD_DT_F32 ||
-      a->y_dtype != SD_DT_F32 || a->M <= 0 || a->M > 256 || a->cin_pad < 512 || a->cin_pad % 32 != 0 || a->cin % 4 != 0 || a->lda % 4 != 0 ||
-      a->a_col0 % 4 != 0 || !sd_aligned16(a->x) || !sd_aligned16(a->w) || !sd_aligned16(scratch))
-    return sd_conv1d_cl_f32(a, stream);
-  int groups, nsplit; long tiles;
-  if (!seg_gemm_shape(a->M, a->cin_pad, a->cout, &groups, &nsplit, &tiles) || (size_t)tiles * nsplit * SK_T * SK_T * sizeof(float) > scratch_bytes ||
-      !a->x || !a->w || !a->y || a->cin <= 0 || a->cin > a->cin_pad || a->o_col0 < 0 || a->o_col0 + a->cout > a->ldo || a->a_col0 < 0 || a->a_col0 + a->cin > a->lda)
-    return sd_conv1d_cl_f32(a, stream);
-  float* part = static_cast<float*>(scratch);
-  SdProfScope prof(SD_PROF_SEG_SPLITK, static_cast<hipStream_t>(stream), 2.0 * (double)a->M * (double)a->cout * (double)a->cin);
-  hipLaunchKernelGGL(seg_gemm_partial_f32_kernel, dim3((unsigned)(tiles * nsplit)), dim3(256), 0, static_cast<hipStream_t>(stream), *a, nsplit, groups, part);
-  SD_CHECK_LAUNCH("seg_gemm_partial_f32_kernel");
-  hipLaunchKernelGGL(seg_gemm_reduce_f32_kernel, dim3((unsigned)(tiles * 4)), dim3(256), 0, static_cast<hipStream_t>(stream), *a, nsplit, part);
-  SD_CHECK_LAUNCH("seg_gemm_reduce_f32_kernel");
-  return SD_OK;
+  return sd_seg_gemm_f32_with(a, scratch, scratch_bytes, stream, sd_conv_tuning_now());
+}
+
+// The choice as text (sd_hip_trace.h): the same decide(), no launch, no device
+extern "C" size_t sd_conv_choice_read(const sd_conv_args* a, int op, int n_cu, size_t scratch_bytes, char* buf, size_t cap) {
+  const SdConvTuning t = sd_conv_tuning_now(n_cu < 0 ? 0 : n_cu);
+  SdConvChoice c[2];
+  int n = 0, vec = 0, e;
+  if (op == SD_CONV_OP_F16 || op == SD_CONV_OP_SPLIT16) e = sd_conv_f16_decide(a, op, t, c, &n, &vec);
+  else if (op >= SD_CONV_OP_F32 && op <= SD_CONV_OP_SEG_GEMM) e = decide(a, op, scratch_bytes > 0, scratch_bytes, t, c, &n, &vec);
+  else e = sd_set_error(SD_ERR_ARG, "sd_conv_choice_read: unknown op %d", op);
+  if (e != SD_OK) return 0;
+  char text[2 * 160];
+  size_t len = 0;
+  for (int i = 0; i < n; ++i)
+    len += (size_t)snprintf(text + len, sizeof(text) - len, "%s\t%ld\t%d\t%zu\t%d\n", c[i].label, c[i].grid, c[i].block, c[i].lds, c[i].stat_rows);
+  if (buf && cap) {
+    const size_t nb = len < cap - 1 ? len : cap - 1;
+    memcpy(buf, text, nb);
+    buf[nb] = 0;
+  }
+  return len + 1;
 }

@@ -16,6 +16,7 @@
 #include "sd_common.h"
 #include "sd_conv_tile.h"
 #include "sd_epilogue.h"
+#include "sd_hip_trace.h"
 #include <cstdlib>
 
 namespace {
@@ -558,251 +559,6 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_f16_t256_kernel(const sd_con
 #endif
 }
 
-// ------------------------------------------------------------------------------------------
-// EXPERIMENT, compiled only into variant builds (build_native.py --variant w4 "-DSD_WITH_W4", selected at run time with
-// SD_EXPERIMENT=1 SD_F16_W4=1): the same 256x256 tile and LDS-DMA ring with FOUR waves of 128 x 128.  A K step's
-// fragment reads drop from 8 x 24 KB to 4 x 32 KB (the 8-wave form moves 192 KB of reads + 64 KB of DMA writes per step through a
-// 128 B/clk LDS for 2048 cycles of matrix work), at the price of one wave per SIMD: its 256 accumulator registers live in AGPRs
-// (200 VGPRs + 256 AGPRs, no spill, no v_accvgpr copy in the loop), nothing hides a stall but the wave's own instruction stream.
-// f16 operands, register (DIRECT) epilogue only.  Per step and wave: 128 MFMAs, 32 ds_read_b128 in two sets of 64 registers
-// (k slice 0 / 1), 16 DMA pieces (the weights of step k + 1, the activations of step k + 2); the barrier sits in front of the
-// step's LAST 64 MFMAs.  The loop body is straight-line and pinned chunk by chunk with sched_barrier (ISA: MMMMMMMM RRR D x 16 per
-// step, two waits, one barrier).  Passes tests/test_gpu_f16.py (158 tests).  Measured against the shipped 8-wave kernel, same box,
-// 1 005 000 rows: 1024 x 1024 871-873 vs 900-912 TFLOP/s, 3072 x 3072 1147-1149 vs 1120-1121 (first cut, compiler-scheduled: 858 /
-// 1159 vs 898 / 1151).  Not shipped: a wave that is alone on its SIMD stands still whenever one of its 16 DMA pieces waits for a
-// slot in the CU's vector-memory queue (round 2: 70-100 cycles per piece with four waves issuing), and with 456 registers per wave
-// there is no room for loader waves beside it.
-#ifdef SD_WITH_W4
-template <typename TO>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_gemm_f16_w4_kernel(const sd_conv_args p, const int vec) {
-  constexpr int TBK = 64;
-  constexpr int TROW = 128;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid >> 1, wn = wid & 1;
-  const int n_tiles = (p.cout + TBN - 1) / TBN;
-  const int wg = sd_xcd_tile(blockIdx.x, gridDim.x);
-  const int tile_n = wg % n_tiles, tile_m = wg / n_tiles;
-  const int m0 = tile_m * TBM, n0 = tile_n * TBN;
-
-  // staging role: thread (r0 = tid / 8, ps = tid % 8) fills physical 16-byte slot ps of rows r0 + 32 i (i < 8) of BOTH operands.
-  // Addresses = a workgroup-uniform base (SGPRs) + a 32-bit per-lane element offset: 16 address registers instead of 32.
-  const int r0 = tid >> 3;
-  const int ls8 = ((tid & 7) ^ ((r0 >> 1) & 7)) * 8;
-  const int ktot = p.taps * p.cin_pad;
-  const int nk = p.taps * (p.cin_pad / TBK);
-  const int half = p.taps / 2;
-  int m0c = m0 < p.M ? m0 : p.M - 1;
-  const _Float16* const Ab = static_cast<const _Float16*>(p.x) + p.a_col0 + (size_t)m0c * p.lda;      // row m0 of the activations
-  int n0c = n0 < p.cout ? n0 : p.cout - 1;
-  const _Float16* Wb = static_cast<const _Float16*>(p.w) + (size_t)n0c * ktot;                        // row n0 of the weights, advanced per K step
-  int pa[8], pb[8];
-  auto set_tap = [&](int tap) {
-    const int delta = (tap - half) * p.dil;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      int m = m0 + r0 + 32 * i;
-      m = m < p.M ? m : p.M - 1;
-      const int seg = (m / p.T) * p.T;
-      int tt = m - seg + delta;
-      tt = sd_reflect(tt, p.T);
-      pa[i] = (seg + tt - m0c) * p.lda;                 // |rows| < 256 + T: fits 32 bits for any lda this library accepts
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int n = n0 + r0 + 32 * i;
-    n = n < p.cout ? n : p.cout - 1;
-    pb[i] = (n - n0c) * ktot + ls8;
-  }
-  set_tap(0);
-  int ld_tap = 0, ld_c0 = 0;
-  char* const dst = smem_raw + (wid * 8) * TROW;
-  auto issue_b = [&](int st) {
-    char* base = dst + R3_B_BASE + st * R3_B_STAGE;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) SD_GLDS16(Wb + pb[i], base + i * 32 * TROW);
-    Wb += TBK;
-  };
-  auto issue_a = [&](int st) {
-    char* base = dst + st * R3_A_STAGE;
-    const int col = ld_c0 + ls8;
-    const int acol = col < p.cin ? col : 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) SD_GLDS16(Ab + (pa[i] + acol), base + i * 32 * TROW);
-    ld_c0 += TBK;
-    if (ld_c0 >= p.cin_pad) {
-      ld_c0 = 0;
-      ++ld_tap;
-      if (ld_tap < p.taps) set_tap(ld_tap);
-    }
-  };
-
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
-  f32x4v acc0[8][4], acc1[8][4];          // [16-row time tile][16-channel tile]: channels 0-63 / 64-127 of the wave's 128
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { acc0[i][j][r] = 0.f; acc1[i][j][r] = 0.f; }
-  const int fr = lane & 15, fq = lane >> 4;
-  const int ab_sw = (fr >> 1) & 7;
-  const char* const a_base = smem_raw + (wm * 128 + fr) * TROW;
-  const char* const b_base = smem_raw + R3_B_BASE + (wn * 128 + fr) * TROW;
-  const int so0 = (fq ^ ab_sw) << 4, so1 = ((4 + fq) ^ ab_sw) << 4;
-
-  h8 xa[8], xb[8], ya[8], yb[8];          // fragment sets of k slice 0 (x) and 1 (y)
-#define W4_READ(fa_, fb_, sa_, sb_, so_)                                                                          \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                 \
-    fa_[i] = *reinterpret_cast<const h8*>(a_base + (sa_) * R3_A_STAGE + i * 16 * TROW + (so_));                   \
-    fb_[i] = *reinterpret_cast<const h8*>(b_base + (sb_) * R3_B_STAGE + i * 16 * TROW + (so_));                   \
-  }
-#define W4_MMA(fa_, fb_)                                                                                          \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                 \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                               \
-      acc0[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb_[j], fa_[i], acc0[i][j], 0, 0, 0);                   \
-      acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb_[4 + j], fa_[i], acc1[i][j], 0, 0, 0);               \
-    }                                                                                                             \
-  }
-
-  issue_b(0);
-  issue_a(0);
-  if (nk > 1) issue_a(1);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ya[i][e] = (_Float16)0.f; yb[i][e] = (_Float16)0.f; }     // the first step's "deferred" slice adds zeros
-  int sa = 0, sb = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    // ---- barrier(kt): this step's stages have landed, every wave holds the previous step's last fragments in registers
-    if (kt + 1 >= nk) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");        // the activations of step kt + 1 stay in flight
-    __builtin_amdgcn_s_barrier();
-    const int sa2 = sa == 0 ? 2 : sa - 1;                                    // the A stage of step kt - 1
-    // One straight-line body, instruction order pinned chunk by chunk (left to itself hipcc sinks the 16 fragment reads of a half
-    // step behind ~58 of the 64 MFMAs they should run under and waits for them right after): a chunk = the two fragment reads of row
-    // tile i of the NEXT k slice, one DMA piece, and the 8 MFMAs of row tile i of the slice whose fragments are complete.  Past the
-    // last step the DMA pieces are re-reads of valid addresses into stages nobody reads (no branch in the body).
-    const bool hb = kt + 1 < nk, ha = kt + 2 < nk;
-    const char* const ar = a_base + sa * R3_A_STAGE;
-    const char* const br = b_base + sb * R3_B_STAGE;
-    char* const bdst = dst + R3_B_BASE + (sb ^ 1) * R3_B_STAGE;
-    char* const adst = dst + sa2 * R3_A_STAGE;
-    const int col = ld_c0 + ls8;
-    const int acol = (ha && col < p.cin) ? col : 0;
-    const _Float16* const Wk = hb ? Wb : Wb - TBK;
-    // chunk i = the 8 MFMAs of row tile i, then (chunks 0-5 only) fragment reads of the next slice: 3, 3, 3, 3, 2, 2 — the last two
-    // chunks' MFMAs cover the latency of the last reads, so the next half step starts without a wait
-#define W4_Q(k_) ((k_) < 8 ? 8 + (k_) : (k_) - 8)          /* k-th fragment read: all 8 b, then a[0..7], the order the consumer needs them */
-#define W4_RD(fa_, fb_, q_, so_)                                                                              \
-  do {                                                                                                       \
-    if ((q_) < 8) fa_[(q_)] = *reinterpret_cast<const h8*>(ar + (q_) * 16 * TROW + (so_));                    \
-    else fb_[(q_) - 8] = *reinterpret_cast<const h8*>(br + ((q_) - 8) * 16 * TROW + (so_));                   \
-  } while (0)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {                                            // deferred k slice 1 of step kt - 1
-        acc0[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(yb[j], ya[i], acc0[i][j], 0, 0, 0);
-        acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(yb[4 + j], ya[i], acc1[i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (i < 4) { W4_RD(xa, xb, W4_Q(3 * i), so0); W4_RD(xa, xb, W4_Q(3 * i + 1), so0); W4_RD(xa, xb, W4_Q(3 * i + 2), so0); }
-      else if (i < 6) { W4_RD(xa, xb, W4_Q(12 + 2 * (i - 4)), so0); W4_RD(xa, xb, W4_Q(13 + 2 * (i - 4)), so0); }
-      SD_GLDS16(Wk + pb[i], bdst + i * 32 * TROW);                             // the weights of step kt + 1
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc0[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xb[j], xa[i], acc0[i][j], 0, 0, 0);
-        acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xb[4 + j], xa[i], acc1[i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (i < 4) { W4_RD(ya, yb, W4_Q(3 * i), so1); W4_RD(ya, yb, W4_Q(3 * i + 1), so1); W4_RD(ya, yb, W4_Q(3 * i + 2), so1); }
-      else if (i < 6) { W4_RD(ya, yb, W4_Q(12 + 2 * (i - 4)), so1); W4_RD(ya, yb, W4_Q(13 + 2 * (i - 4)), so1); }
-      SD_GLDS16(Ab + (pa[i] + acol), adst + i * 32 * TROW);                    // the activations of step kt + 2
-    }
-#undef W4_RD
-#undef W4_Q
-    __builtin_amdgcn_sched_barrier(0);
-    if (hb) Wb += TBK;
-    if (ha) {
-      ld_c0 += TBK;
-      if (ld_c0 >= p.cin_pad) {
-        ld_c0 = 0;
-        ++ld_tap;
-        if (ld_tap < p.taps) set_tap(ld_tap);
-      }
-    }
-    sa = sa == 2 ? 0 : sa + 1;
-    sb ^= 1;
-  }
-  W4_MMA(ya, yb);
-#undef W4_READ
-#undef W4_MMA
-  sd_direct_epilogue<TO>(p, acc0, m0 + wm * 128, n0 + wn * 128, fr, fq);
-  sd_direct_epilogue<TO>(p, acc1, m0 + wm * 128, n0 + wn * 128 + 64, fr, fq);
-}
-
-template <typename TO>
-int launch_w4(const sd_conv_args* a, int vec, hipStream_t stream) {
-  const long tiles_m = (a->M + TBM - 1) / TBM;
-  const long tiles_n = (a->cout + TBN - 1) / TBN;
-  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_w4_kernel<TO>, SD_PROF_CONV_WIDE, sd_conv_flops(a), tiles_m * tiles_n, 256, R3_LDS_BYTES, stream, *a, vec));
-  SD_CHECK_LAUNCH(sizeof(TO) == 2 ? "conv_gemm_f16_w4_kernel<f16>" : "conv_gemm_f16_w4_kernel<f32>");
-  return SD_OK;
-}
-#endif  // SD_WITH_W4
-
-// the launch label of an instantiation and its walk (sd_common.h SD_CHECK_LAUNCH)
-template <typename TO, bool DIRECT, bool SPLIT>
-constexpr const char* t256_label(bool super) {
-  if constexpr (SPLIT) {
-    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<split,direct>/lockstep" : "conv_gemm_f16_t256_kernel<split,direct>/grid";
-    else return "conv_gemm_f16_t256_kernel<split,staged>/grid";
-  } else if constexpr (sizeof(TO) == 2) {
-    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<f16,direct>/lockstep" : "conv_gemm_f16_t256_kernel<f16,direct>/grid";
-    else return "conv_gemm_f16_t256_kernel<f16,staged>/grid";
-  } else {
-    if constexpr (DIRECT) return super ? "conv_gemm_f16_t256_kernel<f32,direct>/lockstep" : "conv_gemm_f16_t256_kernel<f32,direct>/grid";
-    else return "conv_gemm_f16_t256_kernel<f32,staged>/grid";
-  }
-}
-
-template <typename TO, bool DIRECT, bool SPLIT = false>
-int launch_t256(const sd_conv_args* a, int vec, hipStream_t stream) {
-  const long tiles_m = (a->M + TBM - 1) / TBM;
-  const long tiles_n = (a->cout + TBN - 1) / TBN;
-  // the super-tile walk (256 persistent workgroups, 8 x 4 tiles per XCD and pass) when the tile list is several rounds long, the chip has 8 x 32
-  // CUs and the column tiles come in fours (sd_set_tuning(SD_TUNE_T256_LOCKSTEP_TILES): from how many tiles; default 4 x the CU count)
-  static const int n_cu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
-  const long total = tiles_m * tiles_n;
-  long from = sd_t256_lockstep_tiles().load(std::memory_order_relaxed);
-  if (from < 0) from = 4L * 256;
-  const bool super = DIRECT && n_cu == 256 && tiles_n % 4 == 0 && total < (1L << 30) && total >= from;
-  // work = the algorithmic (f32-equivalent) flops: a split row carries cin / 2 values
-  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_t256_kernel<TO, DIRECT, SPLIT>, SD_PROF_CONV_WIDE, (SPLIT ? 0.5 : 1.0) * sd_conv_flops(a), super ? 256L : total, 512,
-                              R3_LDS_BYTES, stream, *a, vec, super ? 1 : 0));
-  SD_CHECK_LAUNCH((t256_label<TO, DIRECT, SPLIT>(super)));
-  return SD_OK;
-}
-
-template <typename TA, typename TO>
-int launch(const sd_conv_args* a, int vec, hipStream_t stream) {
-  const long tiles_m = (a->M + BM - 1) / BM;
-  const long tiles_n = (a->cout + BN - 1) / BN;
-  SD_CHECK_HIP(sd_launch_conv(conv_gemm_f16_kernel<TA, TO>, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles_m * tiles_n, 256, STAGE_BYTES, stream, *a, vec));
-  SD_CHECK_LAUNCH(sizeof(TA) == 2 ? (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f16,f16>" : "conv_gemm_f16_kernel<f16,f32>")
-                                  : (sizeof(TO) == 2 ? "conv_gemm_f16_kernel<f32,f16>" : "conv_gemm_f16_kernel<f32,f32>"));      // <x, y>
-  return SD_OK;
-}
-
 }  // namespace
 
 #ifdef SD_STAMP
@@ -812,63 +568,6 @@ extern "C" int sd_debug_read_stamps(unsigned long long* out, int n) {
   return SD_OK;
 }
 #endif
-
-std::atomic<long>& sd_t256_lockstep_tiles() {
-  static std::atomic<long> v{-1L};
-  return v;
-}
-
-std::atomic<long>& sd_f16_narrow_tiles() {
-  static std::atomic<long> v{128L};
-  return v;
-}
-
-extern "C" int sd_conv1d_cl_f16(const sd_conv_args* a, sd_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f16: null args");
-  SD_CHECK_ARG(a->w_dtype == SD_DT_F16, "sd_conv1d_cl_f16: weights must be packed f16 (w_dtype=%d)", a->w_dtype);
-  SD_CHECK_ARG((a->x_dtype == SD_DT_F32 || a->x_dtype == SD_DT_F16) && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_F16),
-               "sd_conv1d_cl_f16: bad x_dtype/y_dtype %d/%d", a->x_dtype, a->y_dtype);
-  int vec;
-  if (int e = sd_check_conv(a, {"sd_conv1d_cl_f16", 8, BK, 8, false, true, 64}, &vec)) return e;
-  const long tiles = (long)((a->M + BM - 1) / BM) * ((a->cout + BN - 1) / BN);
-  SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_f16: grid too large");
-  const bool xa = a->x_dtype == SD_DT_F16, ya = a->y_dtype == SD_DT_F16;
-  // Kernel choice, measured per shape on MI355X (tools/probe_conv.py, B*T = 1 005 000 rows): the 256x256
-  // LDS-DMA kernel wins wherever the output is wide (3072x3072: 987 vs ~800 TFLOP/s, 1024x1024: 789 vs
-  // 726, 128->3072: 342 vs 315); the register-staged 128x128 kernel with two workgroups per CU is faster
-  // on the narrow outputs (Res2Net 128x384: 555, 3072->128: 530 vs 408) and is the only one with the
-  // tee_add epilogue.  SD_F16_KERNEL=reg|t256 forces one kernel for A/B runs.
-  static const int forced = [] {
-    const char* e = sd_experiment_env("SD_F16_KERNEL");
-    if (!e) return -1;
-    return e[0] == 'r' ? 0 : e[0] == 't' ? 2 : -1;
-  }();
-  // ... except for small launches of the C-wide layers (round 3, tools/sweep_f16.py: 1024 -> 1024 at 16 / 32 segments 0.024 / 0.030 ms
-  // on the 128x128 kernel against 0.035 / 0.038; from 64 segments up, and for 3C -> 3C always, the 256x256 kernel wins): at most 128
-  // tiles of 256x256 -> two workgroups of 128x128 per CU fill the chip better than a fraction of one round of big tiles
-  const long t256 = (long)((a->M + TBM - 1) / TBM) * ((a->cout + TBN - 1) / TBN);
-  const bool wide = a->cout >= 1024 && !(a->cout <= 1024 && t256 <= sd_f16_narrow_tiles().load(std::memory_order_relaxed));
-  const int choice = forced >= 0 ? forced : (wide ? 2 : 0);
-  // (the 256x256 kernel: no tee_add epilogue, and column statistics only for tiles that span <= 2 segments)
-  if (xa && choice == 2 && !(a->tee && a->tee_add) && !(a->colstat && a->T < 128)) {
-    static const bool direct_ok = [] {     // SD_T256_DIRECT=0: the LDS-staged epilogue for every layer (A/B runs)
-      const char* e = sd_experiment_env("SD_T256_DIRECT");
-      return !(e && e[0] == '0');
-    }();
-    const bool plain = vec && (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg && !a->tee;
-#ifdef SD_WITH_W4
-    static const bool w4 = [] { const char* e = sd_experiment_env("SD_F16_W4"); return e && e[0] == '1'; }();     // A/B: the 4-wave form
-    if (plain && direct_ok && w4) return ya ? launch_w4<_Float16>(a, vec, stream) : launch_w4<float>(a, vec, stream);
-#endif
-    if (plain && direct_ok) return ya ? launch_t256<_Float16, true>(a, vec, stream) : launch_t256<float, true>(a, vec, stream);
-    return ya ? launch_t256<_Float16, false>(a, vec, stream) : launch_t256<float, false>(a, vec, stream);
-  }
-  if (xa && ya) return launch<_Float16, _Float16>(a, vec, stream);
-  if (xa && !ya) return launch<_Float16, float>(a, vec, stream);
-  if (!xa && ya) return launch<float, _Float16>(a, vec, stream);
-  return launch<float, float>(a, vec, stream);
-}
 
 // ------------------------------------------------------------------------------------------ f32-split16x3
 namespace {
@@ -922,44 +621,86 @@ extern "C" int sd_split16_pack_f32(const float* x, int ldx, int col0, int M, int
   return SD_OK;
 }
 
+// ------------------------------------------------------------------------------------------ host: check, choose, launch
+// (the choice: sd_conv_choice.h, whose geometry must be this file's)
+static_assert(SD_T128 == BM && SD_T128 == BN && SD_T256 == TBM && SD_T256 == TBN && SD_LDS_F16_128 == (size_t)STAGE_BYTES && SD_LDS_T256 == (size_t)R3_LDS_BYTES,
+              "sd_conv_choice.h: tile sizes and LDS bytes");
 
-// x plain f32 (split while staging): the 128x128 kernel
-static int conv1d_cl_split16_narrow(const sd_conv_args* a, hipStream_t stream) {
-  SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16), "sd_conv1d_cl_split16: w must be SD_DT_SPLIT16, y f32 or SD_DT_SPLIT16");
-  SD_CHECK_ARG(!a->colstat, "sd_conv1d_cl_split16: column statistics come from the 256x256 kernel (SD_DT_SPLIT16 x) only");
-  int vec;      // (sd_store_tile's groups of 8 columns)
-  if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 4, 32, 8, false, true, 0}, &vec)) return e;
-  const long tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->cout + BN - 1) / BN;
-  SD_CHECK_ARG(tiles_m * tiles_n < (1L << 31), "sd_conv1d_cl_split16: grid too large");
-  if (a->y_dtype == SD_DT_SPLIT16)      // y written as split halves by the shared epilogue's vector path (ldo in VALUE columns)
-    SD_CHECK_ARG(vec && a->ldo % 32 == 0, "sd_conv1d_cl_split16: an SD_DT_SPLIT16 output needs ldo %% 32 == 0 and the aligned (vector) epilogue (ldo=%d o_col0=%d cout=%d)",
-                 a->ldo, a->o_col0, a->cout);
-  SD_CHECK_HIP(sd_launch_conv(conv_gemm_split16_n128_kernel<float>, SD_PROF_CONV_GEMM, sd_conv_flops(a), tiles_m * tiles_n, 256, STAGE_BYTES, stream, *a, vec));
-  SD_CHECK_LAUNCH("conv_gemm_split16_n128_kernel");
+// Check and choose of sd_conv1d_cl_f16 and sd_conv1d_cl_split16 (op: SD_CONV_OP_*): what they share with sd_conv_choice_read
+int sd_conv_f16_decide(const sd_conv_args* a, int op, const SdConvTuning& t, SdConvChoice c[2], int* n, int* vec) {
+  if (op == SD_CONV_OP_F16) {
+    SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_f16: null args");
+    SD_CHECK_ARG(a->w_dtype == SD_DT_F16, "sd_conv1d_cl_f16: weights must be packed f16 (w_dtype=%d)", a->w_dtype);
+    SD_CHECK_ARG((a->x_dtype == SD_DT_F32 || a->x_dtype == SD_DT_F16) && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_F16),
+                 "sd_conv1d_cl_f16: bad x_dtype/y_dtype %d/%d", a->x_dtype, a->y_dtype);
+    if (int e = sd_check_conv(a, {"sd_conv1d_cl_f16", 8, BK, 8, false, true, SD_COLSTAT_T_128}, vec)) return e;
+    *n = sd_choose_conv_f16(*a, *vec, t, &c[0]) ? 1 : 0;
+  } else {
+    SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_split16: null args");
+    SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_split16: null x/w/y");
+    const bool y_ok = a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16;
+    if (a->x_dtype == SD_DT_F32) {      // x plain f32, split while staged
+      SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && y_ok, "sd_conv1d_cl_split16: w must be SD_DT_SPLIT16, y f32 or SD_DT_SPLIT16");
+      SD_CHECK_ARG(!a->colstat, "sd_conv1d_cl_split16: column statistics come from the 256x256 kernel (SD_DT_SPLIT16 x) only");
+      // (vec: sd_store_tile's groups of 8 columns)
+      if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 4, 32, 8, false, true, 0}, vec)) return e;
+    } else {
+      SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && a->x_dtype == SD_DT_SPLIT16 && y_ok,
+                   "sd_conv1d_cl_split16: x and w must be split-packed (SD_DT_SPLIT16), y f32 or SD_DT_SPLIT16 (got %d/%d/%d)", a->x_dtype, a->w_dtype, a->y_dtype);
+      // (value columns in groups of 32: the operand is cin_pad values wide)
+      if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 32, 32, 8, false, false, SD_COLSTAT_T_256}, vec)) return e;
+    }
+    if (a->y_dtype == SD_DT_SPLIT16)      // y written as split halves by the staged epilogue's vector path (ldo in VALUE columns)
+      SD_CHECK_ARG(*vec && a->ldo % 32 == 0 && !a->colstat,
+                   "sd_conv1d_cl_split16: an SD_DT_SPLIT16 output needs ldo %% 32 == 0, aligned slices and no column statistics (ldo=%d o_col0=%d cout=%d)",
+                   a->ldo, a->o_col0, a->cout);
+    *n = sd_choose_conv_split16(*a, *vec, t, &c[0]) ? 1 : 0;
+  }
+  SD_CHECK_ARG(*n > 0, "%s", c[0].refuse);
   return SD_OK;
 }
 
-extern "C" int sd_conv1d_cl_split16(const sd_conv_args* a, sd_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(a != nullptr, "sd_conv1d_cl_split16: null args");
-  SD_CHECK_ARG(a->x && a->w && a->y, "sd_conv1d_cl_split16: null x/w/y");
-  if (a->x_dtype == SD_DT_F32) return conv1d_cl_split16_narrow(a, stream);
-  SD_CHECK_ARG(a->w_dtype == SD_DT_SPLIT16 && a->x_dtype == SD_DT_SPLIT16 && (a->y_dtype == SD_DT_F32 || a->y_dtype == SD_DT_SPLIT16),
-               "sd_conv1d_cl_split16: x and w must be split-packed (SD_DT_SPLIT16), y f32 or SD_DT_SPLIT16 (got %d/%d/%d)", a->x_dtype, a->w_dtype, a->y_dtype);
-  int vec;      // (value columns in groups of 32: the operand is cin_pad values wide)
-  if (int e = sd_check_conv(a, {"sd_conv1d_cl_split16", 32, 32, 8, false, false, 128}, &vec)) return e;
-  const long tiles = (long)((a->M + TBM - 1) / TBM) * ((a->cout + TBN - 1) / TBN);
-  SD_CHECK_ARG(tiles < (1L << 31), "sd_conv1d_cl_split16: grid too large");
-  // the kernel sees rows of halfs: a value column is two halfs, a K step of 64 halfs is 32 values
+// work: the algorithmic (f32-equivalent) flops
+static int launch(const sd_conv_args* a, const SdConvChoice& c, int vec, double work, hipStream_t stream) {
+#define SD_GO(kern, ...) SD_CHECK_HIP(sd_launch_conv(kern, c.prof, work, c.grid, c.block, c.lds, stream, __VA_ARGS__)); break
+  switch (c.kernel) {
+    case SD_K_F16_128_HH: SD_GO((conv_gemm_f16_kernel<_Float16, _Float16>), *a, vec);
+    case SD_K_F16_128_HF: SD_GO((conv_gemm_f16_kernel<_Float16, float>), *a, vec);
+    case SD_K_F16_128_FH: SD_GO((conv_gemm_f16_kernel<float, _Float16>), *a, vec);
+    case SD_K_F16_128_FF: SD_GO((conv_gemm_f16_kernel<float, float>), *a, vec);
+    case SD_K_F16_T256_H_DIRECT: SD_GO((conv_gemm_f16_t256_kernel<_Float16, true, false>), *a, vec, c.super_walk);
+    case SD_K_F16_T256_H_STAGED: SD_GO((conv_gemm_f16_t256_kernel<_Float16, false, false>), *a, vec, c.super_walk);
+    case SD_K_F16_T256_F_DIRECT: SD_GO((conv_gemm_f16_t256_kernel<float, true, false>), *a, vec, c.super_walk);
+    case SD_K_F16_T256_F_STAGED: SD_GO((conv_gemm_f16_t256_kernel<float, false, false>), *a, vec, c.super_walk);
+    case SD_K_SPLIT_T256_DIRECT: SD_GO((conv_gemm_f16_t256_kernel<float, true, true>), *a, vec, c.super_walk);
+    case SD_K_SPLIT_T256_STAGED: SD_GO((conv_gemm_f16_t256_kernel<float, false, true>), *a, vec, c.super_walk);
+    case SD_K_SPLIT_N128: SD_GO(conv_gemm_split16_n128_kernel<float>, *a, vec);
+    default: return sd_set_error(SD_ERR_ARG, "sd_conv1d_cl_f16: no kernel %d in this operator", c.kernel);
+  }
+#undef SD_GO
+  SD_CHECK_LAUNCH(c.label);
+  return SD_OK;
+}
+
+int sd_conv1d_cl_f16_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t) {
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = sd_conv_f16_decide(a, SD_CONV_OP_F16, t, c, &n, &vec)) return e;
+  return launch(a, c[0], vec, sd_conv_flops(a), static_cast<hipStream_t>(stream));
+}
+extern "C" int sd_conv1d_cl_f16(const sd_conv_args* a, sd_stream_t stream) { return sd_conv1d_cl_f16_with(a, stream, sd_conv_tuning_now()); }
+
+int sd_conv1d_cl_split16_with(const sd_conv_args* a, sd_stream_t stream, const SdConvTuning& t) {
+  SdConvChoice c[2];
+  int n, vec;
+  if (int e = sd_conv_f16_decide(a, SD_CONV_OP_SPLIT16, t, c, &n, &vec)) return e;
+  if (c[0].kernel == SD_K_SPLIT_N128) return launch(a, c[0], vec, sd_conv_flops(a), static_cast<hipStream_t>(stream));
+  // the 256x256 kernel sees rows of halfs: a value column is two halfs, a K step of 64 halfs is 32 values (a split row carries cin / 2 values)
   sd_conv_args k = *a;
   k.lda = 2 * a->lda; k.a_col0 = 2 * a->a_col0;
   k.cin = 2 * a->cin_pad; k.cin_pad = 2 * a->cin_pad;
   k.x_dtype = SD_DT_F16; k.w_dtype = SD_DT_F16;
-  const bool plain = vec && (a->act == SD_ACT_RELU || a->act == SD_ACT_NONE) && a->act2 == SD_ACT_NONE && !a->bias_per_seg && !a->tee;
-  if (a->y_dtype == SD_DT_SPLIT16) {    // y as split halves: the LDS-staged epilogue's store phase (the register epilogue writes f32 only)
-    SD_CHECK_ARG(vec && a->ldo % 32 == 0 && !a->colstat, "sd_conv1d_cl_split16: an SD_DT_SPLIT16 output needs ldo %% 32 == 0, aligned slices and no column statistics");
-    return launch_t256<float, false, true>(&k, vec, stream);
-  }
-  if (plain) return launch_t256<float, true, true>(&k, vec, stream);
-  return launch_t256<float, false, true>(&k, vec, stream);
+  return launch(&k, c[0], vec, 0.5 * sd_conv_flops(&k), static_cast<hipStream_t>(stream));
 }
+extern "C" int sd_conv1d_cl_split16(const sd_conv_args* a, sd_stream_t stream) { return sd_conv1d_cl_split16_with(a, stream, sd_conv_tuning_now()); }
+

@@ -71,10 +71,11 @@ bool any_split(const sd_ecapa_weights* w, int dt) { return w->split16 != 0 && dt
 bool wide_split(const sd_ecapa_weights* w, int dt) { return w->split16 == 1 && dt == SD_DT_F32; }
 
 enum { MAP_UNIFORM, MAP_LENGTHS, MAP_PACKED };
-// nt: SD_TUNE_F16_NARROW_TILES (default 128), read ONCE per forward: the plan decides up front which tensors exist only as
-// SD_DT_SPLIT16, so every rule of one forward must see the same value whatever sd_set_tuning() does meanwhile.
+// tune: the tuning snapshot (sd_conv_choice.h), taken ONCE per forward: the plan decides up front which tensors exist only as
+// SD_DT_SPLIT16, so every rule and every conv of one forward must see the same values whatever sd_set_tuning() does meanwhile.
 struct PlanIn {
-  const sd_ecapa_weights* w; int B, T, M, map, dt; long nt; Switches sw; bool feats_aligned;
+  const sd_ecapa_weights* w; int B, T, M, map, dt; SdConvTuning tune; Switches sw; bool feats_aligned;
+  long narrow_tiles() const { return tune.tune[SD_TUNE_F16_NARROW_TILES]; }
   int Tc() const { return map == MAP_PACKED ? M : T; }            // the segment length the position-free layers see
   bool split() const { return any_split(w, dt); }
   bool wsplit() const { return wide_split(w, dt); }
@@ -98,13 +99,8 @@ bool has_buf(const sd_ecapa_weights* w, int dt, int buf) {
   }
 }
 
-// Small launches of the C-wide layers (measured, tools/probe_split16.py: 1024 -> 1024 at 32 segments 0.063 ms on the 128x128 split
-// kernel against 0.085 ms for pack + 256x256 kernel, 0.041 against 0.079 at 16; from 64 segments up, and for 3C -> 3C always, the
-// 256x256 kernel wins): at most 128 tiles of 256x256 and cout <= 1024 -> the narrow kernel, which has no column statistics.
-bool wide_goes_narrow(const sd_layer& l, int M, long narrow_tiles) {
-  const long tiles = (long)((M + 255) / 256) * ((l.cout + 255) / 256);
-  return l.cout <= 1024 && tiles <= narrow_tiles;
-}
+// Small launches of the C-wide layers go to the narrow split kernel, which has no column statistics: sd_wide_goes_narrow (sd_conv_choice.h)
+bool wide_goes_narrow(const PlanIn& in, const sd_layer& l) { return sd_wide_goes_narrow(l.cout, in.M, in.narrow_tiles()); }
 
 // The wide kernel's packing: weights scaled by 2^s with the scale folded into bias_split / scale_split.  A wide-ROLE layer (stem,
 // tdnn1, tdnn2, MFA) of a small geometry (cout <= 256) may carry the NARROW packing instead (w_split + split_scale_inv, no folded
@@ -114,11 +110,12 @@ bool wide_packed(const sd_layer& l) { return l.w_split && l.bias_split && l.scal
 // The SE squeeze / the pooling's global mean and std come out of a wide conv's epilogue as per-tile column sums, parked in `scratch`
 // bytes of a dead buffer, where the geometry allows.  The epilogue sums over all T rows of a segment: uniform map only.  The buffers are
 // sized for the smallest row unit a launch can write: an f32 forward can reach the exact operator's 80 / 96 / 112-row tiles
-// (sd_conv1d_cl_f32_rows) also WITH split weights; the f16 and split kernels always write units of 128.
+// (SD_CONV_OP_F32_STAT_ROWS) also WITH split weights; the f16 and split kernels always write units of 128.  The floor on T is the
+// operator's own (SdConvRule::colstat_T).
 bool colstat_rule(const PlanIn& in, const sd_layer& l, size_t scratch) {
-  const size_t unit = in.dt == SD_DT_F32 ? 80 : 128;
-  return in.sw.colstat && in.map == MAP_UNIFORM && in.T >= (in.wsplit() ? 128 : 64) && l.cout % 256 == 0 &&
-         !(in.wsplit() && l.w_split && wide_goes_narrow(l, in.M, in.nt)) && (size_t)((in.M + unit - 1) / unit) * 6 * l.cout * sizeof(float) <= scratch;
+  const size_t unit = in.dt == SD_DT_F32 ? SD_STAT_UNIT_MIN : SD_T128;
+  return in.sw.colstat && in.map == MAP_UNIFORM && in.T >= (in.wsplit() ? SD_COLSTAT_T_256 : SD_COLSTAT_T_128) && l.cout % 256 == 0 &&
+         !(in.wsplit() && l.w_split && wide_goes_narrow(in, l)) && (size_t)((in.M + unit - 1) / unit) * 6 * l.cout * sizeof(float) <= scratch;
 }
 
 // what the 128x128 split kernel needs of the f32 operand it splits while staging
@@ -136,7 +133,7 @@ Route wide_route(const PlanIn& in, const sd_layer& l, int ld, int col0, bool col
   if (!(in.wsplit() && wide_packed(l))) return R_F32;
   // (f32 x stays: split while staged; the folded 2^s form of bias / scale serves this kernel too.  Column statistics have yielded to a
   // small launch in colstat_rule, and start at T = 128 there, which is what the 256x256 kernel needs of them)
-  return wide_goes_narrow(l, in.M, in.nt) && stage_aligned(l, ld, col0) ? R_SPLIT128_FOLDED : R_SPLIT256_PACK;
+  return wide_goes_narrow(in, l) && stage_aligned(l, ld, col0) ? R_SPLIT128_FOLDED : R_SPLIT256_PACK;
 }
 
 // Does a layer on `route` read the SD_DT_SPLIT16 twin of its input (buffer `twin`, same layout as the f32 buffer) instead of packing it?
@@ -452,7 +449,7 @@ const sd_layer& layer_of(const sd_ecapa_weights* w, const Step& s) {
 
 int dtype_of(int form) { return form == AS_F16 ? SD_DT_F16 : form == AS_SPLIT ? SD_DT_SPLIT16 : SD_DT_F32; }
 
-struct Exec { const sd_ecapa_weights* w; const SdSegs& sg; const Buffers& b; sd_stream_t stream; int M, Tc, dt; bool split; };
+struct Exec { const sd_ecapa_weights* w; const SdSegs& sg; const Buffers& b; sd_stream_t stream; int M, Tc, dt; bool split; const SdConvTuning& tune; };
 
 // stat_rows: the row unit of the column statistics the last conv wrote (128 unless the exact-f32 operator picked one of its 80 / 96 /
 // 112-row tiles: small launches), for the finish pass that follows it
@@ -497,15 +494,15 @@ int run_step(const Exec& x, const Step& s, int* stat_rows) {
   if (s.op == OP_ASP_G) { a.scale = nullptr; a.shift = nullptr; }
   if (s.wr[2].form) { a.colstat = static_cast<float*>(p[s.wr[2].buf]); *stat_rows = 128; }
   switch (s.route) {
-    case R_PACKED: return sd_conv1d_cl_packed_f32(&a, x.sg.span, B, x.stream);
-    case R_SEG_GEMM: return sd_seg_gemm_f32(&a, p[SKP], x.b.skp_bytes, x.stream);
-    case R_F32: return a.colstat ? sd_conv1d_cl_f32_rows(&a, x.stream, stat_rows) : sd_conv1d_cl_f32(&a, x.stream);
-    case R_F16: return sd_conv1d_cl_f16(&a, x.stream);
+    case R_PACKED: return sd_conv1d_cl_packed_f32_with(&a, x.sg.span, B, x.stream, x.tune);
+    case R_SEG_GEMM: return sd_seg_gemm_f32_with(&a, p[SKP], x.b.skp_bytes, x.stream, x.tune);
+    case R_F32: return sd_conv1d_cl_f32_with(&a, x.stream, x.tune, a.colstat ? stat_rows : nullptr);
+    case R_F16: return sd_conv1d_cl_f16_with(&a, x.stream, x.tune);
     case R_SPLIT128: a.w_scale_inv = l.split_scale_inv; break;                 // the layer's own bias / scale
     default: a.bias = l.bias_split; a.scale = l.scale_split; break;            // the folded 2^s vectors
   }
   a.w = l.w_split; a.w_dtype = SD_DT_SPLIT16; a.cin_pad = (l.cin + 31) / 32 * 32;
-  return sd_conv1d_cl_split16(&a, x.stream);
+  return sd_conv1d_cl_split16_with(&a, x.stream, x.tune);
 }
 
 #define SD_TRY(expr)            \
@@ -524,15 +521,14 @@ int forward(const sd_ecapa_weights* w, const float* feats, const SdSegs& sg, flo
   SD_CHECK_ARG(sg.packed || (long)B * T < (1L << 31), "sd_ecapa_forward: B*T overflows int");
   SD_CHECK_ARG(sd_aligned16(ws_dev), "sd_ecapa_forward: workspace must be 16-byte aligned");
   const int M = sg.packed ? sg.M : B * T;
-  const PlanIn in = {w, B, T, M, sg.packed ? MAP_PACKED : sg.rel_len ? MAP_LENGTHS : MAP_UNIFORM, dt,
-                     sd_f16_narrow_tiles().load(std::memory_order_relaxed), switches(), sd_aligned16(feats)};
+  const PlanIn in = {w, B, T, M, sg.packed ? MAP_PACKED : sg.rel_len ? MAP_LENGTHS : MAP_UNIFORM, dt, sd_conv_tuning_now(), switches(), sd_aligned16(feats)};
   Plan plan;
   SD_TRY(make_plan(in, &plan));
   Buffers b = carve(w, B, (size_t)M, ws_dev, dt);
   if (ws_bytes < b.bytes) return sd_set_error(SD_ERR_WORKSPACE, "sd_ecapa_forward: workspace %zu < %zu bytes", ws_bytes, b.bytes);
   b.p[FEATS] = const_cast<float*>(feats);
   b.p[EMB] = emb;
-  const Exec x = {w, sg, b, stream, M, in.Tc(), dt, in.split()};
+  const Exec x = {w, sg, b, stream, M, in.Tc(), dt, in.split(), in.tune};
   int stat_rows = 128;
   for (int i = 0; i < plan.n; ++i) SD_TRY(run_step(x, plan.s[i], &stat_rows));
   return SD_OK;
@@ -559,7 +555,7 @@ extern "C" size_t sd_ecapa_plan_read(const sd_ecapa_weights* w, int B, int T, in
     sd_set_error(SD_ERR_ARG, "sd_ecapa_plan_read: B=%d T=%d M=%d map_kind=%d", B, T, M, map_kind);
     return 0;
   }
-  const PlanIn in = {w, B, packed ? 0 : T, packed ? M : B * T, map_kind, w->w_dtype, sd_f16_narrow_tiles().load(std::memory_order_relaxed), switches(), true};
+  const PlanIn in = {w, B, packed ? 0 : T, packed ? M : B * T, map_kind, w->w_dtype, sd_conv_tuning_now(0), switches(), true};
   Plan plan;
   if (make_plan(in, &plan) != SD_OK) return 0;
   auto put = [](std::string& t, const TRef* r) {

@@ -19,7 +19,7 @@ arithmetic of the split operators (include/sd_hip.h) in numpy, for the twins who
 `CASE_TABLE` names, for every case, the launch LABELS (include/sd_hip_trace.h: kernel, instantiation, walk) its runs reach on the
 MI355X, and `F32_LABELS` / `f16_label` / `split_labels` the one label of each single run (case x selection x storage types x tuning);
 tests/test_gpu_exact.py holds every run to its label through the launch log, so these are checked facts, not intentions.  Each entry
-is derived from the dispatch rules of sd_conv_gemm.hip (`conv1d_cl_f32_impl`), sd_conv_gemm_f16.hip (`sd_conv1d_cl_f16`,
+is derived from the dispatch rules of csrc/sd_conv_choice.h (`sd_choose_conv_f32`), sd_conv_gemm_f16.hip (`sd_conv1d_cl_f16`,
 `sd_conv1d_cl_split16`), sd_pool.hip and sd_asp_fused.hip; the derivation stands beside it.  `EXACT_COVERAGE` is the inverse:
 label -> cases."""
 import functools
@@ -184,7 +184,7 @@ def kernel_of(label):
 
 
 # ---- sd_conv1d_cl_f32: the label of every shape under the eight selections of kernel_selection.CONV_KERNELS.
-# conv1d_cl_f32_impl, with t128 = ceil(M / 128) ceil(cout / 128), in this order:
+# sd_choose_conv_f32 (csrc/sd_conv_choice.h), with t128 = ceil(M / 128) ceil(cout / 128), in this order:
 #   1. no colstat, T > 1, M >= 64 and t128 < S64 (128; 0 unless "auto"): the 64x64 ring kernel; <32> when ceil(M / 64) ceil(cout / 64) < 128
 #   2. no colstat and t128 < SKINNY (128; 0 from "tiles128" on): the 32x32 split-K kernel
 #   3. cout >= 1024 and ceil(M / 256) ceil(cout / 256) >= WIDE (1024; 0 under "wide256"), no tee_add, no colstat at T < 128: the 256x256 kernel

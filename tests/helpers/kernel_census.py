@@ -1,7 +1,7 @@
 """The census of launch labels (include/sd_hip_trace.h): every label the sources of libsd_hip.so can count, and the GPU test that
 asserts the label ran (tests/helpers/launch_log.py) while it checks the kernel's numbers against a reference.
 
-tests/test_launch_log_rules.py reads the labels out of csrc/*.hip and fails when this table and the sources differ, when a named test
+tests/test_launch_log_rules.py reads the labels out of csrc/*.hip and csrc/sd_conv_choice.h and fails when this table and the sources differ, when a named test
 does not exist, or when a label is exempt without the guard its exemption claims.  A retuned threshold that orphans a kernel then
 fails the named test on the MI355X instead of going unnoticed."""
 
@@ -70,17 +70,9 @@ KERNEL_TESTS = {
     "fbank_utt16_kernel<packed>": _PACKED_FBANK, "fbank_logmel_kernel<packed>": _PACKED_FBANK, "fbank_finalize_kernel<packed>": _PACKED_FBANK,
     "fbank_packed_tiles_kernel": _PACKED_FBANK,
     "fbg_pad_kernel": _GENERIC, "fbg_dft_f64_kernel": _GENERIC, "fbg_finalize_kernel": _GENERIC,
-    # ---- what the shipped build cannot reach (EXEMPT)
-    "conv_gemm_f32_kernel<reg>": None, "conv_gemm_f32_kernel<reg>/symmetric": None, "conv_gemm_f16_w4_kernel<f16>": None,
-    "conv_gemm_f16_w4_kernel<f32>": None,
 }
 
 # label -> (reason, the guard in front of its launch site: an experiment variable read through sd_experiment_env, or a build flag the
 # shipped build does not set).  A label that is merely hard to reach does not belong here.
-EXEMPT = {
-    "conv_gemm_f32_kernel<reg>": ("register staging of the 128x128 kernel: only with SD_EXPERIMENT=1 SD_F32_DMA=0", 'sd_experiment_env("SD_F32_DMA")'),
-    "conv_gemm_f32_kernel<reg>/symmetric": ("the same, for the symmetric launch", 'sd_experiment_env("SD_F32_DMA")'),
-    "conv_gemm_f16_w4_kernel<f16>": ("the 4-wave 256x256 experiment: compiled only into -DSD_WITH_W4 variant builds", "#ifdef SD_WITH_W4"),
-    "conv_gemm_f16_w4_kernel<f32>": ("the same, f32 output", "#ifdef SD_WITH_W4"),
-}
-ALLOWED_GUARDS = ("sd_experiment_env(", "#ifdef SD_WITH_W4", "#ifdef SD_STAMP")
+EXEMPT = {}
+ALLOWED_GUARDS = ("sd_experiment_env(", "#ifdef SD_STAMP")

@@ -15,7 +15,7 @@ PINNED_LABEL = {"split32": "skinny_gemm_f32_kernel", "tiles128": "conv_gemm_f32_
 
 
 def f32_conv_label(sel, M, T, cout, colstat=False, tee_add=False, stat_rows=False):
-    """The launch label of one sd_conv1d_cl_f32 call under selection `sel` on the MI355X: conv1d_cl_f32_impl (sd_conv_gemm.hip)
+    """The launch label of one sd_conv1d_cl_f32 call under selection `sel` on the MI355X: sd_choose_conv_f32 (csrc/sd_conv_choice.h)
     restated rule by rule, in its order, with the tuning values `select_conv_kernel` sets (shipped: S64 128, SKINNY 128, WIDE 1024
     tiles of 256x256, half tiles and tile rows by the cost rule).  `stat_rows`: the caller takes column statistics in units other
     than 128 rows (the ECAPA schedule; the public entry does not)."""

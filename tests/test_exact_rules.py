@@ -319,7 +319,7 @@ def test_exact_coverage_names_a_gather_and_a_dense_case_for_every_kernel():
 
 
 def test_the_f32_label_table_is_the_dispatch_rule_restated():
-    """F32_LABELS (data, derived by hand beside each entry) against kernel_selection.f32_conv_label (conv1d_cl_f32_impl restated as
+    """F32_LABELS (data, derived by hand beside each entry) against kernel_selection.f32_conv_label (sd_choose_conv_f32 restated as
     code): two statements of the same rules must agree on every shape and selection."""
     for shape, by_sel in E.F32_LABELS.items():
         assert list(by_sel) == kernel_selection.CONV_KERNELS

@@ -43,6 +43,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import ahc_ref  # noqa: E402
 import exact_cases as E  # noqa: E402
+from conv_choice import CHOICE_RUNS, CHOICE_SHAPES, predicted_launches  # noqa: E402
 from kernel_selection import CONV_KERNELS, f16_tiles, restore_conv_kernel, select_conv_kernel  # noqa: E402,F401
 from launch_log import F16_CONV, F32_CONV, SPLIT_CONV, expect_launches  # noqa: E402
 
@@ -274,6 +275,44 @@ def test_conv1d_cl_split16_gives_the_integers(dev, name, e=0, side="x"):
         finally:
             N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, -1), "sd_set_tuning")
         check_conv(dev, c, got, F32, op + " lockstep")
+
+
+_CHOICE_CASES = {}
+
+
+def _choice_case(shape, kind="dense"):
+    """The dense integer case of a CHOICE_SHAPES entry (per-channel bias, relu, scale, shift; x as 2049 s for the split operator),
+    built once per process."""
+    if (shape, kind) not in _CHOICE_CASES:
+        _CHOICE_CASES[shape, kind] = E.dense_case(f"choice-{shape}-{kind}", CHOICE_SHAPES[shape], f16=kind == "dense", kind=kind, kernels=())
+    return _CHOICE_CASES[shape, kind]
+
+
+@pytest.mark.parametrize("runs", list(CHOICE_RUNS.values()), ids=list(CHOICE_RUNS))
+def test_the_choice_is_what_ran(dev, runs):
+    """Every conv entry, at the shapes on both sides of each rule and under every selection that bears on them: what the launch log
+    counted is what sd_conv_choice_read said for the same sd_conv_args and this device's CU count (tests/helpers/conv_choice.py asks
+    inside the entry call), label by label -- and the results are the integers, as everywhere in this file."""
+    from launch_log import CONV, kernel_of, launches
+    N, lib = _lib()
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    try:
+        for op, shape, sel, tune in runs:
+            select_conv_kernel(sel)
+            N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, tune.get("f16_tiles", -1)), "sd_set_tuning")
+            N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, tune.get("lockstep", -1)), "sd_set_tuning")
+            c = _choice_case(shape, "split_x" if op in ("narrow", "wide") else "dense")
+            xdt, ydt = (F16 if tune.get("x16") else F32), (F16 if tune.get("y16") else F32)
+            with predicted_launches(n_cu) as (want, calls):
+                with launches() as log:
+                    got = run_conv(dev, c, op, xdt, ydt)
+            ran = {lb: n for lb, n in log.items() if kernel_of(lb) in CONV and lb != "split16_pack_kernel"}      # (the pack pass: an entry of its own)
+            assert calls and ran == dict(want), (op, shape, sel, tune, ran, dict(want))
+            check_conv(dev, c, got, ydt, f"{op} {shape} {sel} {tune}")
+    finally:
+        restore_conv_kernel()
+        N.check(lib.sd_set_tuning(N.SD_TUNE_F16_NARROW_TILES, -1), "sd_set_tuning")
+        N.check(lib.sd_set_tuning(N.SD_TUNE_T256_LOCKSTEP_TILES, -1), "sd_set_tuning")
 
 
 def _check_colstat(dev, c, got_y, cs, n_cs, ydt, what):

@@ -1,6 +1,7 @@
 """No-GPU checks of the launch log (include/sd_hip_trace.h) and of the census of launch labels (tests/helpers/kernel_census.py): the
-binding table, the untouched main ABI, the log with nothing launched, and -- read out of the source text of csrc/*.hip -- that every
-kernel has a label, every label a GPU test that asserts it ran, and every exemption the guard it claims."""
+binding table, the untouched main ABI, the log with nothing launched, and -- read out of the source text of csrc/*.hip and of the
+conv operators' label table in csrc/sd_conv_choice.h -- that every kernel has a label, every label a GPU test that asserts it ran,
+and every exemption the guard it claims."""
 import ctypes as C
 import os
 import re
@@ -28,7 +29,8 @@ def test_header_and_binding_table_name_the_same_exported_entries():
     header = open(N.PKG_DIR.parent / "include" / "sd_hip_trace.h").read()
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     names = set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-    assert names == set(N.TRACE_PROTOTYPES) == {"sd_trace_abi_version", "sd_launch_log_enable", "sd_launch_log_read", "sd_ecapa_plan_read"}
+    assert names == set(N.TRACE_PROTOTYPES) == {"sd_trace_abi_version", "sd_launch_log_enable", "sd_launch_log_read", "sd_ecapa_plan_read",
+                                                    "sd_conv_choice_read"}
     assert not names & (set(N.PROTOTYPES) | set(N.SPECTRAL_PROTOTYPES) | set(N.AHC_PROTOTYPES) | set(N.HDBSCAN_PROTOTYPES))
     lib = N.load()
     for name, (res, args) in N.TRACE_PROTOTYPES.items():
@@ -41,7 +43,7 @@ def test_header_and_binding_table_name_the_same_exported_entries():
 @needs_lib
 def test_versions_and_struct_sizes_are_untouched():
     lib = N.load()
-    assert lib.sd_trace_abi_version() == 2 == N.SD_TRACE_ABI_VERSION
+    assert lib.sd_trace_abi_version() == 3 == N.SD_TRACE_ABI_VERSION
     assert lib.sd_abi_version() == 11 and lib.sd_spectral_abi_version() == 1 and lib.sd_ahc_abi_version() == 1 and lib.sd_hdbscan_abi_version() == 1
     assert [int(lib.sd_sizeof(i)) for i in range(5)] == [184, 88, 1672, 13944, 0]       # the committed layouts of ABI 11
     header = open(N.PKG_DIR.parent / "include" / "sd_hip.h").read()
@@ -79,7 +81,8 @@ def test_expectations_are_judged_by_family():
 # ------------------------------------------------------------------ the census, from the source text
 
 def _sources():
-    return {f.name: f.read_text() for f in sorted(CSRC.glob("*.hip"))}
+    """The .hip files, and the header that holds the conv operators' label table (the operators hand `choice.label` to the log)."""
+    return {f.name: f.read_text() for f in sorted(CSRC.glob("*.hip")) + [CSRC / "sd_conv_choice.h"]}
 
 
 def _labels():
@@ -92,8 +95,20 @@ def test_every_kernel_has_a_label():
     assert len(kernels) >= 50 and all(k.endswith("_kernel") for k in kernels), sorted(kernels)
     named = {L.kernel_of(lb) for lb in _labels()}
     assert kernels == named, (sorted(kernels - named), sorted(named - kernels))
-    # every label is handed to the log: it stands in an SD_CHECK_LAUNCH or in a table / function such a call reads
-    assert len(re.findall(r"\bSD_CHECK_LAUNCH\(", text)) >= 53
+    # every label is handed to the log: it stands in an SD_CHECK_LAUNCH or in a table / function such a call reads.  The conv operators
+    # have one SD_CHECK_LAUNCH(c.label) per file, behind the switch over the ids of sd_conv_label's table: every id of the table is a case
+    assert len(re.findall(r"\bSD_CHECK_LAUNCH\(", text)) >= 43
+    assert len(re.findall(r"\bSD_CHECK_LAUNCH\(c\.label\)", text)) == 2
+    table = _function_text_c(_sources()["sd_conv_choice.h"], "sd_conv_label")
+    ids = set(re.findall(r"case (SD_K_[A-Z0-9_]+):", table)) | {"SD_K_SPLIT_N128"}          # (the table's default)
+    assert len(ids) == 24 and len(LABEL.findall(table)) == 27
+    cases = set(re.findall(r"case (SD_K_[A-Z0-9_]+):", "".join(t for n, t in _sources().items() if n.endswith(".hip"))))
+    assert cases == ids, (sorted(ids - cases), sorted(cases - ids))
+
+
+def _function_text_c(text, fn):
+    """The body of the C++ function `fn`: from its name to the first line that is a lone closing brace."""
+    return re.search(rf"\b{fn}\(.*?^}}", text, flags=re.M | re.S).group(0)
 
 
 def test_the_census_table_equals_the_labels_of_the_sources():
@@ -146,26 +161,39 @@ def test_every_named_test_exists_and_asserts_its_label():
     assert "viterbi_kernel" in body and "topk_mean_std_kernel" not in body and not any(h in body for h in PRODUCERS)
 
 
+def _check_exemption(label, reason, guard, sources):
+    assert reason and guard.startswith(K.ALLOWED_GUARDS), label
+    hits = [(name, i, text.splitlines()) for name, text in sources.items() for i, line in enumerate(text.splitlines()) if f'"{label}"' in line]
+    assert hits, label
+    for name, i, lines in hits:
+        if guard.startswith("#ifdef"):
+            open_ifs = []
+            for line in lines[:i]:
+                word = line.lstrip()
+                if word.startswith(("#ifdef", "#ifndef", "#if ")):
+                    open_ifs.append(word.split("//")[0].strip())
+                elif word.startswith("#endif"):
+                    open_ifs.pop()
+            assert guard in open_ifs, f"{label}: {guard} is not open at {name}:{i + 1} ({open_ifs})"
+        else:
+            assert any(guard in line for line in lines[max(0, i - 60):i + 1]), f"{label}: no {guard} within 60 lines above {name}:{i + 1}"
+
+
 def test_every_exemption_stands_behind_its_guard():
     """The guard must be one of the kinds the shipped build never passes and must stand in the label's own file: an #ifdef still
-    open at every launch site that names the label, or an experiment variable read at most 60 lines above it."""
+    open at every launch site that names the label, or an experiment variable read at most 60 lines above it.  No label is exempt
+    today, so the rule is shown on a synthetic source: it accepts both kinds of guard and bites on each."""
     for label, (reason, guard) in K.EXEMPT.items():
-        assert reason and guard.startswith(K.ALLOWED_GUARDS), label
-        hits = [(name, i, text.splitlines()) for name, text in _sources().items() for i, line in enumerate(text.splitlines()) if f'"{label}"' in line]
-        assert hits, label
-        for name, i, lines in hits:
-            if guard.startswith("#ifdef"):
-                open_ifs = []
-                for line in lines[:i]:
-                    word = line.lstrip()
-                    if word.startswith(("#ifdef", "#ifndef", "#if ")):
-                        open_ifs.append(word.split("//")[0].strip())
-                    elif word.startswith("#endif"):
-                        open_ifs.pop()
-                assert guard in open_ifs, f"{label}: {guard} is not open at {name}:{i + 1} ({open_ifs})"
-            else:
-                assert any(guard in line for line in lines[max(0, i - 60):i + 1]), f"{label}: no {guard} within 60 lines above {name}:{i + 1}"
-    # and the rule bites: a reachable label is not excused by a guard that is not there
-    text = _sources()["sd_conv_gemm.hip"].splitlines()
-    i = next(j for j, line in enumerate(text) if '"skinny_gemm_f32_kernel"' in line)
-    assert not any('sd_experiment_env("SD_F32_DMA")' in line for line in text[max(0, i - 60):i + 1])
+        _check_exemption(label, reason, guard, _sources())
+    assert K.EXEMPT == {}        # every label of the sources is reachable in the shipped build
+    env = 'sd_experiment_env("SD_TOY")'
+    toy = {"toy.hip": "\n".join(['static const bool on = [] { return ' + env + ' != nullptr; }();', 'if (on) SD_CHECK_LAUNCH("toy_a_kernel");'] + ["//"] * 60 +
+                                ['SD_CHECK_LAUNCH("toy_b_kernel");', "#ifdef SD_STAMP", 'SD_CHECK_LAUNCH("toy_c_kernel");', "#endif",
+                                 'SD_CHECK_LAUNCH("toy_d_kernel");'])}
+    _check_exemption("toy_a_kernel", "behind the variable", env, toy)
+    _check_exemption("toy_c_kernel", "stamp builds only", "#ifdef SD_STAMP", toy)
+    for label, guard, why in (("toy_b_kernel", env, "no .* within 60 lines"), ("toy_d_kernel", "#ifdef SD_STAMP", "is not open"),
+                              ("toy_a_kernel", "#ifdef SD_OTHER", "toy_a_kernel"), ("toy_e_kernel", env, "toy_e_kernel")):
+        with pytest.raises(AssertionError, match=why):
+            _check_exemption(label, "a reason", guard, toy)
+
