@@ -46,17 +46,15 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 namespace {
 
-constexpr int NFFT = 400;
-constexpr int HOP = 160;
-constexpr int NFREQ = 201;
+using namespace sd_fb;       // the framing, MELP (the mel accumulator row stride): sd_fbank_route.h
 constexpr int NBT = 7;       // 32-bin tiles (224 >= 201)
 constexpr int FT = 32;       // frames per wave tile
 constexpr int WAVES = 4;
-constexpr int MELP = 81;     // mel accumulator row stride
 constexpr int MAX_MELS = 80;
 
 
@@ -501,50 +499,13 @@ __global__ void fbank_finalize_kernel(float* out, int ld_out, int T, int n_mels,
     }
 }
 
-}  // namespace
+static_assert(FT == FOLD_FT && WAVES == FOLD_WAVES, "sd_fbank_route.h states the tile geometry");
 
-namespace {
-// round-to-nearest-even f32 -> bf16 bits (finite inputs)
-unsigned short bf16_bits(float v) {
-  unsigned u;
-  std::memcpy(&u, &v, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-float bf16_value(unsigned short b) {
-  const unsigned u = (unsigned)b << 16;
-  float v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-}  // namespace
-
-extern "C" sd_fbank_plan* sd_fbank_plan_create(const float* window, int n_fft, int hop,
-                                               const float* mel_fb, int n_mels,
-                                               int pad_mode, int log_mode, float log_eps, float top_db) {
-  auto fail = [](int code, const char* msg) -> sd_fbank_plan* { sd_set_error(code, "%s", msg); return nullptr; };
-  if (!window || !mel_fb) return fail(SD_ERR_ARG, "sd_fbank_plan_create: null window/mel_fb");
-  if (pad_mode != SD_PAD_ZERO && pad_mode != SD_PAD_REFLECT) return fail(SD_ERR_ARG, "sd_fbank_plan_create: bad pad_mode");
-  if (log_mode != SD_LOG_LN_EPS && log_mode != SD_LOG_DB_TOPDB) return fail(SD_ERR_ARG, "sd_fbank_plan_create: bad log_mode");
-  if (n_fft != NFFT || hop != HOP || n_mels > MAX_MELS) {
-    // any other framing (fbank_batch at sr != 16 kHz, [REF speech_encode.py:14-24]): the DFT and the mel product as implicit GEMMs on
-    // the exact-f32 conv operator (sd_fbank_generic.hip); any window, no symmetry needed
-    if (!sd_fbank_generic_geometry_ok(n_fft, hop, n_mels))
-      return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: need 8 <= n_fft <= 8192, 1 <= hop <= n_fft, 1 <= n_mels <= 256");
-    sd_fbank_plan* plan = new sd_fbank_plan{};
-    plan->n_fft = n_fft; plan->hop = hop; plan->n_mels = n_mels; plan->pad_mode = pad_mode; plan->log_mode = log_mode;
-    plan->log_eps = log_eps; plan->top_db = top_db; plan->generic = true;
-    if (sd_fbank_generic_create_tables(plan, window, mel_fb) != SD_OK) { delete plan; return nullptr; }
-    return plan;
-  }
-  if (n_mels < 1) return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: n_mels must be positive");
-  for (int k = 1; k < NFFT / 2; ++k)
-    if (window[k] != window[NFFT - k])
-      return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: window must be symmetric (w[k] == w[n_fft-k])");
-
-  // ---- tables of the split-f16 kernel.  Basis: value = w[k] cos / sin(2 pi k bin / 400) in float64, hi = f16(v),
-  // lo = f16(v - hi); fragment order of v_mfma_f32_32x32x16_f16's A operand: lane l holds row (bin) l & 31,
-  // k = 16 s + 8 (l >> 5) + e.  One (pass, k step) block is contiguous: [tile in pass][kind][lane][e].
+int folded_create_tables(sd_fbank_plan* plan, const float* window, const float* mel_fb) {
+  const int n_mels = plan->f.n_mels;
+  // Tables of the split-f16 kernel.  Basis: value = w[k] cos / sin(2 pi k bin / 400) in float64, hi = f16(v), lo = f16(v - hi); fragment order of
+  // v_mfma_f32_32x32x16_f16's A operand: lane l holds row (bin) l & 31, k = 16 s + 8 (l >> 5) + e.  One (pass, k step) block is
+  // contiguous: [tile in pass][kind][lane][e].
   std::vector<_Float16> b16(V2_BASIS_BYTES / 2);
   {
     size_t o = 0;
@@ -564,8 +525,9 @@ extern "C" sd_fbank_plan* sd_fbank_plan_create(const float* window, int n_fft, i
                   if (k == NFFT / 2) v = kind < 2 ? 0.5 * v : 0.0;
                   if (k == 0 && kind >= 2) v = 0.0;
                 }
-                const _Float16 hi = (_Float16)(float)v;
-                b16[o] = (kind & 1) ? (_Float16)(float)(v - (double)(float)hi) : hi;
+                _Float16 hi, lo;
+                sd_split_f16(v, &hi, &lo);
+                b16[o] = (kind & 1) ? lo : hi;
               }
     }
   }
@@ -582,196 +544,170 @@ extern "C" sd_fbank_plan* sd_fbank_plan_create(const float* window, int n_fft, i
               for (int e = 0; e < 8; ++e, ++o) {
                 const int m = 32 * t + (l & 31), bin = 32 * q + 16 * s2 + 8 * (e >> 2) + 4 * (l >> 5) + (e & 3);
                 const float w = (m < n_mels && bin < NFREQ) ? mel_fb[(size_t)bin * n_mels + m] : 0.f;
-                const unsigned short w1 = bf16_bits(w);
-                m16[o] = part == 0 ? w1 : bf16_bits(w - bf16_value(w1));
+                const unsigned short w1 = sd_bf16_bits(w);
+                m16[o] = part == 0 ? w1 : sd_bf16_bits(w - sd_bf16_value(w1));
               }
   }
+  if (int e = sd_fbank_upload(plan, &plan->basis16_dev, b16.data(), V2_BASIS_BYTES)) return e;
+  return sd_fbank_upload(plan, &plan->melw16_dev, m16.data(), V2_MELW_BYTES);
+}
+
+// The folded route of sd_fbank_route.h: max-key fill, [packed: the tile table,] the folded-DFT kernel, the finalize pass.
+int folded_launch(const sd_fbank_plan* plan, const SdFbankRoute& r, const SdFbankCall& c, const SdFbankPtrs& p, hipStream_t stream) {
+  const SdFbankFacts& f = plan->f;
+  const bool packed = c.form == SD_FB_PACKED;
+  Fbank2Args a = {};
+  a.wav = p.wav; a.B = c.B; a.n = c.n; a.T = r.T;
+  a.starts = p.starts; a.n_total = c.n_total;
+  a.basis = static_cast<const _Float16*>(plan->basis16_dev); a.melw = static_cast<const __bf16*>(plan->melw16_dev);
+  a.n_mels = f.n_mels; a.pad_mode = f.pad_mode; a.log_mode = f.log_mode; a.log_eps = f.log_eps;
+  a.out = p.out; a.ld_out = c.ld_out;
+  a.maxbuf = static_cast<int*>(p.ws); a.flat = r.flat; a.inv_mels = r.inv_mels;
+  a.lens = p.lens; a.frame_start = p.frame_start;
+  int* const tile_start = packed ? reinterpret_cast<int*>(static_cast<char*>(p.ws) + r.tile_table_off) : nullptr;
+  a.tile_start = tile_start;
+  a.n_lo = r.n_lo; a.M = c.M;
+  // reset the per-utterance max keys with a kernel, not hipMemsetAsync: a byte-pattern memset node
+  // replayed from a captured hipGraph did not reproduce the eager result (configs[3] test)
+  hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)r.fill.grid), dim3(r.fill.block), 0, stream, a.maxbuf, c.B, (int)0x80808080);
+  SD_CHECK_LAUNCH("fill_i32_kernel");
+  if (packed) {
+    hipLaunchKernelGGL(fbank_packed_tiles_kernel, dim3((unsigned)r.tile_table.grid), dim3(r.tile_table.block), 0, stream, p.lens, c.B, r.n_lo, c.n,
+                       tile_start);
+    SD_CHECK_LAUNCH("fbank_packed_tiles_kernel");
+  }
+  const auto logmel = packed ? fbank_logmel_kernel<true> : fbank_logmel_kernel<false>;
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(logmel), V2_LDS_BYTES));
+  {
+    // uniform calls are timed; algorithmic bytes: waveform read once + log-mel written once (192 320 B per 2 s segment)
+    std::optional<SdProfScope> prof;
+    if (!packed) prof.emplace(SD_PROF_FBANK, stream, (double)c.B * ((double)c.n * 4.0 + (double)r.T * f.n_mels * 4.0));
+    hipLaunchKernelGGL(logmel, dim3((unsigned)r.logmel.grid), dim3(r.logmel.block), r.logmel.lds, stream, a);
+  }
+  SD_CHECK_LAUNCH(packed ? "fbank_logmel_kernel<packed>" : "fbank_logmel_kernel<uniform>");
+  // (a packed span's workgroup takes T from its own length and mean-normalises: c.mean_norm is 1 there)
+  hipLaunchKernelGGL(packed ? fbank_finalize_kernel<true> : fbank_finalize_kernel<false>, dim3((unsigned)r.finalize.grid), dim3(r.finalize.block),
+                     r.finalize.lds, stream, p.out, c.ld_out, packed ? 1 : r.T, f.n_mels, a.maxbuf, r.use_floor, f.top_db, c.mean_norm, r.R, p.rel_len,
+                     p.lens, p.frame_start, r.n_lo, packed ? c.n : 0, c.M);
+  SD_CHECK_LAUNCH(packed ? "fbank_finalize_kernel<packed>" : "fbank_finalize_kernel<uniform>");
+  return SD_OK;
+}
+
+// Every entry: describe the call (c: the numbers; here: which pointers are null or misaligned), check it, launch what the route says
+// (sd_fbank_route.h).  A pack with spans on both routes is two launches (plus the tile table and the max-key reset); each span's rows
+// are bitwise sd_fbank_f32 of the span alone (B = 1, n = lens[s]).
+int run_entry(const sd_fbank_plan* plan, SdFbankCall c, const SdFbankPtrs& p, sd_stream_t stream_) {
+  c.no_plan = !plan;
+  c.no_wav = !p.wav;
+  c.no_out = !p.out;
+  c.no_starts = !p.starts;
+  c.no_lens = !p.lens;
+  c.no_frame_start = !p.frame_start;
+  c.no_ws = !p.ws;
+  c.ws_misaligned = !sd_aligned16(p.ws);
+  SdFbankRoute r;
+  char why[SD_FB_WHY];
+  if (int e = sd_fbank_check(plan ? plan->f : SdFbankFacts{}, c, &r, why)) return sd_set_error(e, "%s", why);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (r.kinds & SD_FB_GENERIC) return sd_fbank_generic_launch(plan, r, c, p, stream);
+  if (r.kinds & SD_FB_ONE_LAUNCH)
+    if (int e = sd_fbank_utt16_launch(plan, r, c, p, stream)) return e;
+  if (r.kinds & SD_FB_FOLDED) return folded_launch(plan, r, c, p, stream);
+  return SD_OK;
+}
+
+// the numbers of a call; run_entry adds what it reads off the pointers
+SdFbankCall call_of(const char* entry, int form, int B, int n, long long n_total, int M, int mean_norm, int ld_out, size_t ws_bytes) {
+  SdFbankCall c = {};
+  c.entry = entry; c.form = form;
+  c.B = B; c.n = n; c.n_total = n_total; c.M = M;
+  c.mean_norm = mean_norm; c.ld_out = ld_out; c.ws_bytes = ws_bytes;
+  return c;
+}
+
+}  // namespace
+
+extern "C" sd_fbank_plan* sd_fbank_plan_create(const float* window, int n_fft, int hop,
+                                               const float* mel_fb, int n_mels,
+                                               int pad_mode, int log_mode, float log_eps, float top_db) {
+  auto fail = [](int code, const char* msg) -> sd_fbank_plan* { sd_set_error(code, "%s", msg); return nullptr; };
+  if (!window || !mel_fb) return fail(SD_ERR_ARG, "sd_fbank_plan_create: null window/mel_fb");
+  if (pad_mode != SD_PAD_ZERO && pad_mode != SD_PAD_REFLECT) return fail(SD_ERR_ARG, "sd_fbank_plan_create: bad pad_mode");
+  if (log_mode != SD_LOG_LN_EPS && log_mode != SD_LOG_DB_TOPDB) return fail(SD_ERR_ARG, "sd_fbank_plan_create: bad log_mode");
+  // any other framing (fbank_batch at sr != 16 kHz, [REF speech_encode.py:14-24]): the DFT and the mel product as implicit GEMMs on
+  // the exact-f32 conv operator (sd_fbank_generic.hip); any window, no symmetry needed
+  const bool generic = n_fft != NFFT || hop != HOP || n_mels > MAX_MELS;
+  if (generic) {
+    if (!sd_fbank_generic_geometry_ok(n_fft, hop, n_mels))
+      return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: need 8 <= n_fft <= 8192, 1 <= hop <= n_fft, 1 <= n_mels <= 256");
+  } else {
+    if (n_mels < 1) return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: n_mels must be positive");
+    for (int k = 1; k < NFFT / 2; ++k)
+      if (window[k] != window[NFFT - k])
+        return fail(SD_ERR_UNSUPPORTED, "sd_fbank_plan_create: window must be symmetric (w[k] == w[n_fft-k])");
+  }
+  // A/B: SD_FBANK_UTT=0 sends every length to the folded kernel
+  static const bool utt_switch = [] { const char* e = sd_experiment_env("SD_FBANK_UTT"); return !(e && atoi(e) == 0); }();
   sd_fbank_plan* plan = new sd_fbank_plan{};
-  plan->n_fft = n_fft; plan->hop = hop; plan->n_mels = n_mels; plan->pad_mode = pad_mode; plan->log_mode = log_mode;
-  plan->log_eps = log_eps; plan->top_db = top_db;
-  hipError_t e1 = hipMalloc(&plan->basis16_dev, V2_BASIS_BYTES);
-  hipError_t e2 = e1 == hipSuccess ? hipMalloc(&plan->melw16_dev, V2_MELW_BYTES) : e1;
-  if (e1 == hipSuccess && e2 == hipSuccess) {
-    e1 = hipMemcpy(plan->basis16_dev, b16.data(), V2_BASIS_BYTES, hipMemcpyHostToDevice);
-    e2 = hipMemcpy(plan->melw16_dev, m16.data(), V2_MELW_BYTES, hipMemcpyHostToDevice);
-  }
-  if (e1 != hipSuccess || e2 != hipSuccess) {
-    sd_set_error(SD_ERR_HIP, "sd_fbank_plan_create: device table upload failed: %s",
-                 hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    if (plan->basis16_dev) (void)hipFree(plan->basis16_dev);
-    if (plan->melw16_dev) (void)hipFree(plan->melw16_dev);
-    delete plan;
-    return nullptr;
-  }
-  if (sd_fbank_utt16_create_tables(plan, window, mel_fb) != SD_OK) {      // tables of the one-launch kernel (sd_fbank_utt16.hip)
-    (void)hipFree(plan->basis16_dev);
-    (void)hipFree(plan->melw16_dev);
-    delete plan;
-    return nullptr;
-  }
-  return plan;
+  SdFbankFacts& f = plan->f;
+  f.n_fft = n_fft; f.hop = hop; f.n_mels = n_mels; f.pad_mode = pad_mode; f.log_mode = log_mode; f.log_eps = log_eps; f.top_db = top_db;
+  f.generic = generic; f.utt_tables = !generic; f.utt_switch = utt_switch;
+  f.fold_threads = 256 * V2_GROUPS; f.fold_lds = V2_LDS_BYTES;
+  int e = generic ? sd_fbank_generic_create_tables(plan, window, mel_fb) : folded_create_tables(plan, window, mel_fb);
+  if (e == SD_OK && !generic) e = sd_fbank_utt16_create_tables(plan, window, mel_fb);      // tables of the one-launch kernel
+  if (e == SD_OK) return plan;
+  sd_fbank_free_tables(plan);
+  delete plan;
+  return nullptr;
 }
 
 extern "C" void sd_fbank_plan_destroy(sd_fbank_plan* plan) {
   if (!plan) return;
-  if (plan->generic) { sd_fbank_generic_destroy_tables(plan); delete plan; return; }
-  (void)hipFree(plan->basis16_dev);
-  (void)hipFree(plan->melw16_dev);
-  sd_fbank_utt16_destroy_tables(plan);
+  sd_fbank_free_tables(plan);
   delete plan;
 }
 
 extern "C" int sd_fbank_num_frames(const sd_fbank_plan* plan, int n) {
   if (!plan || n < 0) return sd_set_error(SD_ERR_ARG, "sd_fbank_num_frames: bad arguments");
-  if (plan->generic) return sd_fbank_generic_num_frames(plan, n);
-  return 1 + n / plan->hop;
+  return sd_fbank_frames(plan->f, n);
 }
 
 extern "C" size_t sd_fbank_workspace_bytes(const sd_fbank_plan* plan, int B, int n) {
-  if (plan && plan->generic) return sd_fbank_generic_workspace_bytes(plan, B, n);
-  return ((size_t)(B > 0 ? B : 0) * sizeof(int) + 255) & ~(size_t)255;
+  return sd_fbank_uniform_ws_bytes(plan ? plan->f : SdFbankFacts{}, B, n);
 }
 
-static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_,
-                        const float* rel_len = nullptr);
+extern "C" size_t sd_fbank_packed_workspace_bytes(const sd_fbank_plan* plan, int B, int M, int n_max) {
+  (void)plan; (void)M; (void)n_max;       // (the per-span max keys and the tile table: B and B + 1 ints)
+  return sd_fbank_packed_ws_bytes(B);
+}
 
 extern "C" int sd_fbank_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n,
                             int mean_norm, float* out_dev, int ld_out,
                             void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
-  return fbank_launch(plan, wav_dev, (long long)B * n, nullptr, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream_);
+  SdFbankPtrs p = {};
+  p.wav = wav_dev; p.out = out_dev; p.ws = ws_dev;
+  return run_entry(plan, call_of("sd_fbank_f32", SD_FB_UNIFORM, B, n, (long long)B * n, 0, mean_norm, ld_out, ws_bytes), p, stream_);
 }
 
 extern "C" int sd_fbank_lens_f32(const sd_fbank_plan* plan, const float* wav_dev, int B, int n, const float* rel_len_dev,
                                  float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
-  return fbank_launch(plan, wav_dev, (long long)B * n, nullptr, B, n, 1, out_dev, ld_out, ws_dev, ws_bytes, stream_, rel_len_dev);
+  SdFbankPtrs p = {};
+  p.wav = wav_dev; p.rel_len = rel_len_dev; p.out = out_dev; p.ws = ws_dev;
+  return run_entry(plan, call_of("sd_fbank_lens_f32", SD_FB_LENS, B, n, (long long)B * n, 0, 1, ld_out, ws_bytes), p, stream_);
 }
 
 extern "C" int sd_fbank_windows_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
                                     int B, int n, int mean_norm, float* out_dev, int ld_out,
                                     void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
-  SD_CHECK_ARG(n_total >= 1, "sd_fbank_windows_f32: n_total=%lld", n_total);
-  SD_CHECK_ARG(B == 0 || starts_dev != nullptr, "sd_fbank_windows_f32: null starts");
-  return fbank_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream_);
+  SdFbankPtrs p = {};
+  p.wav = wav_dev; p.starts = starts_dev; p.out = out_dev; p.ws = ws_dev;
+  return run_entry(plan, call_of("sd_fbank_windows_f32", SD_FB_WINDOWS, B, n, n_total, 0, mean_norm, ld_out, ws_bytes), p, stream_);
 }
 
-static int fbank_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                        int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_,
-                        const float* rel_len) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(plan != nullptr, "sd_fbank_f32: null plan");
-  SD_CHECK_ARG(B >= 0 && n >= 0, "sd_fbank_f32: B=%d n=%d", B, n);
-  if (B == 0) return SD_OK;
-  SD_CHECK_ARG(wav_dev && out_dev, "sd_fbank_f32: null wav/out");
-  SD_CHECK_ARG(ld_out >= plan->n_mels, "sd_fbank_f32: ld_out=%d < n_mels=%d", ld_out, plan->n_mels);
-  // torch.stft(center=True, pad_mode="reflect") rejects n <= n_fft/2; zero padding needs one sample
-  if (plan->pad_mode == SD_PAD_REFLECT)
-    SD_CHECK_ARG(n > plan->n_fft / 2, "sd_fbank_f32: reflect padding of %d needs more than %d samples (got %d)", plan->n_fft / 2, plan->n_fft / 2, n);
-  else
-    SD_CHECK_ARG(n >= 1, "sd_fbank_f32: empty waveform");
-  if (plan->generic) return sd_fbank_generic_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, ws_dev, ws_bytes, stream,
-                                                   rel_len);
-  SD_CHECK_ARG(ws_dev != nullptr && ws_bytes >= sd_fbank_workspace_bytes(plan, B, n),
-               "sd_fbank_f32: workspace too small (%zu < %zu)", ws_bytes, sd_fbank_workspace_bytes(plan, B, n));
-  // utterances whose padded signal fits the CU's LDS: ONE launch, one workgroup per utterance (sd_fbank_utt16.hip)
-  if (n_total >= 4 && sd_fbank_utt16_supported(plan, n))    // (16-byte loads: four samples behind `wav`)
-    return sd_fbank_utt16_launch(plan, wav_dev, n_total, starts_dev, B, n, mean_norm, out_dev, ld_out, stream, rel_len);
-  const int T = 1 + n / HOP;
-  Fbank2Args a;
-  a.wav = wav_dev; a.B = B; a.n = n; a.T = T;
-  a.starts = starts_dev; a.n_total = n_total;
-  a.basis = static_cast<const _Float16*>(plan->basis16_dev); a.melw = static_cast<const __bf16*>(plan->melw16_dev);
-  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
-  a.out = out_dev; a.ld_out = ld_out;
-  a.maxbuf = static_cast<int*>(ws_dev);
-  a.flat = T >= FT;
-  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + plan->n_mels - 1) / plan->n_mels);
-  const long tiles = a.flat ? ((long)B * T + FT - 1) / FT : (long)B * ((T + FT - 1) / FT);
-  const long blocks = (tiles + WAVES - 1) / WAVES;
-  SD_CHECK_ARG(blocks < (1L << 31), "sd_fbank_f32: grid too large");
-  // reset the per-utterance max keys with a kernel, not hipMemsetAsync: a byte-pattern memset node
-  // replayed from a captured hipGraph did not reproduce the eager result (configs[3] test)
-  hipLaunchKernelGGL(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a.maxbuf, B, (int)0x80808080);
-  SD_CHECK_LAUNCH("fill_i32_kernel");
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel<false>), V2_LDS_BYTES));
-  {
-    // algorithmic bytes: waveform read once + log-mel written once (192 320 B per 2 s segment)
-    SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
-    hipLaunchKernelGGL(fbank_logmel_kernel<false>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
-  }
-  SD_CHECK_LAUNCH("fbank_logmel_kernel<uniform>");
-  const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
-  {
-    int R = 320 / plan->n_mels; if (R < 1) R = 1; if (R > T) R = T;
-    int threads = ((R * plan->n_mels + 63) / 64) * 64;
-    hipLaunchKernelGGL(fbank_finalize_kernel<false>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float),
-                       stream, out_dev, ld_out, T, plan->n_mels, a.maxbuf, use_floor, plan->top_db, mean_norm, R, rel_len,
-                       nullptr, nullptr, 0, 0, 0);
-    SD_CHECK_LAUNCH("fbank_finalize_kernel<uniform>");
-  }
-  return SD_OK;
-}
-
-static size_t packed_maxbuf_bytes(int B) { return ((size_t)(B > 0 ? B : 0) * sizeof(int) + 255) & ~(size_t)255; }
-
-extern "C" size_t sd_fbank_packed_workspace_bytes(const sd_fbank_plan* plan, int B, int M, int n_max) {
-  (void)plan; (void)M; (void)n_max;       // (the per-span max keys and the tile table: B and B + 1 ints)
-  if (B <= 0) return 0;
-  return packed_maxbuf_bytes(B) + (((size_t)(B + 1) * sizeof(int) + 255) & ~(size_t)255);
-}
-
-// Packed spans ("Packed spans", sd_hip.h): every span takes the route a call for it alone takes -- up to sd_fbank_utt16_max_n samples the
-// one-launch kernel (one workgroup per span, the others idle out), longer ones the folded kernel over their own tiles + the finalize pass.
-// A pack with spans on both routes is two launches (plus the tile table and the max-key reset); each span's rows are bitwise sd_fbank_f32 of
-// the span alone (B = 1, n = lens[s]).
 extern "C" int sd_fbank_packed_f32(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
                                    const int* lens_dev, const int* frame_start_dev, int B, int M, int n_max,
                                    float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, sd_stream_t stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(plan != nullptr, "sd_fbank_packed_f32: null plan");
-  SD_CHECK_ARG(B >= 0, "sd_fbank_packed_f32: B=%d", B);
-  if (B == 0) return SD_OK;
-  SD_CHECK_ARG(M > 0 && n_max >= 1, "sd_fbank_packed_f32: M=%d n_max=%d", M, n_max);
-  SD_CHECK_ARG(wav_dev && starts_dev && lens_dev && frame_start_dev && out_dev, "sd_fbank_packed_f32: null pointer");
-  SD_CHECK_ARG(n_total >= 4, "sd_fbank_packed_f32: n_total=%lld (at least 4 samples)", n_total);
-  SD_CHECK_ARG(ld_out >= plan->n_mels, "sd_fbank_packed_f32: ld_out=%d < n_mels=%d", ld_out, plan->n_mels);
-  if (plan->generic || plan->pad_mode != SD_PAD_ZERO)
-    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_fbank_packed_f32: packed spans take the 25 ms / 10 ms plan with zero padding (speechbrain)");
-  const size_t need = sd_fbank_packed_workspace_bytes(plan, B, M, n_max);
-  SD_CHECK_ARG(ws_dev && ws_bytes >= need && sd_aligned16(ws_dev), "sd_fbank_packed_f32: workspace %zu < %zu bytes, or unaligned", ws_bytes, need);
-  // every span of the folded route has at most T_s / 32 + 1 tiles: M / 32 + B in all
-  const long blocks = ((long)M / FT + B + WAVES - 1) / WAVES;
-  SD_CHECK_ARG(blocks < (1L << 31) && (long)M / FT + B < (1L << 31), "sd_fbank_packed_f32: grid too large");
-  const int n_split = sd_fbank_utt16_max_n(plan);
-  if (n_split >= 1)
-    if (int e = sd_fbank_utt16_packed_launch(plan, wav_dev, n_total, starts_dev, lens_dev, frame_start_dev, B, M, n_max < n_split ? n_max : n_split,
-                                             out_dev, ld_out, stream))
-      return e;
-  if (n_max <= n_split) return SD_OK;
-  Fbank2Args a = {};
-  a.wav = wav_dev; a.B = B; a.n = n_max; a.T = 1 + n_max / HOP;
-  a.starts = starts_dev; a.n_total = n_total;
-  a.basis = static_cast<const _Float16*>(plan->basis16_dev); a.melw = static_cast<const __bf16*>(plan->melw16_dev);
-  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
-  a.out = out_dev; a.ld_out = ld_out;
-  a.maxbuf = static_cast<int*>(ws_dev);
-  a.flat = 0;
-  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + plan->n_mels - 1) / plan->n_mels);
-  a.lens = lens_dev; a.frame_start = frame_start_dev;
-  a.tile_start = reinterpret_cast<int*>(static_cast<char*>(ws_dev) + packed_maxbuf_bytes(B));
-  a.n_lo = n_split > 0 ? n_split : 0; a.M = M;
-  hipLaunchKernelGGL(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a.maxbuf, B, (int)0x80808080);
-  SD_CHECK_LAUNCH("fill_i32_kernel");
-  hipLaunchKernelGGL(fbank_packed_tiles_kernel, dim3(1), dim3(1024), 0, stream, lens_dev, B, a.n_lo, n_max, const_cast<int*>(a.tile_start));
-  SD_CHECK_LAUNCH("fbank_packed_tiles_kernel");
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_logmel_kernel<true>), V2_LDS_BYTES));
-  hipLaunchKernelGGL(fbank_logmel_kernel<true>, dim3((unsigned)blocks), dim3(256 * V2_GROUPS), V2_LDS_BYTES, stream, a);
-  SD_CHECK_LAUNCH("fbank_logmel_kernel<packed>");
-  const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
-  int R = 320 / plan->n_mels; if (R < 1) R = 1;
-  const int threads = ((R * plan->n_mels + 63) / 64) * 64;
-  hipLaunchKernelGGL(fbank_finalize_kernel<true>, dim3((unsigned)B), dim3(threads), (size_t)R * plan->n_mels * sizeof(float), stream, out_dev,
-                     ld_out, 1, plan->n_mels, a.maxbuf, use_floor, plan->top_db, 1, R, nullptr, lens_dev, frame_start_dev, a.n_lo, n_max, M);
-  SD_CHECK_LAUNCH("fbank_finalize_kernel<packed>");
-  return SD_OK;
+  SdFbankPtrs p = {};
+  p.wav = wav_dev; p.starts = starts_dev; p.lens = lens_dev; p.frame_start = frame_start_dev; p.out = out_dev; p.ws = ws_dev;
+  return run_entry(plan, call_of("sd_fbank_packed_f32", SD_FB_PACKED, B, n_max, n_total, M, 1, ld_out, ws_bytes), p, stream_);
 }

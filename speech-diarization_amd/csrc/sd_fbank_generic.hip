@@ -28,7 +28,6 @@
 namespace {
 
 constexpr int FBG_MAX_NFFT = 8192;
-constexpr size_t FBG_CHUNK_BYTES = (size_t)256 << 20;
 
 struct PadArgs {
   const float* wav; const long long* starts; long long n_total;
@@ -173,40 +172,16 @@ __global__ __launch_bounds__(FIN_THREADS) void fbg_finalize_kernel(FinArgs p) {
   }
 }
 
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-size_t pad_len(const sd_fbank_plan* plan, int n) { return ((size_t)n + 2 * (size_t)(plan->n_fft / 2) + 3) & ~(size_t)3; }
-
-size_t per_utterance_bytes(const sd_fbank_plan* plan, int n, int T) {
-  return (pad_len(plan, n) + (size_t)T * ((size_t)plan->g_nfp + (size_t)plan->g_nmp)) * sizeof(float);
-}
-
-int chunk_utterances(const sd_fbank_plan* plan, int B, int n, int T) {
-  const size_t per = per_utterance_bytes(plan, n, T);
-  size_t bc = FBG_CHUNK_BYTES / (per ? per : 1);
-  if (bc < 1) bc = 1;
-  return (size_t)B < bc ? B : (int)bc;
-}
-
 }  // namespace
 
 bool sd_fbank_generic_geometry_ok(int n_fft, int hop, int n_mels) {
   return n_fft >= 8 && n_fft <= FBG_MAX_NFFT && hop >= 1 && hop <= n_fft && n_mels >= 1 && n_mels <= 256;
 }
 
-// frames of torch.stft(center = True): 1 + (n + 2 (n_fft / 2) - n_fft) / hop  (= 1 + n / hop for an even n_fft)
-int sd_fbank_generic_num_frames(const sd_fbank_plan* plan, int n) {
-  const long long padded = (long long)n + 2 * (plan->n_fft / 2);
-  return padded < plan->n_fft ? 0 : (int)(1 + (padded - plan->n_fft) / plan->hop);
-}
-
 int sd_fbank_generic_create_tables(sd_fbank_plan* plan, const float* window, const float* mel_fb) {
-  const int n_fft = plan->n_fft, n_mels = plan->n_mels;
+  const int n_fft = plan->f.n_fft, n_mels = plan->f.n_mels;
   const int n_freq = n_fft / 2 + 1;
-  plan->g_nfreq = n_freq;
-  plan->g_nfp = round_up(n_freq, 32);                          // 32 bins = one 64-column tile of the DFT kernel; the mel product's K step
-  plan->g_nmp = round_up(n_mels, 4);
-  const int nfp = plan->g_nfp, ncol = 2 * nfp;
+  const int nfp = sd_fb::fbg_nfp(n_fft), ncol = 2 * nfp;
   // twiddles in float64, [n_fft][2 nfp]: (re, im) columns of a bin side by side
   std::vector<double> tw((size_t)n_fft * ncol, 0.0);
   for (int pos = 0; pos < n_fft; ++pos)
@@ -220,61 +195,34 @@ int sd_fbank_generic_create_tables(sd_fbank_plan* plan, const float* window, con
   std::vector<float> wm((size_t)n_mels * nfp, 0.f);
   for (int m = 0; m < n_mels; ++m)
     for (int f = 0; f < n_freq; ++f) wm[(size_t)m * nfp + f] = mel_fb[(size_t)f * n_mels + m];
-  hipError_t e = hipMalloc(&plan->g_wdft_dev, tw.size() * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&plan->g_wmel_dev, wm.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(plan->g_wdft_dev, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(plan->g_wmel_dev, wm.data(), wm.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    sd_fbank_generic_destroy_tables(plan);
-    return sd_set_error(SD_ERR_HIP, "sd_fbank_plan_create: device table upload failed: %s", hipGetErrorString(e));
-  }
-  return SD_OK;
+  if (int e = sd_fbank_upload(plan, &plan->g_wdft_dev, tw.data(), tw.size() * sizeof(double))) return e;
+  return sd_fbank_upload(plan, &plan->g_wmel_dev, wm.data(), wm.size() * sizeof(float));
 }
 
-void sd_fbank_generic_destroy_tables(sd_fbank_plan* plan) {
-  if (plan->g_wdft_dev) (void)hipFree(plan->g_wdft_dev);
-  if (plan->g_wmel_dev) (void)hipFree(plan->g_wmel_dev);
-  plan->g_wdft_dev = plan->g_wmel_dev = nullptr;
-}
-
-size_t sd_fbank_generic_workspace_bytes(const sd_fbank_plan* plan, int B, int n) {
-  if (B <= 0 || n < 0) return 256;
-  const int T = sd_fbank_generic_num_frames(plan, n);
-  return ((size_t)chunk_utterances(plan, B, n, T) * per_utterance_bytes(plan, n, T) + 1023) & ~(size_t)255;
-}
-
-int sd_fbank_generic_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                            int mean_norm, float* out_dev, int ld_out, void* ws_dev, size_t ws_bytes, hipStream_t stream,
-                            const float* rel_len) {
-  const int T = sd_fbank_generic_num_frames(plan, n);
-  SD_CHECK_ARG(T >= 1, "sd_fbank_f32: %d samples give no frame at n_fft=%d", n, plan->n_fft);
-  const int nfp = plan->g_nfp, nmp = plan->g_nmp;
-  SD_CHECK_ARG((long long)T * B < (1LL << 31), "sd_fbank_f32: too many frames");
-  SD_CHECK_ARG(sd_aligned16(ws_dev) && ws_bytes >= sd_fbank_generic_workspace_bytes(plan, B, n), "sd_fbank_f32: workspace too small or misaligned");
-  const int Bc = chunk_utterances(plan, B, n, T);
-  const int Lp = (int)pad_len(plan, n);
-  float* xpad = static_cast<float*>(ws_dev);
+int sd_fbank_generic_launch(const sd_fbank_plan* plan, const SdFbankRoute& r, const SdFbankCall& c, const SdFbankPtrs& p, hipStream_t stream) {
+  const SdFbankFacts& f = plan->f;
+  const int B = c.B, n = c.n, T = r.T, nfp = r.g_nfp, nmp = r.g_nmp, Bc = r.g_Bc, Lp = r.g_Lp;
+  float* xpad = static_cast<float*>(p.ws);
   float* pw = xpad + (size_t)Bc * Lp;
   float* mel = pw + (size_t)Bc * T * nfp;
-  const int use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int nb = B - b0 < Bc ? B - b0 : Bc;
     const long long M = (long long)nb * T;
-    PadArgs pa{wav_dev, starts_dev, n_total, xpad, b0, nb, n, Lp, plan->n_fft / 2, plan->pad_mode};
+    PadArgs pa{p.wav, p.starts, c.n_total, xpad, b0, nb, n, Lp, f.n_fft / 2, f.pad_mode};
     const long long tot = (long long)nb * Lp;
     const unsigned grid = (unsigned)((tot + 255) / 256 < 65536 ? (tot + 255) / 256 : 65536);
     hipLaunchKernelGGL(fbg_pad_kernel, dim3(grid), dim3(256), 0, stream, pa);
     SD_CHECK_LAUNCH("fbg_pad_kernel");
-    DftArgs da{xpad, Lp, plan->hop, T, M, static_cast<const double*>(plan->g_wdft_dev), plan->n_fft, 2 * nfp, pw, nfp};
+    DftArgs da{xpad, Lp, f.hop, T, M, static_cast<const double*>(plan->g_wdft_dev), f.n_fft, 2 * nfp, pw, nfp};
     hipLaunchKernelGGL(fbg_dft_f64_kernel, dim3((unsigned)((M + DT - 1) / DT), (unsigned)(2 * nfp / DT)), dim3(256), 0, stream, da);
     SD_CHECK_LAUNCH("fbg_dft_f64_kernel");
     sd_conv_args a;
     std::memset(&a, 0, sizeof(a));
     a.x = pw; a.lda = nfp; a.w = plan->g_wmel_dev; a.w_dtype = SD_DT_F32; a.y = mel; a.ldo = nmp;
-    a.M = (int)M; a.T = 1; a.cin = nfp; a.cin_pad = nfp; a.cout = plan->n_mels; a.taps = 1; a.dil = 1;
+    a.M = (int)M; a.T = 1; a.cin = nfp; a.cin_pad = nfp; a.cout = f.n_mels; a.taps = 1; a.dil = 1;
     a.act = SD_ACT_NONE; a.act2 = SD_ACT_NONE;
     if (int e = sd_conv1d_cl_f32(&a, stream)) return e;
-    FinArgs fa{mel, nmp, T, 0, out_dev, ld_out, b0, T, plan->n_mels, plan->log_mode, plan->log_eps, plan->top_db, use_floor, mean_norm, rel_len};
+    FinArgs fa{mel, nmp, T, 0, p.out, c.ld_out, b0, T, f.n_mels, f.log_mode, f.log_eps, f.top_db, r.use_floor, c.mean_norm, p.rel_len};
     hipLaunchKernelGGL(fbg_finalize_kernel, dim3((unsigned)nb), dim3(FIN_THREADS), 0, stream, fa);
     SD_CHECK_LAUNCH("fbg_finalize_kernel");
   }

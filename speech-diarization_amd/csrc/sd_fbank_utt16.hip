@@ -41,25 +41,17 @@
 #include "sd_conv_tile.h"
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
 namespace {
 
-constexpr int NFFT = 400;
-constexpr int HOP = 160;
-constexpr int NFREQ = 201;
+using namespace sd_fb;                  // the framing and this kernel's LDS layout: sd_fbank_route.h
 constexpr int NN2 = 25;
 constexpr int NBLK = 7;                 // blocks of four n2 (28 >= 25)
 constexpr int FT = 16;                  // frames per wave tile
-constexpr int MELP = 81;
-constexpr int U16_MAX_T = 208;          // 13 tiles: two rounds of the 8 waves
-constexpr int U16_THREADS = 512;
 constexpr int U16_MAX_GROUPS = (((U16_MAX_T * HOP - 1) + NFFT + 3) / 4 + U16_THREADS - 1) / U16_THREADS;
-constexpr int A2_BYTES = 16 * 1024;
-constexpr int RING_BYTES = 16 * 1024;   // two chunks of eight 1 KB fragments: the streamed tables, shared by the eight waves
-constexpr int SCRATCH_FLOATS = 64;      // [0..15] wave maxima of the log-mel rows, [16..23] of |x|, [24..31] "this wave saw a NaN sample"
-constexpr int LDS_LIMIT = 160 * 1024;
 constexpr float XMAX = 16.f;
 constexpr double A1SCALE = 32.0, A2SCALE = 32.0;
 constexpr float YSCALE = 1.0f / 256.0f;
@@ -107,8 +99,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for<I + 1, N>(f);
   }
 }
-
-__host__ __device__ constexpr int img_words(int n) { return (n + NFFT) + (n + NFFT) / HOP + 1; }
 
 // r[i] holds in lane group g the value (i, g)  ->  r[i] holds in lane group g the value (g, i)
 __device__ __forceinline__ void transpose4(unsigned (&r)[4]) {
@@ -643,24 +633,6 @@ __global__ __launch_bounds__(U16_THREADS, 2) void fbank_utt16_kernel(const U16Ar
   U16_STAMP(15);
 }
 
-size_t u16_lds_bytes(int n, int T) {
-  const size_t words = (size_t)img_words(n) > (size_t)T * MELP ? (size_t)img_words(n) : (size_t)T * MELP;
-  return (size_t)A2_BYTES + RING_BYTES + SCRATCH_FLOATS * 4 + words * 4;
-}
-
-unsigned short bf16_bits(float v) {
-  unsigned u;
-  std::memcpy(&u, &v, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-float bf16_value(unsigned short b) {
-  const unsigned u = (unsigned)b << 16;
-  float v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-
 // what row (lane group G, component c) of the stage-1 product is: k1 and re / im, or one of the two reals
 struct RowOf { int k1; int kind; };      // kind 0: re, 1: im, 2: Y[0] (real), 3: rho (Y[8] rotated to the real axis)
 RowOf row_of(int G, int c) {
@@ -680,11 +652,11 @@ extern "C" int sd_debug_read_utt16_stamps(unsigned long long* host, int n) {
 #endif
 
 int sd_fbank_utt16_create_tables(sd_fbank_plan* plan, const float* window, const float* mel_fb) {
-  const int n_mels = plan->n_mels;
+  const int n_mels = plan->f.n_mels;
   std::vector<unsigned short> tab((size_t)T_FRAGS * 512);
   auto put_f16 = [&](size_t frag_hi, size_t frag_lo, int l, int e, double v) {
-    const _Float16 hi = (_Float16)(float)v;
-    const _Float16 lo = (_Float16)(float)(v - (double)(float)hi);
+    _Float16 hi, lo;
+    sd_split_f16(v, &hi, &lo);
     tab[frag_hi * 512 + l * 8 + e] = __builtin_bit_cast(unsigned short, hi);
     tab[frag_lo * 512 + l * 8 + e] = __builtin_bit_cast(unsigned short, lo);
   };
@@ -704,8 +676,8 @@ int sd_fbank_utt16_create_tables(sd_fbank_plan* plan, const float* window, const
         else if (r.kind == 1) v = -w * std::sin(ang);
         else if (r.kind == 2) v = w;
         else v = w * std::cos(ang - M_PI * (double)n2 / 25.0);
-        const _Float16 hi = (_Float16)(float)v;
-        const _Float16 lo = (_Float16)(float)(v - (double)(float)hi);
+        _Float16 hi, lo;
+        sd_split_f16(v, &hi, &lo);
         const size_t f0 = (size_t)T_STREAM + S_A1 + 2 * n2;
         tab[f0 * 512 + l * 8 + e] = __builtin_bit_cast(unsigned short, hi);
         tab[(f0 + 1) * 512 + l * 8 + e] = k < 16 ? __builtin_bit_cast(unsigned short, lo) : (unsigned short)0;
@@ -757,90 +729,33 @@ int sd_fbank_utt16_create_tables(sd_fbank_plan* plan, const float* window, const
           }
           float w = 0.f;
           if (bin >= 0 && bin < NFREQ && m < n_mels) w = (float)((double)mel_fb[(size_t)bin * n_mels + m] * PSCALE);
-          const unsigned short w1 = bf16_bits(w);
+          const unsigned short w1 = sd_bf16_bits(w);
           const size_t f0 = (size_t)T_STREAM + S_MEL + (size_t)(pr * MEL_TILES + t) * 2;   // consumption order: problem-major
           tab[f0 * 512 + l * 8 + e] = w1;
-          tab[(f0 + 1) * 512 + l * 8 + e] = bf16_bits(w - bf16_value(w1));
+          tab[(f0 + 1) * 512 + l * 8 + e] = sd_bf16_bits(w - sd_bf16_value(w1));
         }
-  plan->utt16_tables_dev = nullptr;
-  hipError_t e = hipMalloc(&plan->utt16_tables_dev, (size_t)T_FRAGS * 1024);
-  if (e == hipSuccess) e = hipMemcpy(plan->utt16_tables_dev, tab.data(), (size_t)T_FRAGS * 1024, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    sd_fbank_utt16_destroy_tables(plan);
-    return sd_set_error(SD_ERR_HIP, "sd_fbank_plan_create: device table upload failed: %s", hipGetErrorString(e));
-  }
-  return SD_OK;
+  return sd_fbank_upload(plan, &plan->utt16_tables_dev, tab.data(), (size_t)T_FRAGS * 1024);
 }
 
-void sd_fbank_utt16_destroy_tables(sd_fbank_plan* plan) {
-  if (plan->utt16_tables_dev) (void)hipFree(plan->utt16_tables_dev);
-  plan->utt16_tables_dev = nullptr;
-}
-
-bool sd_fbank_utt16_supported(const sd_fbank_plan* plan, int n) {
-  static const bool on = [] { const char* e = sd_experiment_env("SD_FBANK_UTT"); return !(e && atoi(e) == 0); }();   // A/B: SD_FBANK_UTT=0 sends every length to the folded kernel
-  if (!on || !plan->utt16_tables_dev) return false;
-  const int T = 1 + n / HOP;
-  return T <= U16_MAX_T && u16_lds_bytes(n, T) <= (size_t)LDS_LIMIT;
-}
-
-int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev, int B, int n,
-                          int mean_norm, float* out_dev, int ld_out, hipStream_t stream, const float* rel_len) {
-  const int T = 1 + n / HOP;
+int sd_fbank_utt16_launch(const sd_fbank_plan* plan, const SdFbankRoute& r, const SdFbankCall& c, const SdFbankPtrs& p, hipStream_t stream) {
+  const SdFbankFacts& f = plan->f;
+  const bool packed = c.form == SD_FB_PACKED;
   U16Args a;
-  a.wav = wav_dev; a.B = B; a.n = n; a.T = T;
-  a.starts = starts_dev; a.n_total = n_total;
+  a.wav = p.wav; a.B = c.B; a.n = r.n_cap; a.T = frames(r.n_cap);
+  a.starts = p.starts; a.n_total = c.n_total;
   a.tables = static_cast<const char*>(plan->utt16_tables_dev);
-  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
-  a.top_db = plan->top_db;
-  a.use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
-  a.mean_norm = mean_norm;
-  a.rel_len = rel_len;
-  a.out = out_dev; a.ld_out = ld_out;
-  const int per_row = plan->n_mels % 4 == 0 ? plan->n_mels / 4 : plan->n_mels;
-  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + per_row - 1) / per_row);
-  a.lens = nullptr; a.frame_start = nullptr; a.M = 0;
-  const size_t lds = u16_lds_bytes(n, T);
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel<false>), LDS_LIMIT));
+  a.n_mels = f.n_mels; a.pad_mode = f.pad_mode; a.log_mode = f.log_mode; a.log_eps = f.log_eps;
+  a.top_db = f.top_db; a.use_floor = r.use_floor; a.mean_norm = c.mean_norm; a.rel_len = p.rel_len;
+  a.out = p.out; a.ld_out = c.ld_out;
+  a.inv_mels = r.inv_row;
+  a.lens = p.lens; a.frame_start = p.frame_start; a.M = c.M;
+  const auto kernel = packed ? fbank_utt16_kernel<true> : fbank_utt16_kernel<false>;
+  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(kernel), LDS_LIMIT));
   {
-    SdProfScope prof(SD_PROF_FBANK, stream, (double)B * ((double)n * 4.0 + (double)T * plan->n_mels * 4.0));
-    hipLaunchKernelGGL(fbank_utt16_kernel<false>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
+    std::optional<SdProfScope> prof;      // uniform calls are timed
+    if (!packed) prof.emplace(SD_PROF_FBANK, stream, (double)c.B * ((double)c.n * 4.0 + (double)a.T * f.n_mels * 4.0));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.utt16.grid), dim3(r.utt16.block), r.utt16.lds, stream, a);
   }
-  SD_CHECK_LAUNCH("fbank_utt16_kernel<uniform>");
-  return SD_OK;
-}
-
-int sd_fbank_utt16_max_n(const sd_fbank_plan* plan) {
-  if (!sd_fbank_utt16_supported(plan, 1)) return 0;
-  int lo = 1, hi = (U16_MAX_T + 1) * HOP;       // supported(lo); not supported(hi): 1 + hi / 160 frames > U16_MAX_T
-  while (hi - lo > 1) {
-    const int mid = lo + (hi - lo) / 2;
-    if (sd_fbank_utt16_supported(plan, mid)) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-int sd_fbank_utt16_packed_launch(const sd_fbank_plan* plan, const float* wav_dev, long long n_total, const long long* starts_dev,
-                                 const int* lens_dev, const int* frame_start_dev, int B, int M, int n_cap, float* out_dev, int ld_out,
-                                 hipStream_t stream) {
-  const int T = 1 + n_cap / HOP;
-  U16Args a;
-  a.wav = wav_dev; a.B = B; a.n = n_cap; a.T = T;
-  a.starts = starts_dev; a.n_total = n_total;
-  a.tables = static_cast<const char*>(plan->utt16_tables_dev);
-  a.n_mels = plan->n_mels; a.pad_mode = plan->pad_mode; a.log_mode = plan->log_mode; a.log_eps = plan->log_eps;
-  a.top_db = plan->top_db;
-  a.use_floor = plan->log_mode == SD_LOG_DB_TOPDB && plan->top_db >= 0.f;
-  a.mean_norm = 1;
-  a.rel_len = nullptr;
-  a.out = out_dev; a.ld_out = ld_out;
-  const int per_row = plan->n_mels % 4 == 0 ? plan->n_mels / 4 : plan->n_mels;
-  a.inv_mels = (unsigned)((((unsigned long long)1 << 32) + per_row - 1) / per_row);
-  a.lens = lens_dev; a.frame_start = frame_start_dev; a.M = M;
-  const size_t lds = u16_lds_bytes(n_cap, T);      // (monotone in n: enough for every span the kernel takes, lens[b] <= n_cap)
-  SD_CHECK_HIP(sd_func_max_lds(reinterpret_cast<const void*>(fbank_utt16_kernel<true>), LDS_LIMIT));
-  hipLaunchKernelGGL(fbank_utt16_kernel<true>, dim3((unsigned)B), dim3(U16_THREADS), lds, stream, a);
-  SD_CHECK_LAUNCH("fbank_utt16_kernel<packed>");
+  SD_CHECK_LAUNCH(packed ? "fbank_utt16_kernel<packed>" : "fbank_utt16_kernel<uniform>");
   return SD_OK;
 }

@@ -141,7 +141,7 @@ def test_fbank_short_segments_and_errors(dev):
     from speech_diarization_amd.engine import fbank_device
     from speech_diarization_amd.features import FbankPlan
     plan = FbankPlan("speechbrain")
-    wav = synth.synthetic_segments(1, 9, 1600)             # T = 11 < 32: one tile row per utterance
+    wav = synth.synthetic_segments(1, 9, 1600)             # T = 11: the one-launch kernel, one workgroup per utterance
     got = fbank_device(torch.from_numpy(wav).to(dev), plan).cpu().numpy()
     assert np.abs(got - fbank_ref.speechbrain_fbank_ref(wav)).max() < 1e-3
     assert fbank_device(torch.zeros(0, 1600, device=dev), plan).shape == (0, 11, 80)
@@ -149,6 +149,26 @@ def test_fbank_short_segments_and_errors(dev):
         fbank_device(torch.zeros(1, 150, device=dev), FbankPlan("torchaudio"))
     with pytest.raises(AssertionError):
         fbank_device(torch.zeros(1600, device=dev), plan)
+
+
+@pytest.mark.parametrize("B,n,route", [(1, 3, ["fill_i32_kernel", "fbank_logmel_kernel<uniform>", "fbank_finalize_kernel<uniform>"]),
+                                       (2, 2, ["fbank_utt16_kernel<uniform>"])])
+def test_fbank_with_fewer_than_four_samples_behind_wav(dev, B, n, route):
+    """The one-launch kernel loads 16 bytes at a time, so a call with fewer than four samples behind `wav` (B n <= 3) is the one uniform
+    call of the shipped build that reaches the folded kernel's tile-per-row walk (T < 32: flat = 0); four samples take the one-launch
+    kernel again.  One frame of zero-padded signal, against float64; 1e-3 on the dB scale as everywhere in this module."""
+    from oracle import fbank_ref
+    from speech_diarization_amd import synth
+    from speech_diarization_amd.engine import fbank_device
+    from speech_diarization_amd.features import FbankPlan
+    wav = synth.synthetic_segments(7, B, n, std=0.2)
+    plan = FbankPlan("speechbrain")
+    for mean_norm in (False, True):
+        with expect_launches(exactly=route, family=FBANK):
+            got = fbank_device(torch.from_numpy(wav).to(dev), plan, mean_norm=mean_norm).cpu().numpy()
+        ref = fbank_ref.speechbrain_fbank_ref(wav, mean_norm=mean_norm)
+        assert got.shape == ref.shape == (B, 1, 80)
+        assert np.abs(got - ref).max() < 1e-3, (B, n, mean_norm, np.abs(got - ref).max())
 
 
 @pytest.fixture(params=["auto", "split32", "tiles128", "tiles64", "rows80", "rows96", "rows112", "wide256"])

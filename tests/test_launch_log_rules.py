@@ -97,7 +97,7 @@ def test_every_kernel_has_a_label():
     assert kernels == named, (sorted(kernels - named), sorted(named - kernels))
     # every label is handed to the log: it stands in an SD_CHECK_LAUNCH or in a table / function such a call reads.  The conv operators
     # have one SD_CHECK_LAUNCH(c.label) per file, behind the switch over the ids of sd_conv_label's table: every id of the table is a case
-    assert len(re.findall(r"\bSD_CHECK_LAUNCH\(", text)) >= 43
+    assert len(re.findall(r"\bSD_CHECK_LAUNCH\(", text)) == 39        # (43 until each fbank launch was written once: one site serves both instantiations)
     assert len(re.findall(r"\bSD_CHECK_LAUNCH\(c\.label\)", text)) == 2
     table = _function_text_c(_sources()["sd_conv_choice.h"], "sd_conv_label")
     ids = set(re.findall(r"case (SD_K_[A-Z0-9_]+):", table)) | {"SD_K_SPLIT_N128"}          # (the table's default)
