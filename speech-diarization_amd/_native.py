@@ -197,6 +197,17 @@ HDBSCAN_PROTOTYPES = {
     "sd_hdb_outgoing_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own
+SD_DIAG_ABI_VERSION = 1
+_D = C.c_double
+DIAG_PROTOTYPES = {
+    "sd_diag_abi_version": (_I, []),
+    "sd_whiten_stats_workspace_bytes": (_Z, [_I, _I]),
+    "sd_whiten_stats_f64": (_I, [_P, C.c_long, _I, _I, _P, _P, C.c_long, _P, _Z, _P]),
+    "sd_whiten_apply_f64": (_I, [_P, C.c_long, _I, _I, _P, _P, C.c_long, _D, _P, C.c_long, _P]),
+    "sd_label_centroids_f32": (_I, [_P, C.c_long, _I, _I, _P, _I, _D, _P, C.c_long, _P, _P]),
+}
+
 # include/sd_hip_trace.h: the launch log and the ECAPA plan, same shared object, a table and a version of its own
 SD_TRACE_ABI_VERSION = 3
 TRACE_PROTOTYPES = {
@@ -237,6 +248,7 @@ def load() -> C.CDLL:
                 ("sd_hip_spectral.h", SPECTRAL_PROTOTYPES, "sd_spectral_abi_version", SD_SPECTRAL_ABI_VERSION, "spectral "),
                 ("sd_hip_ahc.h", AHC_PROTOTYPES, "sd_ahc_abi_version", SD_AHC_ABI_VERSION, "AHC "),
                 ("sd_hip_hdbscan.h", HDBSCAN_PROTOTYPES, "sd_hdbscan_abi_version", SD_HDBSCAN_ABI_VERSION, "HDBSCAN "),
+                ("sd_hip_diag.h", DIAG_PROTOTYPES, "sd_diag_abi_version", SD_DIAG_ABI_VERSION, "diag "),
                 ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
             missing = [name for name in table if not hasattr(lib, name)]
             if missing:

@@ -618,3 +618,65 @@ def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws:
         N.check(lib.sd_hdb_outgoing_f32(rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(),
                                         ws.data_ptr(), ws.numel() * ws.element_size(), _stream(rows)), "sd_hdb_outgoing_f32")
     return nn, best
+
+
+# ----------------------------------------------------------------------------- f64 whitening and cluster centres (include/sd_hip_diag.h)
+
+def whiten_stats(rows: torch.Tensor, ws: torch.Tensor | None = None):
+    """Column means and the centred Gram matrix of rows f32 [n >= 2, d <= 256] in f64 on the f64 matrix cores, two passes as np.cov:
+    -> (mean f64 [d], gram f64 [d, d] = sum_i (x_i - mean)^T (x_i - mean), exactly symmetric; divide by n - 1 for the covariance).
+    Rows are read in place (row stride a multiple of 4, 16-byte aligned); bitwise reproducible, the summation order depends on (n, d)
+    alone.  `ws`: a uint8 workspace of at least sd_whiten_stats_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    _need_cuda(rows)
+    n, d, ld = _rows_ld(rows, "rows")
+    mean = torch.empty((d,), dtype=torch.float64, device=rows.device)
+    gram = torch.empty((d, d), dtype=torch.float64, device=rows.device)
+    lib = N.load()
+    with torch.cuda.device(rows.device):
+        ws = _workspace(ws, int(lib.sd_whiten_stats_workspace_bytes(n, d)), rows.device)
+        N.check(lib.sd_whiten_stats_f64(rows.data_ptr(), ld, n, d, mean.data_ptr(), gram.data_ptr(), d, ws.data_ptr(),
+                                        ws.numel() * ws.element_size(), _stream(rows)), "sd_whiten_stats_f64")
+    return mean, gram
+
+
+def whiten_apply(rows: torch.Tensor, mean: torch.Tensor, W: torch.Tensor, eps_add: float = 1e-9) -> torch.Tensor:
+    """out[i] = f32(v / (||v|| + eps_add)), v = (rows[i] - mean) @ W in f64 on the f64 matrix cores: rows f32 [n, d <= 256] read in
+    place, mean f64 [d], W f64 [d, d] (symmetry is not assumed) -> f32 [n, d]; one rounding to f32."""
+    _need_cuda(rows, mean, W)
+    n, d, ld = _rows_ld(rows, "rows")
+    mean = mean.contiguous()
+    W = W.contiguous()
+    if mean.dtype != torch.float64 or mean.shape != (d,) or W.dtype != torch.float64 or W.shape != (d, d):
+        raise ValueError(f"mean {tuple(mean.shape)} {mean.dtype} / W {tuple(W.shape)} {W.dtype} must be f64 [{d}] and f64 [{d}, {d}]")
+    out = torch.empty((n, d), dtype=torch.float32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        N.check(N.load().sd_whiten_apply_f64(rows.data_ptr(), ld, n, d, mean.data_ptr(), W.data_ptr(), d, C.c_double(eps_add), out.data_ptr(), d,
+                                             _stream(rows)), "sd_whiten_apply_f64")
+    return out
+
+
+def label_centroids(rows: torch.Tensor, labels: torch.Tensor, k: int, eps_add: float = 1e-9):
+    """The unit mean of every label's rows: rows f32 [n, d <= 256] read in place, labels int32 [n], 1 <= k <= 1024 ->
+    (centres f32 [k, d], count int32 [k]).  The mean is accumulated in f64 in ascending row order and divided by (its norm + eps_add);
+    a label outside [0, k) is skipped, a label without rows gives a zero row and count 0."""
+    _need_cuda(rows, labels)
+    n, d, ld = _rows_ld(rows, "rows")
+    if labels.dtype != torch.int32 or labels.shape != (n,) or not labels.is_contiguous():
+        raise ValueError(f"labels must be a contiguous int32 vector of {n} entries, got {tuple(labels.shape)} {labels.dtype}")
+    k = int(k)
+    out = torch.empty((max(k, 0), d), dtype=torch.float32, device=rows.device)
+    count = torch.empty((max(k, 0),), dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        N.check(N.load().sd_label_centroids_f32(rows.data_ptr(), ld, n, d, labels.data_ptr(), k, C.c_double(eps_add), out.data_ptr(), d,
+                                                count.data_ptr(), _stream(rows)), "sd_label_centroids_f32")
+    return out, count
+
+
+def rows_product(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a @ b.T of f32 rows a [n, d], b [k, d] -> f32 [n, k] on the f32 matrix cores (exact f32 products): the operator behind the
+    1x1 convs at T = 1 with b as the packed weights, as the three products of `asnorm_scores`."""
+    _need_cuda(a, b)
+    a, b = a.contiguous().float(), b.contiguous().float()
+    d = a.shape[1]
+    wp = pack_weight(b.unsqueeze(2), b.device, torch.float32) if d % 32 else b.reshape(b.shape[0], 1, d).contiguous()
+    return conv1d_cl(a, wp, 1, cin=d)
