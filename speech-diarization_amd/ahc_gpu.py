@@ -35,32 +35,18 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import ops
+from .device_rows import DeviceRoute, operator_for, upload_rows
 
-class DeviceSums:
-    """The two kernels of include/sd_hip_ahc.h over cluster sums that live on the GPU."""
 
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the device AHC route takes its rows as a GPU tensor; there is no CPU fallback")
-        self._ws = None
-
-    def normalise(self, X: torch.Tensor) -> torch.Tensor:
-        """Unit rows, a zero row left zero (sklearn `normalize`), f32 [N, D padded to a multiple of 4 with zero columns]."""
-        from . import ops
-        Xn = ops.l2norm_rows(X, sklearn_zero_guard=True)
-        pad = -Xn.shape[1] % 4
-        return torch.nn.functional.pad(Xn, (0, pad)) if pad else Xn
+class DeviceSums(DeviceRoute):
+    """The two kernels of include/sd_hip_ahc.h over cluster sums that live on the GPU; the workspace is kept between calls."""
+    route = "AHC"
 
     def nearest(self, sums: torch.Tensor, inv_count: torch.Tensor):
-        from . import _native, ops
-        need = int(_native.load().sd_ahc_nearest_workspace_bytes(sums.shape[0], sums.shape[1]))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        return ops.ahc_nearest(sums, inv_count, ws=self._ws)
+        return ops.ahc_nearest(sums, inv_count, ws=self.ws)
 
     def merge(self, sums, count, inv_count, nn, best, cos_thr: float):
-        from . import ops
         return ops.ahc_merge(sums, count, inv_count, nn, best, cos_thr)
 
 
@@ -73,10 +59,7 @@ def ahc_cosine_rows(X, cos_thr: float = 0.70, *, operator=None, return_info: boo
     Early returns as in `cluster.ahc_cosine`: N = 0 and N = 1.  A non-finite row raises ValueError before anything is launched."""
     from . import cluster
     info = {"rounds": 0, "clusters": 0, "gram_rows": 0, "last_best": float("-inf")}
-    if operator is None:
-        if not isinstance(X, torch.Tensor) or X.device.type != "cuda":
-            raise RuntimeError("the device AHC route takes its rows as a GPU tensor; there is no CPU fallback")
-        operator = DeviceSums(X.device)
+    operator = operator_for(X, operator, DeviceSums)
     X = torch.as_tensor(X)
     if X.dim() != 2:
         raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
@@ -138,7 +121,5 @@ class AhcGpuClusterer:
     def fit_predict(self, X) -> np.ndarray:
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
         if self.operator is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("AhcGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
-            X = X.cuda()
+            X = upload_rows(X, "AhcGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
         return ahc_cosine_rows(X, self.cos_thr, operator=self.operator)

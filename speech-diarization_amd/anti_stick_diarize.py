@@ -463,15 +463,13 @@ def cluster_hdbscan(embs: np.ndarray, min_cluster_size: int = 2, clusterer_facto
             raise ValueError(f"use_gpu must be False, True or 'rows', got {use_gpu!r}")
         if clusterer_factory is not None:
             raise ValueError("use_gpu='rows' is a clusterer of its own; it takes no clusterer_factory")
-        import torch
         from . import hdbscan_gpu
+        from .device_rows import upload_rows
         embs = np.asarray(embs)
         if embs.shape[0] < 2:            # as cluster.cluster_hdbscan: one segment is one speaker
             return np.zeros(embs.shape[0], dtype=int)
-        if not torch.cuda.is_available():
-            raise RuntimeError("use_gpu='rows' runs on the HIP path (a visible GPU); there is no CPU fallback")
         embs_norm = embs / (np.linalg.norm(embs, axis=1, keepdims=True) + 1e-8)
-        rows = torch.from_numpy(np.ascontiguousarray(embs_norm, dtype=np.float32)).cuda()
+        rows = upload_rows(embs_norm, "use_gpu='rows' runs on the HIP path (a visible GPU); there is no CPU fallback")
         return hdbscan_gpu.hdbscan_rows(rows, min_cluster_size, None, True, metric="cosine")
     aff = (lambda x: cosine_affinity(x, True)) if use_gpu else None
     return cluster.cluster_hdbscan(embs, min_cluster_size, clusterer_factory, affinity=aff)

@@ -25,17 +25,21 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import ops
+from .device_rows import DeviceRoute
+
 APPLY_BLOCKS = (8, 16, 24, 32)        # block widths sd_affinity_apply_f32 takes
 
 
-class DeviceOperator:
+class DeviceOperator(DeviceRoute):
     """max(K, 0) for an f32 affinity that lives on the GPU.  K is read in place on every pass and never copied, unless it is not
     symmetric: then 0.5 (K + K^T) is formed once, as the host functions do (`assume_symmetric=True` skips the check; the output
     of `ops.cosine_affinity` is exactly symmetric)."""
 
+    route, takes = "spectral", "the affinity"
+
     def __init__(self, K: torch.Tensor, assume_symmetric: bool = False):
-        if not isinstance(K, torch.Tensor) or K.device.type != "cuda":
-            raise RuntimeError("the device spectral route takes the affinity as a GPU tensor; there is no CPU fallback")
+        super().__init__(self.guard(K))
         if K.dim() != 2 or K.shape[0] != K.shape[1]:
             raise ValueError(f"affinity must be square, got {tuple(K.shape)}")
         K = K if K.dtype == torch.float32 and (K.stride(1) == 1 or K.shape[0] <= 1) else K.float().contiguous()
@@ -43,16 +47,12 @@ class DeviceOperator:
             K = 0.5 * (K + K.T)
         self.K = K
         self.n = K.shape[0]
-        self.device = K.device
-        self._ws = None
 
     def degree(self, zero_diag: bool) -> torch.Tensor:
-        from . import ops
         return ops.affinity_degree(self.K, zero_diag)
 
     def apply(self, scale: torch.Tensor, V: torch.Tensor, zero_diag: bool) -> torch.Tensor:
         """V f32 [n, c], any c >= 1: padded with zero columns to the next block width the kernel takes, in pieces of at most 32."""
-        from . import _native, ops
         out = []
         for c0 in range(0, V.shape[1], APPLY_BLOCKS[-1]):
             piece = V[:, c0:c0 + APPLY_BLOCKS[-1]]
@@ -60,10 +60,7 @@ class DeviceOperator:
             b = next(w for w in APPLY_BLOCKS if w >= c)
             if b != c:
                 piece = torch.cat([piece, torch.zeros((self.n, b - c), dtype=piece.dtype, device=piece.device)], dim=1)
-            need = int(_native.load().sd_affinity_apply_workspace_bytes(self.n, b))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-            out.append(ops.affinity_apply(self.K, scale, piece, zero_diag, ws=self._ws)[:, :c])
+            out.append(ops.affinity_apply(self.K, scale, piece, zero_diag, ws=self.ws)[:, :c])
         return out[0] if len(out) == 1 else torch.cat(out, dim=1)
 
 

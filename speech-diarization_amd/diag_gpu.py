@@ -24,51 +24,35 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-_NO_CPU = "the device whitening route takes its rows as a GPU tensor; there is no CPU fallback"
+from . import ops
+from .device_rows import DeviceRoute, operator_for
+
 EIG_FLOOR = 1e-6          # [REF diar_diag.py:191]
 NORM_EPS = 1e-9           # [REF diar_diag.py:193, 381]
 
 
-def _rows4(X: torch.Tensor) -> torch.Tensor:
-    """X f32 [n, d] as a view whose row stride is a multiple of 4 and whose base is 16-byte aligned (a padded copy when it is not)."""
+def _f32(X: torch.Tensor) -> torch.Tensor:
+    """X as f32 with contiguous rows; `ops.rows4` does the rest (a padded copy where the stride or the alignment demands one)."""
     X = X.float()
-    n, d = X.shape
-    if X.stride(1) == 1 and X.stride(0) % 4 == 0 and X.stride(0) >= d and X.data_ptr() % 16 == 0:
-        return X
-    pad = -d % 4
-    return torch.nn.functional.pad(X, (0, pad))[:, :d] if pad else X.clone(memory_format=torch.contiguous_format)
+    return X if X.stride(1) == 1 else X.contiguous()
 
 
-class DeviceDiag:
+class DeviceDiag(DeviceRoute):
     """The three entries of include/sd_hip_diag.h over rows that live on the GPU; the workspace is kept between calls."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(_NO_CPU)
-        self._ws = None
+    route = "whitening"
 
     def stats(self, X: torch.Tensor):
-        from . import _native, ops
-        need = int(_native.load().sd_whiten_stats_workspace_bytes(X.shape[0], X.shape[1]))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
-        return ops.whiten_stats(_rows4(X), ws=self._ws)
+        return ops.whiten_stats(_f32(X), ws=self.ws)
 
     def apply(self, X: torch.Tensor, mean: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
-        from . import ops
-        return ops.whiten_apply(_rows4(X), mean, W, NORM_EPS)
+        return ops.whiten_apply(_f32(X), mean, W, NORM_EPS)
 
     def centroids(self, X: torch.Tensor, labels: torch.Tensor, k: int):
-        from . import ops
-        return ops.label_centroids(_rows4(X), labels.to(torch.int32).contiguous(), k, NORM_EPS)
+        return ops.label_centroids(_f32(X), labels.to(torch.int32).contiguous(), k, NORM_EPS)
 
 
 def _operator(X, operator, what: str):
-    if operator is None:
-        if not isinstance(X, torch.Tensor) or X.device.type != "cuda":
-            raise RuntimeError(_NO_CPU)
-        operator = DeviceDiag(X.device)
+    operator = operator_for(X, operator, DeviceDiag)
     X = torch.as_tensor(X)
     if X.dim() != 2 or X.shape[1] == 0:
         raise ValueError(f"{what}: rows must be a matrix [N, D >= 1], got {tuple(X.shape)}")

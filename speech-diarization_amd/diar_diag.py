@@ -348,11 +348,9 @@ def _resegment_host(embs, n, pi, pj, whiten, asnorm, cluster, cos_thr, use_vbx, 
 def _resegment_device(embs, n, pi, pj, whiten, asnorm, cluster, cos_thr, use_vbx, alpha, device, operator):
     import torch
     from . import ahc_gpu, diag_gpu, hdbscan_gpu, ops
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("resegment(device=...) is the GPU route; there is no CPU fallback (device=None is the host route)")
-    X = embs if isinstance(embs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(embs, dtype=np.float32))
-    X = X.to(dev, dtype=torch.float32)
+    from .device_rows import upload_rows
+    X = upload_rows(embs, "resegment(device=...) is the GPU route; there is no CPU fallback (device=None is the host route)", device)
+    dev = X.device
     if not bool(torch.isfinite(X).all()):
         raise ValueError("embeddings must be finite")
     if whiten:

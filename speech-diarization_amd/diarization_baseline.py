@@ -218,10 +218,9 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 
 def _device_rows(X: np.ndarray, use_gpu: bool, clustering: str):
     """The rows on the device, for the clustering routes that stay there."""
-    import torch
-    if not use_gpu or not torch.cuda.is_available():
-        raise RuntimeError(f"clustering={clustering!r} runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
-    return torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+    from .device_rows import upload_rows
+    return upload_rows(X, f"clustering={clustering!r} runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback",
+                       "cuda" if use_gpu else None)
 
 
 def _spectral_gpu_affinity(X: np.ndarray, use_gpu: bool):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import ops
 from .features import HOP, FbankPlan
 from .synth import EcapaConfig, config_from_state_dict
 
@@ -268,6 +269,14 @@ class EcapaWeights:
                 L.split_scale_inv = float(2.0 ** -s)
 
 
+def forward_entries(precision: str) -> tuple[str, str]:
+    """(forward, forward with relative lengths): the entries an engine of `precision` calls.  "f32s" / "f32ns" are a property of the
+    packed weights (sd_ecapa_weights.split16) on the f32 schedule, so they share the f32 entries."""
+    if precision == "f16":
+        return "sd_ecapa_forward_f16", "sd_ecapa_forward_lens_f16"
+    return "sd_ecapa_forward_f32", "sd_ecapa_forward_lens_f32"
+
+
 class EmbeddingEngine:
     """fbank + ECAPA-TDNN on one GPU. Thread-safe (one forward at a time per engine)."""
 
@@ -286,10 +295,9 @@ class EmbeddingEngine:
         self.dim = self.weights.cfg.lin_neurons
         self.min_samples = min_samples(self.weights.cfg)
         self.precision = precision
-        # "f32s" = f32-split16x3: the f32 schedule (f32 activations) whose wide layers run three f16 MFMA products per value
-        # pair at f32-level accuracy; a property of the packed weights (sd_ecapa_weights.split16), same entry point
-        self._forward = self._lib.sd_ecapa_forward_f16 if precision == "f16" else self._lib.sd_ecapa_forward_f32
-        self._forward_lens = self._lib.sd_ecapa_forward_lens_f16 if precision == "f16" else self._lib.sd_ecapa_forward_lens_f32
+        # "f32s" = f32-split16x3: the f32 schedule (f32 activations) whose wide layers run three f16 MFMA products per value pair at
+        # f32-level accuracy
+        self._forward, self._forward_lens = forward_entries(precision)
         self._ws = None
         self._ws_frozen = False
 
@@ -306,7 +314,7 @@ class EmbeddingEngine:
 
     def _packed_workspace(self, B: int, M: int, n_max: int):
         n_mels = self.weights.cfg.input_size
-        return self._grow((M * n_mels * 4, max(int(self._lib.sd_fbank_packed_workspace_bytes(self.plan.handle, B, M, n_max)), 256),
+        return self._grow((M * n_mels * 4, max(self.plan.packed_workspace_bytes(B, M, n_max), 256),
                            int(self._lib.sd_ecapa_packed_workspace_bytes(C.byref(self.weights.struct), B, M))))
 
     def _grow(self, need):
@@ -356,8 +364,7 @@ class EmbeddingEngine:
         if n < self.min_samples:
             raise ValueError(f"segment of {n} samples is too short: ECAPA's reflect padding needs at least "
                              f"{min_frames(self.weights.cfg)} frames ({self.min_samples} samples)")
-        with self._lock, torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with self._lock:
             mb = min(self.max_batch, B)
             feats, fb_ws, ec_ws = self._workspace(mb, n)
             T = FbankPlan.num_frames(n)
@@ -365,17 +372,13 @@ class EmbeddingEngine:
             for lo in range(0, B, mb):
                 nb = min(mb, B - lo)
                 x = wav[lo:lo + nb]
-                if rel_lens is not None:
-                    rl = rel_lens[lo:lo + nb].data_ptr()
-                    N.check(self._lib.sd_fbank_lens_f32(self.plan.handle, x.data_ptr(), nb, n, rl, feats.data_ptr(), self.weights.cfg.input_size,
-                                                        fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_lens_f32")
-                    N.check(self._forward_lens(W, feats.data_ptr(), nb, T, rl, out[lo:lo + nb].data_ptr(),
-                                               ec_ws.data_ptr(), ec_ws.numel(), stream), f"sd_ecapa_forward_lens_{self.precision}")
-                    continue
-                N.check(self._lib.sd_fbank_f32(self.plan.handle, x.data_ptr(), nb, n, 1, feats.data_ptr(), self.weights.cfg.input_size,
-                                               fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_f32")
-                N.check(self._forward(W, feats.data_ptr(), nb, T, out[lo:lo + nb].data_ptr(),
-                                      ec_ws.data_ptr(), ec_ws.numel(), stream), f"sd_ecapa_forward_{self.precision}")
+                rl = None if rel_lens is None else rel_lens[lo:lo + nb]
+                self.plan.rows(x, feats, fb_ws, rl)
+                y = out[lo:lo + nb].data_ptr()
+                if rl is not None:
+                    ops.launch(self._forward_lens, x, W, feats.data_ptr(), nb, T, rl.data_ptr(), y, ec_ws.data_ptr(), ec_ws.numel())
+                else:
+                    ops.launch(self._forward, x, W, feats.data_ptr(), nb, T, y, ec_ws.data_ptr(), ec_ws.numel())
         return out
 
     def embed_windows(self, signal: torch.Tensor, starts: torch.Tensor, n: int) -> torch.Tensor:
@@ -399,19 +402,15 @@ class EmbeddingEngine:
                              f"{min_frames(self.weights.cfg)} frames ({self.min_samples} samples)")
         if signal.numel() < 1:
             raise ValueError("empty signal")
-        with self._lock, torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with self._lock:
             mb = min(self.max_batch, B)
             feats, fb_ws, ec_ws = self._workspace(mb, n)
             T = FbankPlan.num_frames(n)
             W = C.byref(self.weights.struct)
             for lo in range(0, B, mb):
                 nb = min(mb, B - lo)
-                N.check(self._lib.sd_fbank_windows_f32(self.plan.handle, signal.data_ptr(), signal.numel(), starts[lo:lo + nb].data_ptr(),
-                                                       nb, n, 1, feats.data_ptr(), self.weights.cfg.input_size,
-                                                       fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_windows_f32")
-                N.check(self._forward(W, feats.data_ptr(), nb, T, out[lo:lo + nb].data_ptr(),
-                                      ec_ws.data_ptr(), ec_ws.numel(), stream), f"sd_ecapa_forward_{self.precision}")
+                self.plan.windows(signal, starts[lo:lo + nb], n, feats, fb_ws)
+                ops.launch(self._forward, signal, W, feats.data_ptr(), nb, T, out[lo:lo + nb].data_ptr(), ec_ws.data_ptr(), ec_ws.numel())
         return out
 
     def embed_spans(self, signal: torch.Tensor, starts, lengths, frame_budget: int | None = None) -> torch.Tensor:
@@ -446,19 +445,15 @@ class EmbeddingEngine:
         st_d = tab[:B]
         ln_d = tab[B:2 * B].to(torch.int32)
         fs_d = tab[2 * B:].to(torch.int32)
-        n_mels = self.weights.cfg.input_size
         W = C.byref(self.weights.struct)
-        with self._lock, torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with self._lock:
             for (lo, hi), o, f0 in zip(batches, offs, fs_at[:-1]):
                 nb, M, n_max = hi - lo, int(o[-1]), int(ln[lo:hi].max())
                 feats, fb_ws, ec_ws = self._packed_workspace(nb, M, n_max)
                 fs = fs_d[int(f0):int(f0) + nb + 1]
-                N.check(self._lib.sd_fbank_packed_f32(self.plan.handle, signal.data_ptr(), signal.numel(), st_d[lo:hi].data_ptr(),
-                                                      ln_d[lo:hi].data_ptr(), fs.data_ptr(), nb, M, n_max, feats.data_ptr(), n_mels,
-                                                      fb_ws.data_ptr(), fb_ws.numel(), stream), "sd_fbank_packed_f32")
-                N.check(self._lib.sd_ecapa_forward_packed_f32(W, feats.data_ptr(), fs.data_ptr(), nb, M, out[lo:hi].data_ptr(),
-                                                              ec_ws.data_ptr(), ec_ws.numel(), stream), "sd_ecapa_forward_packed_f32")
+                self.plan.packed(signal, st_d[lo:hi], ln_d[lo:hi], fs, M, n_max, feats, fb_ws)
+                ops.launch("sd_ecapa_forward_packed_f32", signal, W, feats.data_ptr(), fs.data_ptr(), nb, M, out[lo:hi].data_ptr(), ec_ws.data_ptr(),
+                           ec_ws.numel())
         return out
 
     def features(self, wav: torch.Tensor) -> torch.Tensor:
@@ -472,7 +467,6 @@ def fbank_windows_device(signal: torch.Tensor, starts: torch.Tensor, n: int, pla
     """HIP fbank of the windows signal[starts[b] : starts[b] + n] of one device-resident recording -> [B, T, n_mels]."""
     if signal.dim() != 1 or signal.device.type != "cuda":
         raise RuntimeError("fbank_windows_device needs a 1-d GPU tensor; there is no CPU fallback")
-    lib = N.load()
     signal = signal.contiguous().float()
     starts = starts.to(signal.device, dtype=torch.int64).contiguous()
     B = int(starts.numel())
@@ -480,11 +474,8 @@ def fbank_windows_device(signal: torch.Tensor, starts: torch.Tensor, n: int, pla
     out = torch.empty((B, T, plan.n_mels), dtype=torch.float32, device=signal.device)
     if B == 0:
         return out
-    with torch.cuda.device(signal.device):
-        ws = torch.empty((max(plan.workspace_bytes(B, n), 256),), dtype=torch.uint8, device=signal.device)
-        stream = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
-        N.check(lib.sd_fbank_windows_f32(plan.handle, signal.data_ptr(), signal.numel(), starts.data_ptr(), B, int(n), int(bool(mean_norm)),
-                                         out.data_ptr(), plan.n_mels, ws.data_ptr(), ws.numel(), stream), "sd_fbank_windows_f32")
+    ws = torch.empty((max(plan.workspace_bytes(B, n), 256),), dtype=torch.uint8, device=signal.device)
+    plan.windows(signal, starts, n, out, ws, mean_norm)
     return out
 
 
@@ -493,7 +484,6 @@ def fbank_packed_device(signal: torch.Tensor, starts, lengths, plan: FbankPlan) 
     -> [M, n_mels], span s at rows frame_start[s] .. frame_start[s + 1] (`span_frame_offsets`)."""
     if signal.dim() != 1 or signal.device.type != "cuda":
         raise RuntimeError("fbank_packed_device needs a 1-d GPU tensor; there is no CPU fallback")
-    lib = N.load()
     signal = signal.contiguous().float()
     st, ln = check_spans(starts, lengths, int(signal.numel()), 1, 1)
     fs = span_frame_offsets(ln)
@@ -501,15 +491,12 @@ def fbank_packed_device(signal: torch.Tensor, starts, lengths, plan: FbankPlan) 
     out = torch.empty((M, plan.n_mels), dtype=torch.float32, device=signal.device)
     if B == 0:
         return out
-    with torch.cuda.device(signal.device):
-        st_d = torch.from_numpy(st).to(signal.device)
-        ln_d = torch.from_numpy(ln.astype(np.int32)).to(signal.device)
-        fs_d = torch.from_numpy(fs).to(signal.device)
-        n_max = int(ln.max())
-        ws = torch.empty((max(int(lib.sd_fbank_packed_workspace_bytes(plan.handle, B, M, n_max)), 256),), dtype=torch.uint8, device=signal.device)
-        stream = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
-        N.check(lib.sd_fbank_packed_f32(plan.handle, signal.data_ptr(), signal.numel(), st_d.data_ptr(), ln_d.data_ptr(), fs_d.data_ptr(), B, M,
-                                        n_max, out.data_ptr(), plan.n_mels, ws.data_ptr(), ws.numel(), stream), "sd_fbank_packed_f32")
+    st_d = torch.from_numpy(st).to(signal.device)
+    ln_d = torch.from_numpy(ln.astype(np.int32)).to(signal.device)
+    fs_d = torch.from_numpy(fs).to(signal.device)
+    n_max = int(ln.max())
+    ws = torch.empty((max(plan.packed_workspace_bytes(B, M, n_max), 256),), dtype=torch.uint8, device=signal.device)
+    plan.packed(signal, st_d, ln_d, fs_d, M, n_max, out, ws)
     return out
 
 
@@ -519,16 +506,12 @@ def fbank_device(wav: torch.Tensor, plan: FbankPlan, mean_norm: bool = True) -> 
         raise AssertionError("wav must be [B, n]")
     if wav.device.type != "cuda":
         raise RuntimeError("fbank_device needs a GPU tensor; there is no CPU fallback")
-    lib = N.load()
     wav = wav.contiguous().float()
     B, n = wav.shape
     T = plan.frames(n)
     out = torch.empty((B, T, plan.n_mels), dtype=torch.float32, device=wav.device)
     if B == 0:
         return out
-    with torch.cuda.device(wav.device):
-        ws = torch.empty((max(plan.workspace_bytes(B, n), 256),), dtype=torch.uint8, device=wav.device)
-        stream = C.c_void_p(torch.cuda.current_stream(wav.device).cuda_stream)
-        N.check(lib.sd_fbank_f32(plan.handle, wav.data_ptr(), B, n, int(bool(mean_norm)), out.data_ptr(), plan.n_mels,
-                                 ws.data_ptr(), ws.numel(), stream), "sd_fbank_f32")
+    ws = torch.empty((max(plan.workspace_bytes(B, n), 256),), dtype=torch.uint8, device=wav.device)
+    plan.rows(wav, out, ws, mean_norm=mean_norm)
     return out

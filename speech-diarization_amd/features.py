@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import ops
 
 N_FFT = 400
 HOP = 160
@@ -104,7 +105,8 @@ FRONT_ENDS = {
 
 
 class FbankPlan:
-    """Owns an `sd_fbank_plan` (device-side DFT basis + sparse mel table)."""
+    """Owns an `sd_fbank_plan` (device-side DFT basis + sparse mel table) and the calls of the three fbank entries on it: `rows`,
+    `windows`, `packed`.  Each writes `out` (f32, n_mels columns) and takes `ws`, a uint8 tensor of the matching `*workspace_bytes`."""
 
     def __init__(self, kind: str = "speechbrain", n_mels: int = 80, sr: int = 16000):
         if kind not in FRONT_ENDS:
@@ -145,6 +147,29 @@ class FbankPlan:
 
     def workspace_bytes(self, B: int, n: int) -> int:
         return int(self._lib.sd_fbank_workspace_bytes(self._h, B, n))
+
+    def packed_workspace_bytes(self, B: int, M: int, n_max: int) -> int:
+        return int(self._lib.sd_fbank_packed_workspace_bytes(self._h, B, M, n_max))
+
+    def rows(self, wav: torch.Tensor, out: torch.Tensor, ws: torch.Tensor, rel_lens: torch.Tensor | None = None, mean_norm: bool = True) -> None:
+        """Uniform rows wav f32 [B, n] -> out [B, T, n_mels]; with `rel_lens` (f32 [B], speechbrain's relative lengths) the mean counts
+        each row's leading frames only (`sd_fbank_lens_f32`, always mean-normalised)."""
+        B, n = wav.shape
+        if rel_lens is not None:
+            ops.launch("sd_fbank_lens_f32", wav, self._h, wav.data_ptr(), B, n, rel_lens.data_ptr(), out.data_ptr(), self.n_mels, ws.data_ptr(), ws.numel())
+        else:
+            ops.launch("sd_fbank_f32", wav, self._h, wav.data_ptr(), B, n, int(bool(mean_norm)), out.data_ptr(), self.n_mels, ws.data_ptr(), ws.numel())
+
+    def windows(self, signal: torch.Tensor, starts: torch.Tensor, n: int, out: torch.Tensor, ws: torch.Tensor, mean_norm: bool = True) -> None:
+        """The windows signal[starts[b] : starts[b] + n] (starts int64 [B]) of one resident signal -> out [B, T, n_mels]."""
+        ops.launch("sd_fbank_windows_f32", signal, self._h, signal.data_ptr(), signal.numel(), starts.data_ptr(), starts.numel(), int(n),
+                   int(bool(mean_norm)), out.data_ptr(), self.n_mels, ws.data_ptr(), ws.numel())
+
+    def packed(self, signal: torch.Tensor, starts: torch.Tensor, lengths: torch.Tensor, frame_start: torch.Tensor, M: int, n_max: int,
+               out: torch.Tensor, ws: torch.Tensor) -> None:
+        """The packed spans signal[starts[s] : starts[s] + lengths[s]] (int64 / int32 / int32 [B], [B], [B + 1]) -> out [M, n_mels]."""
+        ops.launch("sd_fbank_packed_f32", signal, self._h, signal.data_ptr(), signal.numel(), starts.data_ptr(), lengths.data_ptr(),
+                   frame_start.data_ptr(), starts.numel(), M, n_max, out.data_ptr(), self.n_mels, ws.data_ptr(), ws.numel())
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

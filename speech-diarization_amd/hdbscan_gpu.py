@@ -48,8 +48,10 @@ import math
 import numpy as np
 import torch
 
+from . import ops
+from .device_rows import DeviceRoute, operator_for, upload_rows
+
 SKLEARN_WRITTEN_AGAINST = "1.7.2"
-_NO_CPU = "the device HDBSCAN route takes its rows as a GPU tensor; there is no CPU fallback"
 
 
 def _sklearn_tree():
@@ -64,36 +66,15 @@ def _sklearn_tree():
     return MST_edge_dtype, _process_mst, tree_to_labels
 
 
-class DeviceRows:
+class DeviceRows(DeviceRoute):
     """The two kernels of include/sd_hip_hdbscan.h over unit rows that live on the GPU; the workspace is kept between calls."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(_NO_CPU)
-        self._ws = None
-
-    def _workspace(self, need: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def normalise(self, X: torch.Tensor) -> torch.Tensor:
-        """Unit rows, a zero row left zero (sklearn `normalize`), f32 [N, D padded to a multiple of 4 with zero columns]."""
-        from . import ops
-        Xn = ops.l2norm_rows(X, sklearn_zero_guard=True)
-        pad = -Xn.shape[1] % 4
-        return torch.nn.functional.pad(Xn, (0, pad)) if pad else Xn
+    route = "HDBSCAN"
 
     def core(self, rows: torch.Tensor, k: int) -> torch.Tensor:
-        from . import _native, ops
-        need = int(_native.load().sd_hdb_core_workspace_bytes(rows.shape[0], rows.shape[1], int(k)))
-        return ops.hdb_core(rows, k, ws=self._workspace(need))
+        return ops.hdb_core(rows, k, ws=self.ws)
 
     def outgoing(self, rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor):
-        from . import _native, ops
-        need = int(_native.load().sd_hdb_outgoing_workspace_bytes(rows.shape[0], rows.shape[1]))
-        return ops.hdb_outgoing(rows, core, comp, ws=self._workspace(need))
+        return ops.hdb_outgoing(rows, core, comp, ws=self.ws)
 
 
 def _by_lowest_member(comp: np.ndarray) -> np.ndarray:
@@ -167,10 +148,7 @@ def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, a
     info = {"rounds": 0, "gram_rows": 0, "components_per_round": [], "mst_weight": 0.0}
     if metric not in ("euclidean", "cosine"):
         raise ValueError(f"hdbscan_rows clusters rows under metric 'euclidean' or 'cosine'; metric={metric!r} has no rows to work on")
-    if operator is None:
-        if not isinstance(X, torch.Tensor) or X.device.type != "cuda":
-            raise RuntimeError(_NO_CPU)
-        operator = DeviceRows(X.device)
+    operator = operator_for(X, operator, DeviceRows)
     X = torch.as_tensor(X)
     if X.dim() != 2:
         raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
@@ -234,7 +212,5 @@ class HdbscanGpuClusterer:
     def fit_predict(self, X) -> np.ndarray:
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
         if self.operator is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
-            X = X.cuda()
+            X = upload_rows(X, "HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
         return hdbscan_rows(X, self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric, operator=self.operator)

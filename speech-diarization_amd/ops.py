@@ -17,8 +17,40 @@ from . import _native as N
 _ACT = {None: N.SD_ACT_NONE, "none": N.SD_ACT_NONE, "relu": N.SD_ACT_RELU, "tanh": N.SD_ACT_TANH, "sigmoid": N.SD_ACT_SIGMOID}
 
 
+_ENTRIES = frozenset(name for key, table in vars(N).items() if key.endswith("PROTOTYPES") for name in table)
+
+
+def _current_stream(index: int) -> int:
+    """The raw handle of the current torch stream of GPU `index`: the one place the binding asks torch for it."""
+    return torch.cuda.current_stream(index).cuda_stream
+
+
 def _stream(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return C.c_void_p(_current_stream(t.device.index))
+
+
+def launch(name: str, on: torch.Tensor, *args) -> None:
+    """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
+    of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
+    if name not in _ENTRIES:
+        raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
+    with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
+        N.check(getattr(N.load(), name)(*args, _stream(on)), name)
+
+
+class Workspace:
+    """A grow-only uint8 buffer on one device, for the entries that take a workspace: kept between calls, it is allocated again only
+    when a call needs more than it holds."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.buf = None
+
+    def take(self, need: int) -> torch.Tensor:
+        """At least max(need, 16) bytes; the same storage as the last call unless `need` exceeds it."""
+        if self.buf is None or self.buf.numel() < need:
+            self.buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+        return self.buf
 
 
 def _need_cuda(*ts: torch.Tensor) -> None:
@@ -79,7 +111,6 @@ def conv1d_cl(x: torch.Tensor, w_packed: torch.Tensor, T: int, *, cin: int, dil:
     f16, output `out_dtype`).  `colstat` (f32, `colstat_floats(M, cout)` elements) receives the epilogue's
     per-tile column sums for `colstat_finish`."""
     _need_cuda(x, w_packed, bias, scale, shift, out, tee, tee_add, colstat)
-    lib = N.load()
     cout, taps, cin_pad = w_packed.shape
     M = x.shape[0]
     half = w_packed.dtype == torch.float16
@@ -93,9 +124,7 @@ def conv1d_cl(x: torch.Tensor, w_packed: torch.Tensor, T: int, *, cin: int, dil:
     a = _conv_args(x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype), w_packed.data_ptr(), _dt(w_packed.dtype), out.data_ptr(), out.stride(0), o_col0,
                    _dt(out.dtype), M, T, cin, cin_pad, cout, taps, dil, bias=bias, bias_per_seg=bias_per_seg, act=act, act2=act2, scale=scale,
                    shift=shift, tee=tee, tee_lo=tee_lo, tee_hi=tee_hi, tee_add=tee_add, ta_col0=ta_col0, colstat=colstat)
-    with torch.cuda.device(x.device):
-        fn, name = (lib.sd_conv1d_cl_f16, "sd_conv1d_cl_f16") if half else (lib.sd_conv1d_cl_f32, "sd_conv1d_cl_f32")
-        N.check(fn(C.byref(a), _stream(x)), name)
+    launch("sd_conv1d_cl_f16" if half else "sd_conv1d_cl_f32", x, C.byref(a))
     return out
 
 
@@ -120,8 +149,7 @@ def conv1d_cl_packed(x: torch.Tensor, w_packed: torch.Tensor, frame_start, *, ci
     a = _conv_args(x.data_ptr(), x.stride(0), a_col0, _dt(x.dtype), w_packed.data_ptr(), _dt(w_packed.dtype), out.data_ptr(), out.stride(0), o_col0,
                    _dt(out.dtype), M, M, cin, cin_pad, cout, taps, dil, bias=bias, bias_per_seg=bias_per_seg, act=act, act2=act2, scale=scale,
                    shift=shift, tee=tee, tee_lo=tee_lo, tee_hi=tee_hi, tee_add=tee_add, ta_col0=ta_col0)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_conv1d_cl_packed_f32(C.byref(a), fs.data_ptr(), B, _stream(x)), "sd_conv1d_cl_packed_f32")
+    launch("sd_conv1d_cl_packed_f32", x, C.byref(a), fs.data_ptr(), B)
     return out
 
 
@@ -131,9 +159,8 @@ def seg_mean_std_packed(x: torch.Tensor, frame_start, want_std: bool = True, eps
     fs, B = _span_table(frame_start, x.device)
     C_ = x.shape[1]
     out = torch.empty((B, (2 if want_std else 1) * C_), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_seg_mean_std_packed_dt(x.data_ptr(), _dt(x.dtype), x.stride(0), 0, fs.data_ptr(), B, x.shape[0], C_,
-                                                   int(bool(want_std)), C.c_float(eps), out.data_ptr(), _stream(x)), "sd_seg_mean_std_packed_dt")
+    launch("sd_seg_mean_std_packed_dt", x, x.data_ptr(), _dt(x.dtype), x.stride(0), 0, fs.data_ptr(), B, x.shape[0], C_, int(bool(want_std)),
+           C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -142,10 +169,8 @@ def se_scale_residual_packed(x: torch.Tensor, gate: torch.Tensor, res: torch.Ten
     _need_cuda(x, gate, res)
     fs, B = _span_table(frame_start, x.device)
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_se_scale_residual_packed_dt(x.data_ptr(), x.stride(0), gate.data_ptr(), res.data_ptr(), res.stride(0), 0,
-                                                        y.data_ptr(), y.stride(0), 0, fs.data_ptr(), B, x.shape[0], x.shape[1], _dt(x.dtype),
-                                                        _stream(x)), "sd_se_scale_residual_packed_dt")
+    launch("sd_se_scale_residual_packed_dt", x, x.data_ptr(), x.stride(0), gate.data_ptr(), res.data_ptr(), res.stride(0), 0, y.data_ptr(),
+           y.stride(0), 0, fs.data_ptr(), B, x.shape[0], x.shape[1], _dt(x.dtype))
     return y
 
 
@@ -155,9 +180,8 @@ def asp_pool_packed(logit: torch.Tensor, h: torch.Tensor, frame_start, eps: floa
     fs, B = _span_table(frame_start, h.device)
     C_ = h.shape[1]
     out = torch.empty((B, 2 * C_), dtype=torch.float32, device=h.device)
-    with torch.cuda.device(h.device):
-        N.check(N.load().sd_asp_pool_packed_dt(logit.data_ptr(), logit.stride(0), h.data_ptr(), _dt(h.dtype), h.stride(0), fs.data_ptr(), B,
-                                               h.shape[0], C_, C.c_float(eps), out.data_ptr(), _stream(h)), "sd_asp_pool_packed_dt")
+    launch("sd_asp_pool_packed_dt", h, logit.data_ptr(), logit.stride(0), h.data_ptr(), _dt(h.dtype), h.stride(0), fs.data_ptr(), B, h.shape[0], C_,
+           C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -178,9 +202,7 @@ def seg_gemm(x: torch.Tensor, w_packed: torch.Tensor, *, cin: int, bias=None, ac
         scratch = torch.empty(need // 4, dtype=torch.float32, device=x.device)
     a = _conv_args(x.data_ptr(), x.stride(0), 0, N.SD_DT_F32, w_packed.data_ptr(), N.SD_DT_F32, out.data_ptr(), out.stride(0), 0, N.SD_DT_F32,
                    M, 1, cin, cin_pad, cout, 1, 1, bias=bias, act=act, act2=act2, scale=scale, shift=shift)
-    with torch.cuda.device(x.device):
-        N.check(lib.sd_seg_gemm_f32(C.byref(a), scratch.data_ptr() if scratch is not None else None,
-                                    scratch.numel() * 4 if scratch is not None else 0, _stream(x)), "sd_seg_gemm_f32")
+    launch("sd_seg_gemm_f32", x, C.byref(a), _ptr(scratch), scratch.numel() * 4 if scratch is not None else 0)
     return out
 
 
@@ -194,8 +216,7 @@ def split16_pack(x: torch.Tensor, a_col0: int = 0, cin: int | None = None, mul: 
     cin = x.shape[1] - a_col0 if cin is None else cin
     cp = (cin + 31) // 32 * 32
     out = torch.empty((M, 2 * cp), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_split16_pack_f32(x.data_ptr(), x.stride(0), a_col0, M, cin, C.c_float(mul), out.data_ptr(), cp, _stream(x)), "sd_split16_pack_f32")
+    launch("sd_split16_pack_f32", x, x.data_ptr(), x.stride(0), a_col0, M, cin, C.c_float(mul), out.data_ptr(), cp)
     return out
 
 
@@ -218,7 +239,6 @@ def conv1d_cl_split16(x: torch.Tensor, w_split: torch.Tensor, w_shift: int, T: i
     `narrow=True`: the 128x128 kernel that splits the f32 activations while staging them (no pack pass; tee_add, per-segment bias and
     act2 allowed, no colstat), the 2^-s passed as `w_scale_inv`; `out_split`: its y as SD_DT_SPLIT16 rows instead of f32."""
     _need_cuda(x, w_split, bias, scale, shift, out, tee, tee_add, colstat)
-    lib = N.load()
     cout, taps, chunks, _ = w_split.shape
     cp = chunks * 32
     M = x.shape[0]
@@ -251,8 +271,7 @@ def conv1d_cl_split16(x: torch.Tensor, w_split: torch.Tensor, w_shift: int, T: i
                    ta_col0=ta_col0, colstat=colstat)
     if narrow:
         a.w_scale_inv = 1.0 / f
-    with torch.cuda.device(x.device):
-        N.check(lib.sd_conv1d_cl_split16(C.byref(a), _stream(x)), "sd_conv1d_cl_split16")
+    launch("sd_conv1d_cl_split16", x, C.byref(a))
     del keep
     return out
 
@@ -268,7 +287,6 @@ def res2net_chain(r: torch.Tensor, T: int, layers: list[dict]) -> torch.Tensor:
     _need_cuda(r)
     if r.dtype != torch.float16 or r.stride(1) != 1:
         raise TypeError("r must be f16 with contiguous channels")
-    lib = N.load()
     arr = (N.sd_layer * len(layers))()
     for L, d in zip(arr, layers):
         _need_cuda(d["w"], d.get("bias"), d.get("scale"), d.get("shift"))
@@ -276,10 +294,9 @@ def res2net_chain(r: torch.Tensor, T: int, layers: list[dict]) -> torch.Tensor:
         L.w, L.bias, L.scale, L.shift = d["w"].data_ptr(), _ptr(d.get("bias")), _ptr(d.get("scale")), _ptr(d.get("shift"))
         L.cin, L.cin_pad, L.cout, L.taps, L.dil, L.w_dtype = d.get("cin", cin_pad), cin_pad, cout, taps, d["dil"], _dt(d["w"].dtype)
     B = r.shape[0] // T
-    with torch.cuda.device(r.device):
-        ws_bytes = max(256, int(lib.sd_res2net_chain_workspace_bytes(len(layers))))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=r.device)
-        N.check(lib.sd_res2net_chain_f16(r.data_ptr(), r.stride(0), B, T, arr, len(layers), ws.data_ptr(), ws_bytes, _stream(r)), "sd_res2net_chain_f16")
+    ws_bytes = max(256, int(N.load().sd_res2net_chain_workspace_bytes(len(layers))))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=r.device)
+    launch("sd_res2net_chain_f16", r, r.data_ptr(), r.stride(0), B, T, arr, len(layers), ws.data_ptr(), ws_bytes)
     return r
 
 
@@ -294,9 +311,8 @@ def colstat_finish(colstat: torch.Tensor, y: torch.Tensor, B: int, T: int, *, pi
     _need_cuda(colstat, y, pivot)
     C_ = y.shape[1] - y_col0 if C_ is None else C_
     out = torch.empty((B, (2 if want_std else 1) * C_), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(y.device):
-        N.check(N.load().sd_colstat_finish_dt(colstat.data_ptr(), _ptr(pivot), y.data_ptr(), _dt(y.dtype), y.stride(0), y_col0, B, T, C_,
-                                              int(want_std), C.c_float(eps), out.data_ptr(), _stream(y)), "sd_colstat_finish_dt")
+    launch("sd_colstat_finish_dt", y, colstat.data_ptr(), _ptr(pivot), y.data_ptr(), _dt(y.dtype), y.stride(0), y_col0, B, T, C_, int(want_std),
+           C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -304,8 +320,7 @@ def seg_mean(x: torch.Tensor, B: int, T: int, col0: int = 0, C_: int | None = No
     _need_cuda(x)
     C_ = x.shape[1] - col0 if C_ is None else C_
     out = torch.empty((B, C_), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_seg_mean_f32(x.data_ptr(), x.stride(0), col0, B, T, C_, out.data_ptr(), _stream(x)), "sd_seg_mean_f32")
+    launch("sd_seg_mean_f32", x, x.data_ptr(), x.stride(0), col0, B, T, C_, out.data_ptr())
     return out
 
 
@@ -313,9 +328,7 @@ def seg_mean_std(x: torch.Tensor, B: int, T: int, eps: float = 1e-12) -> torch.T
     _need_cuda(x)
     C_ = x.shape[1]
     out = torch.empty((B, 2 * C_), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_seg_mean_std_f32(x.data_ptr(), x.stride(0), 0, B, T, C_, C.c_float(eps), out.data_ptr(), _stream(x)),
-                "sd_seg_mean_std_f32")
+    launch("sd_seg_mean_std_f32", x, x.data_ptr(), x.stride(0), 0, B, T, C_, C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -323,9 +336,8 @@ def se_scale_residual(x: torch.Tensor, gate: torch.Tensor, res: torch.Tensor, B:
     _need_cuda(x, gate, res)
     C_ = x.shape[1]
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_se_scale_residual_f32(x.data_ptr(), x.stride(0), gate.data_ptr(), res.data_ptr(), res.stride(0), 0,
-                                                  y.data_ptr(), y.stride(0), 0, B, T, C_, _stream(x)), "sd_se_scale_residual_f32")
+    launch("sd_se_scale_residual_f32", x, x.data_ptr(), x.stride(0), gate.data_ptr(), res.data_ptr(), res.stride(0), 0, y.data_ptr(), y.stride(0), 0,
+           B, T, C_)
     return y
 
 
@@ -333,9 +345,7 @@ def asp_pool(logit: torch.Tensor, h: torch.Tensor, B: int, T: int, eps: float = 
     _need_cuda(logit, h)
     C_ = h.shape[1]
     out = torch.empty((B, 2 * C_), dtype=torch.float32, device=h.device)
-    with torch.cuda.device(h.device):
-        N.check(N.load().sd_asp_pool_f32(logit.data_ptr(), logit.stride(0), h.data_ptr(), h.stride(0), B, T, C_, C.c_float(eps),
-                                         out.data_ptr(), _stream(h)), "sd_asp_pool_f32")
+    launch("sd_asp_pool_f32", h, logit.data_ptr(), logit.stride(0), h.data_ptr(), h.stride(0), B, T, C_, C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -344,7 +354,6 @@ def asp_attend_pool(a1: torch.Tensor, wc_packed: torch.Tensor, h: torch.Tensor, 
     AttentiveStatisticsPooling): a1 [B*T, att], wc_packed from `pack_weight`, h [B*T, C] -> f32 [B, 2C].
     Raises for geometries the fused kernel does not cover (see `asp_attend_pool_supported`)."""
     _need_cuda(a1, h, wc_packed)
-    lib = N.load()
     C_, att = h.shape[1], a1.shape[1]
     if a1.dtype != h.dtype or wc_packed.dtype != h.dtype:
         raise ValueError("a1, wc and h must share a dtype")
@@ -355,9 +364,8 @@ def asp_attend_pool(a1: torch.Tensor, wc_packed: torch.Tensor, h: torch.Tensor, 
         dt = N.SD_DT_SPLIT16
     a1 = a1.contiguous()
     out = torch.empty((B, 2 * C_), dtype=torch.float32, device=h.device)
-    with torch.cuda.device(h.device):
-        N.check(lib.sd_asp_attend_pool_dt(a1.data_ptr(), wc_packed.data_ptr(), h.data_ptr(), dt, h.stride(0), B, T, C_, att,
-                                          C.c_float(eps), out.data_ptr(), _stream(h)), "sd_asp_attend_pool_dt")
+    launch("sd_asp_attend_pool_dt", h, a1.data_ptr(), wc_packed.data_ptr(), h.data_ptr(), dt, h.stride(0), B, T, C_, att, C.c_float(eps),
+           out.data_ptr())
     return out
 
 
@@ -370,9 +378,7 @@ def l2norm_rows(x: torch.Tensor, eps_add: float = 0.0, sklearn_zero_guard: bool 
     x = x.contiguous().float()
     n, d = x.shape
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_l2norm_rows_f32(x.data_ptr(), d, n, d, C.c_float(eps_add), int(sklearn_zero_guard), out.data_ptr(), d,
-                                            _stream(x)), "sd_l2norm_rows_f32")
+    launch("sd_l2norm_rows_f32", x, x.data_ptr(), d, n, d, C.c_float(eps_add), int(sklearn_zero_guard), out.data_ptr(), d)
     return out
 
 
@@ -390,12 +396,11 @@ def cosine_affinity(x: torch.Tensor, out: torch.Tensor | None = None, rows: tupl
         out = torch.empty((hi - lo, n), dtype=torch.float32, device=x.device)
     if n == 0 or hi == lo:
         return out
-    with torch.cuda.device(x.device):
-        size_fn, fn, name = ((lib.sd_cosine_split16_workspace_bytes, lib.sd_cosine_affinity_rows_split16, "sd_cosine_affinity_rows_split16")
-                             if split16 else (lib.sd_cosine_workspace_bytes, lib.sd_cosine_affinity_rows_f32, "sd_cosine_affinity_rows_f32"))
-        ws_bytes = int(size_fn(n, d))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
-        N.check(fn(x.data_ptr(), n, d, lo, hi, out.data_ptr(), out.stride(0), ws.data_ptr(), ws_bytes, _stream(x)), name)
+    size_fn, name = ((lib.sd_cosine_split16_workspace_bytes, "sd_cosine_affinity_rows_split16") if split16 else
+                     (lib.sd_cosine_workspace_bytes, "sd_cosine_affinity_rows_f32"))
+    ws_bytes = int(size_fn(n, d))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
+    launch(name, x, x.data_ptr(), n, d, lo, hi, out.data_ptr(), out.stride(0), ws.data_ptr(), ws_bytes)
     return out
 
 
@@ -404,9 +409,7 @@ def adjacent_cosine(x: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     x = x.contiguous().float()
     n, d = x.shape
     out = torch.empty((max(n - 1, 0),), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_adjacent_cosine_f32(x.data_ptr(), d, n, d, C.c_float(eps), out.data_ptr(), _stream(x)),
-                "sd_adjacent_cosine_f32")
+    launch("sd_adjacent_cosine_f32", x, x.data_ptr(), d, n, d, C.c_float(eps), out.data_ptr())
     return out
 
 
@@ -417,9 +420,7 @@ def sim_argmax(w: torch.Tensor, c: torch.Tensor):
     k = c.shape[0]
     best = torch.empty((n,), dtype=torch.int32, device=w.device)
     score = torch.empty((n,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        N.check(N.load().sd_sim_argmax_f32(w.data_ptr(), d, n, d, c.data_ptr(), d, k, best.data_ptr(), score.data_ptr(), _stream(w)),
-                "sd_sim_argmax_f32")
+    launch("sd_sim_argmax_f32", w, w.data_ptr(), d, n, d, c.data_ptr(), d, k, best.data_ptr(), score.data_ptr())
     return best, score
 
 
@@ -432,8 +433,7 @@ def topk_mean_std(x: torch.Tensor, k: int) -> torch.Tensor:
         x = x.contiguous()
     rows, n = x.shape
     out = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        N.check(N.load().sd_topk_mean_std_f32(x.data_ptr(), x.stride(0), rows, n, int(k), out.data_ptr(), _stream(x)), "sd_topk_mean_std_f32")
+    launch("sd_topk_mean_std_f32", x, x.data_ptr(), x.stride(0), rows, n, int(k), out.data_ptr())
     return out
 
 
@@ -442,7 +442,6 @@ def asnorm_scores(query: torch.Tensor, centers: torch.Tensor, cohort: torch.Tens
     products on the f32 matrix cores (the operator behind the 1x1 convs, T = 1), top-k cohort statistics per row,
     z-normalisation against the query's and the centre's cohort scores, averaged.  f32 [nq, nr].  Precondition: finite inputs."""
     _need_cuda(query, centers, cohort)
-    lib = N.load()
     qn, rn, cn = (l2norm_rows(t, eps_add=1e-9) for t in (query, centers, cohort))
     d = qn.shape[1]
 
@@ -455,9 +454,8 @@ def asnorm_scores(query: torch.Tensor, centers: torch.Tensor, cohort: torch.Tens
     qstat = topk_mean_std(product(qn, cn), k)
     rstat = topk_mean_std(product(rn, cn), k)
     out = torch.empty_like(raw)
-    with torch.cuda.device(raw.device):
-        N.check(lib.sd_asnorm_combine_f32(raw.data_ptr(), raw.stride(0), raw.shape[0], raw.shape[1], qstat.data_ptr(), rstat.data_ptr(),
-                                          out.data_ptr(), out.stride(0), _stream(raw)), "sd_asnorm_combine_f32")
+    launch("sd_asnorm_combine_f32", raw, raw.data_ptr(), raw.stride(0), raw.shape[0], raw.shape[1], qstat.data_ptr(), rstat.data_ptr(),
+           out.data_ptr(), out.stride(0))
     return out
 
 
@@ -475,12 +473,10 @@ def viterbi(scores: torch.Tensor, alpha: float = 0.995) -> torch.Tensor:
     eps = 1e-8
     log_move = float(np.float32(np.log((1 - alpha) / (K - 1) + eps))) if K > 1 else 0.0
     log_stay = float(np.float32(np.log(alpha + eps)))
-    lib = N.load()
-    with torch.cuda.device(scores.device):
-        nbytes = int(lib.sd_viterbi_workspace_bytes(T, K))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device)
-        N.check(lib.sd_viterbi_f32(scores.data_ptr(), scores.stride(0), T, K, C.c_float(log_stay), C.c_float(log_move), ws.data_ptr(), nbytes,
-                                   path.data_ptr(), _stream(scores)), "sd_viterbi_f32")
+    nbytes = int(N.load().sd_viterbi_workspace_bytes(T, K))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device)
+    launch("sd_viterbi_f32", scores, scores.data_ptr(), scores.stride(0), T, K, C.c_float(log_stay), C.c_float(log_move), ws.data_ptr(), nbytes,
+           path.data_ptr())
     return path
 
 
@@ -496,32 +492,38 @@ def affinity_degree(K: torch.Tensor, zero_diag: bool = False) -> torch.Tensor:
     deg = torch.empty((n,), dtype=torch.float32, device=K.device)
     if n == 0:
         return deg
-    with torch.cuda.device(K.device):
-        N.check(N.load().sd_affinity_degree_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), deg.data_ptr(), _stream(K)),
-                "sd_affinity_degree_f32")
+    launch("sd_affinity_degree_f32", K, K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), deg.data_ptr())
     return deg
 
 
-def _rows_ld(rows: torch.Tensor, what: str) -> tuple[int, int, int]:
-    """(n, d, row stride) of a non-empty f32 matrix with contiguous rows; `what` names it in the message."""
+def rows4(rows: torch.Tensor, what: str = "rows") -> tuple[torch.Tensor, int, int, int]:
+    """The rows contract of the entries that read rows (AHC, HDBSCAN, whitening, centres), stated once: a non-empty f32 matrix with
+    contiguous rows (`what` names it in the message), a row stride that is a multiple of 4 and a 16-byte aligned base
+    -> (view, n, d, row stride).  The view is `rows` itself, read in place (a column slice of a wider matrix is fine); a padded copy
+    only when the stride or the alignment demands one."""
     if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] == 0 or rows.shape[1] == 0 or rows.stride(1) != 1 and rows.shape[1] > 1:
         raise ValueError(f"{what} must be a non-empty f32 matrix with contiguous rows, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
     n, d = rows.shape
-    return n, d, max(rows.stride(0), d) if n > 1 else (d + 3) // 4 * 4      # one row: its stride is never used, any legal value will do
+    ld = max(rows.stride(0), d) if n > 1 else (d + 3) // 4 * 4              # one row: its stride is never used, any legal value will do
+    if ld % 4 or rows.data_ptr() % 16:
+        rows = torch.nn.functional.pad(rows, (0, -d % 4))[:, :d] if d % 4 else rows.clone(memory_format=torch.contiguous_format)
+        ld = rows.stride(0)
+    return rows, n, d, ld
 
 
-def _workspace(ws: torch.Tensor | None, need: int, device) -> torch.Tensor:
-    """`ws` if it holds `need` bytes, a fresh uint8 workspace otherwise."""
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+def _workspace(ws, need: int, device) -> torch.Tensor:
+    """A workspace of at least `need` bytes: the tensor `ws` if it holds them; otherwise taken from `ws` when it is a `Workspace`, and
+    from a fresh one when it is not."""
+    if not isinstance(ws, torch.Tensor) or ws.numel() * ws.element_size() < need:
+        ws = (ws if isinstance(ws, Workspace) else Workspace(device)).take(need)
     return ws
 
 
 def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_diag: bool = False,
-                   ws: torch.Tensor | None = None) -> torch.Tensor:
+                   ws: Workspace | torch.Tensor | None = None) -> torch.Tensor:
     """Y = diag(scale) max(K, 0) diag(scale) V on the GPU, the diagonal of K taken as 0 when `zero_diag`.  K f32 [N, N] read in
-    place, scale f32 [N], V f32 [N, b] with b in {8, 16, 24, 32} -> f32 [N, b].  `ws`: a uint8 workspace of at least
-    sd_affinity_apply_workspace_bytes(N, b) to reuse across calls (allocated when None)."""
+    place, scale f32 [N], V f32 [N, b] with b in {8, 16, 24, 32} -> f32 [N, b].  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_affinity_apply_workspace_bytes(N, b), to reuse across calls (allocated when None)."""
     _need_cuda(K, scale, V)
     if K.dtype != torch.float32 or K.dim() != 2 or K.shape[0] != K.shape[1] or K.stride(1) != 1 and K.shape[0] > 1:
         raise ValueError(f"affinity must be a square f32 matrix with contiguous rows, got {tuple(K.shape)} {K.dtype} strides {K.stride()}")
@@ -534,33 +536,29 @@ def affinity_apply(K: torch.Tensor, scale: torch.Tensor, V: torch.Tensor, zero_d
     Y = torch.empty((n, b), dtype=torch.float32, device=K.device)
     if n == 0:
         return Y
-    lib = N.load()
-    with torch.cuda.device(K.device):
-        ws = _workspace(ws, int(lib.sd_affinity_apply_workspace_bytes(n, b)), K.device)
-        N.check(lib.sd_affinity_apply_f32(K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), scale.data_ptr(), V.data_ptr(), b, b,
-                                          Y.data_ptr(), b, ws.data_ptr(), ws.numel() * ws.element_size(), _stream(K)), "sd_affinity_apply_f32")
+    ws = _workspace(ws, int(N.load().sd_affinity_apply_workspace_bytes(n, b)), K.device)
+    launch("sd_affinity_apply_f32", K, K.data_ptr(), n, max(K.stride(0), n), int(zero_diag), scale.data_ptr(), V.data_ptr(), b, b, Y.data_ptr(), b,
+           ws.data_ptr(), ws.numel() * ws.element_size())
     return Y
 
 
 # ----------------------------------------------------------------------------- average-linkage clustering (include/sd_hip_ahc.h)
 
-def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: torch.Tensor | None = None):
+def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: Workspace | torch.Tensor | None = None):
     """The nearest other cluster of every cluster under score(i, j) = <sums[i], sums[j]> (inv_count[i] inv_count[j]):
-    sums f32 [n, d] read in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine),
-    inv_count f32 [n] -> (nn int32 [n], best f32 [n]); exactly symmetric scores, lowest index among equal ones, bitwise reproducible.
-    `ws`: a uint8 workspace of at least sd_ahc_nearest_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    sums f32 [n, d] under the rows contract (`rows4`), inv_count f32 [n] -> (nn int32 [n], best f32 [n]); exactly symmetric scores,
+    lowest index among equal ones, bitwise reproducible.  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_ahc_nearest_workspace_bytes(n, d), to reuse across calls (allocated when None)."""
     _need_cuda(sums, inv_count)
-    n, d, ld = _rows_ld(sums, "cluster sums")
+    sums, n, d, ld = rows4(sums, "cluster sums")
     inv_count = inv_count.contiguous().float()
     if inv_count.shape != (n,):
         raise ValueError(f"inv_count {tuple(inv_count.shape)} does not match the {n} cluster sums")
     nn = torch.empty((n,), dtype=torch.int32, device=sums.device)
     best = torch.empty((n,), dtype=torch.float32, device=sums.device)
-    lib = N.load()
-    with torch.cuda.device(sums.device):
-        ws = _workspace(ws, int(lib.sd_ahc_nearest_workspace_bytes(n, d)), sums.device)
-        N.check(lib.sd_ahc_nearest_f32(sums.data_ptr(), ld, n, d, inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(),
-                                       ws.numel() * ws.element_size(), _stream(sums)), "sd_ahc_nearest_f32")
+    ws = _workspace(ws, int(N.load().sd_ahc_nearest_workspace_bytes(n, d)), sums.device)
+    launch("sd_ahc_nearest_f32", sums, sums.data_ptr(), ld, n, d, inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
     return nn, best
 
 
@@ -569,73 +567,68 @@ def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, 
     and its count into row i and refreshes inv_count[i] -> (target int32 [n]: i for the upper row of a pair, the row itself otherwise;
     n_merged int32 [1], still on the device)."""
     _need_cuda(sums, count, inv_count, nn, best)
-    n, d, ld = _rows_ld(sums, "cluster sums")
+    view, n, d, ld = rows4(sums, "cluster sums")
+    if view is not sums:
+        raise ValueError(f"cluster sums are merged in place: a row stride that is a multiple of 4 and a 16-byte aligned base, got strides {sums.stride()}")
     for name, t, dt in (("count", count, torch.float32), ("inv_count", inv_count, torch.float32), ("nn", nn, torch.int32),
                         ("best", best, torch.float32)):
         if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
     target = torch.empty((n,), dtype=torch.int32, device=sums.device)
     n_merged = torch.empty((1,), dtype=torch.int32, device=sums.device)
-    with torch.cuda.device(sums.device):
-        N.check(N.load().sd_ahc_merge_f32(sums.data_ptr(), ld, n, d, count.data_ptr(), inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
-                                          C.c_float(cos_thr), target.data_ptr(), n_merged.data_ptr(), _stream(sums)), "sd_ahc_merge_f32")
+    launch("sd_ahc_merge_f32", sums, sums.data_ptr(), ld, n, d, count.data_ptr(), inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
+           C.c_float(cos_thr), target.data_ptr(), n_merged.data_ptr())
     return target, n_merged
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)
 
-def hdb_core(rows: torch.Tensor, k: int, ws: torch.Tensor | None = None) -> torch.Tensor:
-    """core[i] = the k-th largest <rows[i], rows[j]> over j != i, duplicates counted (1 <= k <= min(16, n - 1)): rows f32 [n, d] read
-    in place (row stride a multiple of 4, 16-byte aligned; a column slice of a wider matrix is fine) -> f32 [n].  The products are
-    those of `hdb_outgoing`, bit for bit.  `ws`: a uint8 workspace of at least sd_hdb_core_workspace_bytes(n, d, k) to reuse across
-    calls (allocated when None)."""
+def hdb_core(rows: torch.Tensor, k: int, ws: Workspace | torch.Tensor | None = None) -> torch.Tensor:
+    """core[i] = the k-th largest <rows[i], rows[j]> over j != i, duplicates counted (1 <= k <= min(16, n - 1)): rows f32 [n, d] under
+    the rows contract (`rows4`) -> f32 [n].  The products are those of `hdb_outgoing`, bit for bit.  `ws`: a `Workspace`, or a uint8
+    tensor of at least sd_hdb_core_workspace_bytes(n, d, k), to reuse across calls (allocated when None)."""
     _need_cuda(rows)
-    n, d, ld = _rows_ld(rows, "rows")
+    rows, n, d, ld = rows4(rows)
     core = torch.empty((n,), dtype=torch.float32, device=rows.device)
-    lib = N.load()
-    with torch.cuda.device(rows.device):
-        ws = _workspace(ws, int(lib.sd_hdb_core_workspace_bytes(n, d, int(k))), rows.device)
-        N.check(lib.sd_hdb_core_f32(rows.data_ptr(), ld, n, d, int(k), core.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
-                                    _stream(rows)), "sd_hdb_core_f32")
+    ws = _workspace(ws, int(N.load().sd_hdb_core_workspace_bytes(n, d, int(k))), rows.device)
+    launch("sd_hdb_core_f32", rows, rows.data_ptr(), ld, n, d, int(k), core.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
     return core
 
 
-def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws: torch.Tensor | None = None):
+def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws: Workspace | torch.Tensor | None = None):
     """The heaviest edge that leaves the component of every row under w(i, j) = min(core[i], core[j], <rows[i], rows[j]>):
     rows f32 [n, d] as for `hdb_core`, core f32 [n] (+inf allowed), comp int32 [n] -> (nn int32 [n], best f32 [n]); nn = -1 and
     best = -inf for a row whose component is everything.  Exactly symmetric w, lowest index among equal ones, bitwise reproducible.
-    `ws`: a uint8 workspace of at least sd_hdb_outgoing_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    `ws`: a `Workspace`, or a uint8 tensor of at least sd_hdb_outgoing_workspace_bytes(n, d), to reuse across calls (allocated when
+    None)."""
     _need_cuda(rows, core, comp)
-    n, d, ld = _rows_ld(rows, "rows")
+    rows, n, d, ld = rows4(rows)
     for name, t, dt in (("core", core, torch.float32), ("comp", comp, torch.int32)):
         if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
     nn = torch.empty((n,), dtype=torch.int32, device=rows.device)
     best = torch.empty((n,), dtype=torch.float32, device=rows.device)
-    lib = N.load()
-    with torch.cuda.device(rows.device):
-        ws = _workspace(ws, int(lib.sd_hdb_outgoing_workspace_bytes(n, d)), rows.device)
-        N.check(lib.sd_hdb_outgoing_f32(rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(),
-                                        ws.data_ptr(), ws.numel() * ws.element_size(), _stream(rows)), "sd_hdb_outgoing_f32")
+    ws = _workspace(ws, int(N.load().sd_hdb_outgoing_workspace_bytes(n, d)), rows.device)
+    launch("sd_hdb_outgoing_f32", rows, rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
     return nn, best
 
 
 # ----------------------------------------------------------------------------- f64 whitening and cluster centres (include/sd_hip_diag.h)
 
-def whiten_stats(rows: torch.Tensor, ws: torch.Tensor | None = None):
+def whiten_stats(rows: torch.Tensor, ws: Workspace | torch.Tensor | None = None):
     """Column means and the centred Gram matrix of rows f32 [n >= 2, d <= 256] in f64 on the f64 matrix cores, two passes as np.cov:
     -> (mean f64 [d], gram f64 [d, d] = sum_i (x_i - mean)^T (x_i - mean), exactly symmetric; divide by n - 1 for the covariance).
-    Rows are read in place (row stride a multiple of 4, 16-byte aligned); bitwise reproducible, the summation order depends on (n, d)
-    alone.  `ws`: a uint8 workspace of at least sd_whiten_stats_workspace_bytes(n, d) to reuse across calls (allocated when None)."""
+    Rows under the rows contract (`rows4`); bitwise reproducible, the summation order depends on (n, d) alone.  `ws`: a `Workspace`,
+    or a uint8 tensor of at least sd_whiten_stats_workspace_bytes(n, d), to reuse across calls (allocated when None)."""
     _need_cuda(rows)
-    n, d, ld = _rows_ld(rows, "rows")
+    rows, n, d, ld = rows4(rows)
     mean = torch.empty((d,), dtype=torch.float64, device=rows.device)
     gram = torch.empty((d, d), dtype=torch.float64, device=rows.device)
-    lib = N.load()
-    with torch.cuda.device(rows.device):
-        ws = _workspace(ws, int(lib.sd_whiten_stats_workspace_bytes(n, d)), rows.device)
-        N.check(lib.sd_whiten_stats_f64(rows.data_ptr(), ld, n, d, mean.data_ptr(), gram.data_ptr(), d, ws.data_ptr(),
-                                        ws.numel() * ws.element_size(), _stream(rows)), "sd_whiten_stats_f64")
+    ws = _workspace(ws, int(N.load().sd_whiten_stats_workspace_bytes(n, d)), rows.device)
+    launch("sd_whiten_stats_f64", rows, rows.data_ptr(), ld, n, d, mean.data_ptr(), gram.data_ptr(), d,
+           ws.data_ptr(), ws.numel() * ws.element_size())
     return mean, gram
 
 
@@ -643,15 +636,13 @@ def whiten_apply(rows: torch.Tensor, mean: torch.Tensor, W: torch.Tensor, eps_ad
     """out[i] = f32(v / (||v|| + eps_add)), v = (rows[i] - mean) @ W in f64 on the f64 matrix cores: rows f32 [n, d <= 256] read in
     place, mean f64 [d], W f64 [d, d] (symmetry is not assumed) -> f32 [n, d]; one rounding to f32."""
     _need_cuda(rows, mean, W)
-    n, d, ld = _rows_ld(rows, "rows")
+    rows, n, d, ld = rows4(rows)
     mean = mean.contiguous()
     W = W.contiguous()
     if mean.dtype != torch.float64 or mean.shape != (d,) or W.dtype != torch.float64 or W.shape != (d, d):
         raise ValueError(f"mean {tuple(mean.shape)} {mean.dtype} / W {tuple(W.shape)} {W.dtype} must be f64 [{d}] and f64 [{d}, {d}]")
     out = torch.empty((n, d), dtype=torch.float32, device=rows.device)
-    with torch.cuda.device(rows.device):
-        N.check(N.load().sd_whiten_apply_f64(rows.data_ptr(), ld, n, d, mean.data_ptr(), W.data_ptr(), d, C.c_double(eps_add), out.data_ptr(), d,
-                                             _stream(rows)), "sd_whiten_apply_f64")
+    launch("sd_whiten_apply_f64", rows, rows.data_ptr(), ld, n, d, mean.data_ptr(), W.data_ptr(), d, C.c_double(eps_add), out.data_ptr(), d)
     return out
 
 
@@ -660,15 +651,13 @@ def label_centroids(rows: torch.Tensor, labels: torch.Tensor, k: int, eps_add: f
     (centres f32 [k, d], count int32 [k]).  The mean is accumulated in f64 in ascending row order and divided by (its norm + eps_add);
     a label outside [0, k) is skipped, a label without rows gives a zero row and count 0."""
     _need_cuda(rows, labels)
-    n, d, ld = _rows_ld(rows, "rows")
+    rows, n, d, ld = rows4(rows)
     if labels.dtype != torch.int32 or labels.shape != (n,) or not labels.is_contiguous():
         raise ValueError(f"labels must be a contiguous int32 vector of {n} entries, got {tuple(labels.shape)} {labels.dtype}")
     k = int(k)
     out = torch.empty((max(k, 0), d), dtype=torch.float32, device=rows.device)
     count = torch.empty((max(k, 0),), dtype=torch.int32, device=rows.device)
-    with torch.cuda.device(rows.device):
-        N.check(N.load().sd_label_centroids_f32(rows.data_ptr(), ld, n, d, labels.data_ptr(), k, C.c_double(eps_add), out.data_ptr(), d,
-                                                count.data_ptr(), _stream(rows)), "sd_label_centroids_f32")
+    launch("sd_label_centroids_f32", rows, rows.data_ptr(), ld, n, d, labels.data_ptr(), k, C.c_double(eps_add), out.data_ptr(), d, count.data_ptr())
     return out, count
 
 

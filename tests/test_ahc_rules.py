@@ -2,8 +2,6 @@
 formula, the refusals an entry makes before it launches anything, and the driver itself run on the CPU through an injected numpy
 operator against `cluster.ahc_cosine`."""
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import ahc_ref as A  # noqa: E402
+from abi_rules import ARG, UNSUP, WS, check_header_and_table, check_versions, refused  # noqa: E402
 
 from speech_diarization_amd import _native as N  # noqa: E402
 from speech_diarization_amd import ahc_gpu, cluster  # noqa: E402
@@ -20,30 +19,13 @@ from speech_diarization_amd import ahc_gpu, cluster  # noqa: E402
 
 # ------------------------------------------------------------------ ABI
 
-def _header_names():
-    header = open(N.LIB_PATH.parent.parent / "include" / "sd_hip_ahc.h").read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    return set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-
-
 def test_header_and_binding_table_name_the_same_exported_entries():
-    names = _header_names()
-    assert names == set(N.AHC_PROTOTYPES), names ^ set(N.AHC_PROTOTYPES)
-    assert not names & set(N.PROTOTYPES) and not names & set(N.SPECTRAL_PROTOTYPES)
-    lib = N.load()
-    for name, (res, args) in N.AHC_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    out = subprocess.run(["nm", "-D", "--defined-only", str(N.LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sd_[a-z0-9_]+)$", out, flags=re.M))
-    assert names <= exported, names - exported
+    check_header_and_table("sd_hip_ahc.h", N.AHC_PROTOTYPES, (N.PROTOTYPES, N.SPECTRAL_PROTOTYPES))
 
 
 def test_versions():
-    lib = N.load()
-    assert lib.sd_ahc_abi_version() == 1 == N.SD_AHC_ABI_VERSION
-    assert lib.sd_abi_version() == 11                      # the main ABI and the spectral one are untouched by the new header
-    assert lib.sd_spectral_abi_version() == 1
+    assert N.SD_AHC_ABI_VERSION == 1
+    check_versions(sd_ahc_abi_version=1, sd_abi_version=11, sd_spectral_abi_version=1)      # the main ABI and the spectral one are untouched
 
 
 def test_workspace_formula():
@@ -75,12 +57,6 @@ def test_refusals_happen_before_anything_is_launched():
     """Every case returns its own argument / support / workspace code with a message.  A launch on this pointer soup would have
     returned SD_ERR_HIP (no device here) or faulted (on a GPU)."""
     lib = N.load()
-    ARG, UNSUP, WS = -1, -2, -3
-
-    def refused(status, code, needle):
-        assert status == code, (status, N.last_error())
-        assert needle in N.last_error(), N.last_error()
-
     for name in ("sums", "inv_count", "nn", "best", "ws"):
         refused(_nearest(lib, **{name: None}), ARG, "null pointer")
     for name in ("sums", "count", "inv_count", "nn", "best", "target", "n_merged"):

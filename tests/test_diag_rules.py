@@ -4,12 +4,12 @@ tests/test_gpu_diag.py that asserts it ran), the binding table, the versions, th
 before it launches anything."""
 import os
 import re
-import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import launch_log as L  # noqa: E402
+from abi_rules import ARG, UNSUP, WS, check_header_and_table, check_versions, refused  # noqa: E402
 
 from speech_diarization_amd import _native as N  # noqa: E402
 
@@ -72,32 +72,19 @@ def test_no_floating_point_atomics_and_the_f64_matrix_core():
 
 # ------------------------------------------------------------------ ABI
 
-def _header_names():
-    header = open(N.PKG_DIR.parent / "include" / "sd_hip_diag.h").read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    return set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-
-
 def test_header_and_binding_table_name_the_same_exported_entries():
-    names = _header_names()
-    assert names == set(N.DIAG_PROTOTYPES) == {"sd_diag_abi_version", "sd_whiten_stats_workspace_bytes", "sd_whiten_stats_f64",
-                                               "sd_whiten_apply_f64", "sd_label_centroids_f32"}
-    assert not names & (set(N.PROTOTYPES) | set(N.SPECTRAL_PROTOTYPES) | set(N.AHC_PROTOTYPES) | set(N.HDBSCAN_PROTOTYPES) | set(N.TRACE_PROTOTYPES))
-    lib = N.load()
-    for name, (res, args) in N.DIAG_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    out = subprocess.run(["nm", "-D", "--defined-only", str(N.LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    assert names <= set(re.findall(r"\bT (sd_[a-z0-9_]+)$", out, flags=re.M))
+    names = check_header_and_table("sd_hip_diag.h", N.DIAG_PROTOTYPES,
+                                   (N.PROTOTYPES, N.SPECTRAL_PROTOTYPES, N.AHC_PROTOTYPES, N.HDBSCAN_PROTOTYPES, N.TRACE_PROTOTYPES))
+    assert names == {"sd_diag_abi_version", "sd_whiten_stats_workspace_bytes", "sd_whiten_stats_f64", "sd_whiten_apply_f64", "sd_label_centroids_f32"}
     main = open(N.PKG_DIR.parent / "include" / "sd_hip.h").read()
     assert not any(n in main for n in names)                         # nothing was added to the main header
 
 
 def test_versions_and_struct_sizes():
     lib = N.load()
-    assert lib.sd_diag_abi_version() == 1 == N.SD_DIAG_ABI_VERSION
-    assert lib.sd_trace_abi_version() == 3 and lib.sd_abi_version() == 11 and lib.sd_spectral_abi_version() == 1
-    assert lib.sd_ahc_abi_version() == 1 and lib.sd_hdbscan_abi_version() == 1
+    assert N.SD_DIAG_ABI_VERSION == 1
+    check_versions(sd_diag_abi_version=1, sd_trace_abi_version=3, sd_abi_version=11, sd_spectral_abi_version=1, sd_ahc_abi_version=1,
+                   sd_hdbscan_abi_version=1)
     assert [int(lib.sd_sizeof(i)) for i in range(5)] == [184, 88, 1672, 13944, 0]
 
 
@@ -136,12 +123,6 @@ def test_refusals_happen_before_anything_is_launched():
     """Every case returns its own argument / support / workspace code and sets sd_last_error.  A launch on this pointer soup would
     have returned SD_ERR_HIP (no device here) or faulted (on a GPU)."""
     lib = N.load()
-    ARG, UNSUP, WS = -1, -2, -3
-
-    def refused(status, code, needle):
-        assert status == code, (status, N.last_error())
-        assert needle in N.last_error(), N.last_error()
-
     for name in ("x", "mean", "gram", "ws"):
         refused(_stats(lib, **{name: None}), ARG, "null pointer")
     for name in ("x", "mean", "w", "out"):

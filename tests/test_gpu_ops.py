@@ -359,3 +359,32 @@ def test_viterbi_gpu_path_equals_the_reference_path(dev, golden_dir):
         sc[::7] = np.round(sc[::7])                    # exact ties between states: first maximum must win
         got = dd.viterbi_hmm(sc, alpha, device=dev)
         assert got.dtype == np.int32 and got.tolist() == dd.viterbi_hmm(sc, alpha).tolist(), (T, K, alpha)
+
+
+def test_a_reused_workspace_gives_the_bits_of_a_fresh_one_and_does_not_move(dev):
+    """The five entries that take a workspace, each with `ws=None` and with one shared `ops.Workspace`: the same kernels on the same
+    inputs, so the outputs are equal bit for bit.  [130, 8]: one row block past the first 128-row tile (the tile edge and the slot layout);
+    then [40, 8] in the same workspace, whose need is smaller: it is neither reallocated nor moved."""
+    from speech_diarization_amd import ops
+    g = torch.Generator().manual_seed(11)
+
+    def calls(n, ws):
+        g.manual_seed(n)
+        X = ops.l2norm_rows(torch.randn(n, 8, generator=g).to(dev))
+        ones = torch.ones(n, device=dev)
+        core = ops.hdb_core(X, 2, ws=ws)
+        comp = (torch.arange(n, device=dev) % 3).to(torch.int32)
+        K = ops.cosine_affinity(X)
+        V = torch.randn(n, 8, generator=g).to(dev)
+        return (*ops.ahc_nearest(X, ones, ws=ws), core, *ops.hdb_outgoing(X, core, comp, ws=ws), *ops.whiten_stats(X, ws=ws),
+                ops.affinity_apply(K, ones, V, ws=ws))
+
+    shared = ops.Workspace(dev)
+    fresh, reused = calls(130, None), calls(130, shared)
+    assert len(fresh) == 8 and all(torch.equal(a, b) for a, b in zip(fresh, reused))
+    at, size = shared.buf.data_ptr(), shared.buf.numel()
+    assert size >= 16
+    small_fresh, small_reused = calls(40, None), calls(40, shared)
+    assert all(torch.equal(a, b) for a, b in zip(small_fresh, small_reused))
+    assert shared.buf.data_ptr() == at and shared.buf.numel() == size
+    assert all(torch.equal(a, b) for a, b in zip(fresh, calls(130, shared)))            # and the larger calls again, after the smaller ones

@@ -11,7 +11,6 @@ module docstring of hdbscan_gpu.py).  (6, 3, False) differs under both metrics, 
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -21,6 +20,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import hdbscan_ref as H  # noqa: E402
+from abi_rules import ARG, UNSUP, WS, check_header_and_table, check_versions, refused  # noqa: E402
 
 from speech_diarization_amd import _native as N  # noqa: E402
 from speech_diarization_amd import cluster  # noqa: E402
@@ -35,31 +35,15 @@ def _route():
 
 # ------------------------------------------------------------------ ABI
 
-def _header_names():
-    header = open(N.LIB_PATH.parent.parent / "include" / "sd_hip_hdbscan.h").read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    return set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-
-
 @needs_lib
 def test_header_and_binding_table_name_the_same_exported_entries():
-    names = _header_names()
-    assert names == set(N.HDBSCAN_PROTOTYPES), names ^ set(N.HDBSCAN_PROTOTYPES)
-    assert not names & set(N.PROTOTYPES) and not names & set(N.SPECTRAL_PROTOTYPES) and not names & set(N.AHC_PROTOTYPES)
-    lib = N.load()
-    for name, (res, args) in N.HDBSCAN_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    out = subprocess.run(["nm", "-D", "--defined-only", str(N.LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sd_[a-z0-9_]+)$", out, flags=re.M))
-    assert names <= exported, names - exported
+    check_header_and_table("sd_hip_hdbscan.h", N.HDBSCAN_PROTOTYPES, (N.PROTOTYPES, N.SPECTRAL_PROTOTYPES, N.AHC_PROTOTYPES))
 
 
 @needs_lib
 def test_versions():
-    lib = N.load()
-    assert lib.sd_hdbscan_abi_version() == 1 == N.SD_HDBSCAN_ABI_VERSION
-    assert lib.sd_abi_version() == 11 and lib.sd_spectral_abi_version() == 1 and lib.sd_ahc_abi_version() == 1      # untouched
+    assert N.SD_HDBSCAN_ABI_VERSION == 1
+    check_versions(sd_hdbscan_abi_version=1, sd_abi_version=11, sd_spectral_abi_version=1, sd_ahc_abi_version=1)      # the others: untouched
 
 
 @needs_lib
@@ -121,12 +105,6 @@ def test_refusals_happen_before_anything_is_launched():
     """Every case returns its own argument / support / workspace code with a message.  A launch on this pointer soup would have
     returned SD_ERR_HIP (no device here) or faulted (on a GPU)."""
     lib = N.load()
-    ARG, UNSUP, WS = -1, -2, -3
-
-    def refused(status, code, needle):
-        assert status == code, (status, N.last_error())
-        assert needle in N.last_error(), N.last_error()
-
     for name in ("rows", "core", "ws"):
         refused(_core(lib, **{name: None}), ARG, "null pointer")
     for name in ("rows", "core", "comp", "nn", "best", "ws"):

@@ -3,8 +3,6 @@ workspace formula, the refusals an entry makes before it launches anything, and 
 operator against `np.linalg.eigvalsh`, `cluster.estimate_num_speakers` and `cluster.spectral`."""
 import ctypes as C
 import os
-import re
-import subprocess
 import sys
 import warnings
 
@@ -15,6 +13,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import spectral_ref as R  # noqa: E402
+from abi_rules import ARG, UNSUP, WS, check_header_and_table, check_versions, refused  # noqa: E402
 
 from speech_diarization_amd import _native as N  # noqa: E402
 from speech_diarization_amd import cluster, cluster_gpu  # noqa: E402
@@ -33,29 +32,13 @@ MIN_SPK, MAX_SPK = 1, 12
 
 # ------------------------------------------------------------------ ABI
 
-def _header_names():
-    header = open(N.LIB_PATH.parent.parent / "include" / "sd_hip_spectral.h").read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    return set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", header))
-
-
 def test_header_and_binding_table_name_the_same_exported_entries():
-    names = _header_names()
-    assert names == set(N.SPECTRAL_PROTOTYPES), names ^ set(N.SPECTRAL_PROTOTYPES)
-    assert not names & set(N.PROTOTYPES)
-    lib = N.load()
-    for name, (res, args) in N.SPECTRAL_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    out = subprocess.run(["nm", "-D", "--defined-only", str(N.LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sd_[a-z0-9_]+)$", out, flags=re.M))
-    assert names <= exported, names - exported
+    check_header_and_table("sd_hip_spectral.h", N.SPECTRAL_PROTOTYPES, (N.PROTOTYPES,))
 
 
 def test_versions():
-    lib = N.load()
-    assert lib.sd_spectral_abi_version() == 1 == N.SD_SPECTRAL_ABI_VERSION
-    assert lib.sd_abi_version() == 11                      # the main ABI is untouched by the new header
+    assert N.SD_SPECTRAL_ABI_VERSION == 1
+    check_versions(sd_spectral_abi_version=1, sd_abi_version=11)      # the main ABI is untouched by the new header
 
 
 def _splits(n):
@@ -88,12 +71,6 @@ def test_refusals_happen_before_anything_is_launched():
     """Every case returns its own argument / support / workspace code with a message.  A launch on this pointer soup would have
     returned SD_ERR_HIP (no device here) or faulted (on a GPU)."""
     lib = N.load()
-    ARG, UNSUP, WS = -1, -2, -3
-
-    def refused(status, code, needle):
-        assert status == code, (status, N.last_error())
-        assert needle in N.last_error(), N.last_error()
-
     refused(lib.sd_affinity_degree_f32(None, 10, 10, 0, 0x1000, None), ARG, "null pointer")
     refused(lib.sd_affinity_degree_f32(0x1000, 10, 10, 0, None, None), ARG, "null pointer")
     refused(lib.sd_affinity_degree_f32(0x1000, 0, 10, 0, 0x2000, None), ARG, "N=0")

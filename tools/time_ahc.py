@@ -90,7 +90,7 @@ def main():
         row = {"N": n, "planted_speakers": k, "first_nearest_ms": first_ms, "first_nearest_ms_min": first_lo, "first_nearest_ms_max": first_hi,
                "cosine_affinity_ms": aff_ms, "cosine_affinity_ms_min": aff_lo, "cosine_affinity_ms_max": aff_hi, "reps": reps,
                "first_nearest_over_affinity": first_ms / aff_ms, "first_nearest_TFLOPs": float(n) * n * X.shape[1] / (first_ms * 1e-3) / 1e12,
-               "workspace_MB": op._ws.numel() / 1e6}
+               "workspace_MB": op.ws.buf.numel() / 1e6}
         # the whole clustering
         total, near = [], []
         for it in range(6):                                           # the first one warms every shape up

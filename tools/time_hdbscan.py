@@ -103,7 +103,7 @@ def kernel_cost(n, dev):
     core1 = op.core(Xn, 1)
     row = {"N": n, "d": int(Xn.shape[1]),
            "outgoing_singletons": event_ms(lambda: op.outgoing(Xn, core1, singles), reps),
-           "ahc_nearest": event_ms(lambda: ops.ahc_nearest(Xn, ones, ws=op._ws), reps),
+           "ahc_nearest": event_ms(lambda: ops.ahc_nearest(Xn, ones, ws=op.ws), reps),
            "core_k1": event_ms(lambda: op.core(Xn, 1), reps), "core_k2": event_ms(lambda: op.core(Xn, 2), reps),
            "core_k16": event_ms(lambda: op.core(Xn, 16), max(2, reps // 4))}
     row["outgoing_over_ahc_nearest"] = row["outgoing_singletons"]["median_ms"] / row["ahc_nearest"]["median_ms"]
