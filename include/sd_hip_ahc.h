@@ -28,6 +28,8 @@
 extern "C" {
 #endif
 
+/* The version moves when an existing entry changes its signature or its meaning.  An additive entry (the grouped nearest below) does
+ * not move it: a caller that needs one looks the symbol up. */
 #define SD_AHC_ABI_VERSION 1
 
 int sd_ahc_abi_version(void);
@@ -75,6 +77,39 @@ int sd_ahc_nearest_f32(const float* sums, long ld, int n, int d, const float* in
  * SD_ERR_ARG: a null pointer, n <= 0, d <= 0, ld < d, sums not 16-byte aligned, ld % 4 != 0. */
 int sd_ahc_merge_f32(float* sums, long ld, int n, int d, float* count, float* inv_count, const int* nn, const float* best,
                      float cos_thr, int* target, int* n_merged, sd_stream_t stream);
+
+/* sd_ahc_nearest_f32 for many recordings at once: the rows of all recordings stand one after another and a cluster never looks
+ * outside its own recording.
+ *
+ *     best[i] = max over j != i with group[j] == group[i] of score(i, j),    nn[i] = the lowest such j, as an index into all n rows.
+ *     A row alone in its group: nn[i] = -1, best[i] = -inf.
+ *
+ *   group      device int32 [n]: the recording of every row, NON-DECREASING
+ *   max_group  the caller's upper bound on the rows of any one group, >= 1
+ *   bad        device int32 [1]: set to 0 first; non-zero afterwards when `group` decreases somewhere or a group has more than
+ *              max_group rows (group is monotone, so that is group[i] == group[i + max_group] for some i).  nn and best mean nothing
+ *              then: a broken promise is reported, never answered with silently wrong neighbours
+ *   sums, inv_count, nn, best, ws: as for sd_ahc_nearest_f32, with the workspace size below
+ *
+ * The score, the tile, the k order and the tie rule are those of sd_ahc_nearest_f32: the scores of a recording are bit for bit the
+ * ones it gets alone (its nn shifted by its first row), exactly symmetric, best[i] == best[nn[i]] bitwise for a reciprocal pair.  No
+ * floating-point atomics: results are bitwise equal run to run.
+ *
+ * The walk is a band.  Rows of one group lie at most max_group - 1 apart, so tile (I, J), I <= J, can hold a candidate only for
+ * J - I <= W = min(T - 1, ceil((max_group - 1) / 128)), T = ceil(n / 128).  T · (W + 1) workgroups are launched; one whose row block
+ * and column block share no group (group[last row of I] != group[first row of J]) loads nothing and writes empty slots.  A row block
+ * has 2 W + 2 slots in ascending column order: W + 1 for the tiles to its left and the lower half of its diagonal tile, W + 1 for
+ * the upper half of its diagonal tile and the tiles to its right; every slot is written exactly once, and a second kernel walks them
+ * with a strict `>` and checks the two promises about `group`.  Work and workspace are linear in n at a fixed max_group:
+ *
+ *     sd_ahc_nearest_grouped_workspace_bytes(n, d, max_group) = (2 W + 2) · 128 T · 8;
+ *                                                               0 for n <= 0, d <= 0, d > 1024 or max_group <= 0
+ *
+ * SD_ERR_ARG: a null pointer (group and bad included), n <= 0, d <= 0, ld < d, max_group <= 0, sums not 16-byte aligned, ld % 4 != 0,
+ * ws not 16-byte aligned.  SD_ERR_UNSUPPORTED: d > 1024, W + 1 > 65535.  SD_ERR_WORKSPACE: a workspace smaller than the formula. */
+size_t sd_ahc_nearest_grouped_workspace_bytes(int n, int d, int max_group);
+int sd_ahc_nearest_grouped_f32(const float* sums, long ld, int n, int d, const float* inv_count, const int* group, int max_group, int* nn,
+                               float* best, int* bad, void* ws, size_t ws_bytes, sd_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,8 @@ AHC_PROTOTYPES = {
     "sd_ahc_nearest_workspace_bytes": (_Z, [_I, _I]),
     "sd_ahc_nearest_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "sd_ahc_merge_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "sd_ahc_nearest_grouped_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sd_ahc_nearest_grouped_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
 }
 
 # include/sd_hip_hdbscan.h: the density-clustering entries, same shared object, a table and a version of their own

@@ -24,6 +24,12 @@ The operator is injectable (`operator=`): an object with `device`, `normalise(X)
 on the CPU against a numpy operator.  There is no implicit CPU route: without an operator a host tensor raises the product path's
 RuntimeError.
 
+Many recordings at once: `ahc_cosine_groups(X, sizes, cos_thr)` is the same loop over the rows of all recordings, with
+`nearest_grouped(sums, inv_count, group, max_group) -> (nn, best, bad)` (`ops.ahc_nearest_grouped`, `sd_ahc_nearest_grouped_f32`) in
+place of `nearest`: a cluster looks for its neighbour inside its own recording only, so one pass, one merge and one host
+synchronisation per round serve the whole folder, and every recording gets the labels `ahc_cosine_rows` gives it alone (DESIGN
+section 18).  Opt-in: `diarization_baseline.diarize_audios`, `Diarizer.diarize_many`.
+
 Two differences from the host route
 * the host clips 1 - K at 0 and symmetrises an f32 K; here there is no K: a score is an f32 dot product of f32 sums, and differs from
   the host's f64 mean of f32 cosines by f32 rounding, about 1e-7;
@@ -45,6 +51,9 @@ class DeviceSums(DeviceRoute):
 
     def nearest(self, sums: torch.Tensor, inv_count: torch.Tensor):
         return ops.ahc_nearest(sums, inv_count, ws=self.ws)
+
+    def nearest_grouped(self, sums: torch.Tensor, inv_count: torch.Tensor, group: torch.Tensor, max_group: int):
+        return ops.ahc_nearest_grouped(sums, inv_count, group, max_group, ws=self.ws)
 
     def merge(self, sums, count, inv_count, nn, best, cos_thr: float):
         return ops.ahc_merge(sums, count, inv_count, nn, best, cos_thr)
@@ -99,6 +108,93 @@ def ahc_cosine_rows(X, cos_thr: float = 0.70, *, operator=None, return_info: boo
     labels = cluster_of.cpu().numpy().astype(int)
     assert np.array_equal(labels, cluster.relabel_by_first_appearance(labels)), "cluster ids are not numbered by first appearance"
     info["clusters"] = n
+    return (labels, info) if return_info else labels
+
+
+TILE = 128          # the tile edge of the nearest kernels (GT_T of csrc/sd_gram_tile.h), for the count of `gram_tiles`
+
+
+def _band_tiles(group: torch.Tensor, max_group: int) -> torch.Tensor:
+    """The tiles one grouped nearest pass computes (a 0-dim tensor on the device of `group`): every diagonal tile, and tile (I, J),
+    0 < J - I <= W, whose row block and column block share a group: group[last row of I] == group[first row of J].  The first rows of
+    the blocks ascend, so for a row block these J are a run that starts at I + 1: one searchsorted finds its end."""
+    n = group.shape[0]
+    T = -(-n // TILE)
+    W = min(T - 1, -(-(max_group - 1) // TILE))
+    if W == 0:
+        return torch.tensor(T, device=group.device)
+    first = group[::TILE].contiguous()                                                  # [T]
+    last = group[TILE - 1::TILE][:T - 1].contiguous()                                   # [T - 1]: the last block has no block to its right
+    blocks = torch.arange(T - 1, device=group.device)
+    run = torch.searchsorted(first, last, right=True) - (blocks + 1)
+    return T + torch.minimum(run, (T - 1 - blocks).clamp(max=W)).clamp(min=0).sum()
+
+
+def ahc_cosine_groups(X, sizes, cos_thr: float = 0.70, *, operator=None, return_info: bool = False):
+    """`ahc_cosine_rows` for many recordings in one driver: X [N, D] holds the rows of all recordings one after another, `sizes` the
+    number of rows of each (0 and 1 are legal) -> a list with one label array per recording, each numbered by first appearance within
+    its recording and equal to `ahc_cosine_rows` on that recording's rows alone (the scores are the same bits: include/sd_hip_ahc.h).
+
+    A cluster never looks outside its recording, so one nearest pass (`operator.nearest_grouped`, `sd_ahc_nearest_grouped_f32`), one
+    merge and one host synchronisation per round serve all recordings: the rounds are the maximum over the recordings, not the sum.
+    `group`, the recording of every active cluster, is compacted with the sums and stays non-decreasing because compaction keeps
+    order; max(sizes) bounds a recording's clusters in every round, since clusters only merge.  The kernel's verdict on those two
+    promises (`bad`) comes back in the same host read as the number of merges; non-zero raises RuntimeError.
+
+    info = {"rounds": rounds that merged something, "clusters": per recording, "gram_tiles": the 128 x 128 tiles computed, summed over
+    every nearest pass}.  A non-finite row raises ValueError before anything is launched."""
+    sizes = [int(s) for s in sizes]
+    info = {"rounds": 0, "clusters": [min(s, 1) for s in sizes], "gram_tiles": 0}
+    operator = operator_for(X, operator, DeviceSums)
+    X = torch.as_tensor(X)
+    if X.dim() != 2:
+        raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
+    N = X.shape[0]
+    if min(sizes, default=0) < 0 or sum(sizes) != N:
+        raise ValueError(f"sizes {sizes} do not add up to the {N} rows")
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    max_group = max(sizes, default=0)
+    if max_group <= 1:                                                                  # nothing to merge anywhere
+        labels = [np.zeros(s, dtype=int) for s in sizes]
+        return (labels, info) if return_info else labels
+    if X.shape[1] == 0 or not bool(torch.isfinite(X).all()):
+        raise ValueError("rows must be finite and have at least one column")
+    dev = operator.device
+    sums = operator.normalise(X.to(dev).float())
+    count = torch.ones((N,), dtype=torch.float32, device=dev)
+    inv_count = torch.ones((N,), dtype=torch.float32, device=dev)
+    group = torch.from_numpy(np.repeat(np.arange(len(sizes), dtype=np.int32), sizes)).to(dev)
+    cluster_of = torch.arange(N, device=dev)
+    tiles = torch.zeros((), dtype=torch.long, device=dev)
+    n = N
+    while True:
+        nn, best, bad = operator.nearest_grouped(sums, inv_count, group, max_group)
+        if return_info:
+            tiles = tiles + _band_tiles(group, max_group)
+        target, n_merged = operator.merge(sums, count, inv_count, nn, best, float(cos_thr))
+        m, broken = torch.cat((n_merged.reshape(1), bad.reshape(1))).tolist()           # the host synchronisation of the round
+        if broken:
+            raise RuntimeError(f"grouped nearest pass over {n} clusters: `group` decreases or a group exceeds max_group={max_group}")
+        if m == 0:
+            break
+        info["rounds"] += 1
+        # the compaction of ahc_cosine_rows, with the group of every kept cluster
+        target = target.long()
+        ids = torch.arange(n, device=dev)
+        keep = target == ids
+        new_id = torch.cumsum(keep, 0) - 1
+        cluster_of = new_id[target[cluster_of]]
+        src = torch.empty((n - m + 1,), dtype=torch.long, device=dev)
+        src.scatter_(0, torch.where(keep, new_id, torch.full_like(new_id, n - m)), ids)
+        src = src[: n - m]
+        sums, count, inv_count, group = sums[src], count[src], inv_count[src], group[src]
+        n -= m
+    flat = cluster_of.cpu().numpy().astype(int)
+    labels = [flat[a:b] - (flat[a] if b > a else 0) for a, b in zip(offsets[:-1], offsets[1:])]
+    for lab in labels:                                                                  # a recording's cluster ids are a run of the global ones
+        assert lab.size == 0 or (lab[0] == 0 and np.all(np.diff(np.maximum.accumulate(lab)) <= 1)), "cluster ids are not numbered by first appearance"
+    info["clusters"] = [int(lab.max()) + 1 if lab.size else 0 for lab in labels]
+    info["gram_tiles"] = int(tiles)
     return (labels, info) if return_info else labels
 
 

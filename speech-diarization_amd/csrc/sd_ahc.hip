@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256, 2) void ahc_nearest_kernel(const float* __rest
       for (int j = 0; j < 4; ++j) acc[i][j][r] *= invr * invc[j];
     }
 
-  gt_sym_argmax(acc, [](int, int, int) { return true; }, ti, tj, n, npad, red_v, red_i, ws_val, ws_idx, tid, wm, wn, fr, fq);
+  gt_sym_argmax(acc, [](int, int, int) { return true; }, ti, tj, tj + 1, ti, n, npad, red_v, red_i, ws_val, ws_idx, tid, wm, wn, fr, fq);
 }
 
 __global__ __launch_bounds__(256) void ahc_nearest_finish_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,

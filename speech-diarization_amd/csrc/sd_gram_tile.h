@@ -12,11 +12,12 @@
 //   zeros past d.  acc[i][j][r] = <row rbase + 16 i + 4 fq + r, row cbase + 16 j + fr>, rbase = 128 ti + 64 wm, cbase = 128 tj + 64 wn.
 // * Symmetric argmax, from registers, of the weights the caller has made of acc (a weight and its mirror must be the same bits)
 //   for a tile on or above the diagonal.  Row maxima: over j in the lane, over fr across the 16-lane row, over the two waves of a
-//   row through LDS -> slot [tj + 1] of row block ti.  Column maxima (the row maxima of the mirrored tile, from the same
-//   accumulators): over i, r in the lane, over fq across lanes 16 / 32 apart, over the two waves of a column -> slot [ti] of row
-//   block tj.  The diagonal tile keeps col > row for the first and row < col for the second.  Among equal weights the lowest index
-//   wins at every step.
-// * gt_finish walks the tiles + 1 slots of a row in ascending order with a strict >.
+//   row through LDS -> slot [slot_row] of row block ti.  Column maxima (the row maxima of the mirrored tile, from the same
+//   accumulators): over i, r in the lane, over fq across lanes 16 / 32 apart, over the two waves of a column -> slot [slot_col] of
+//   row block tj.  The diagonal tile keeps col > row for the first and row < col for the second.  Among equal weights the lowest
+//   index wins at every step.  The caller numbers the slots so that the columns a slot stands for ascend with it: the full walk
+//   (sd_ahc.hip, sd_hdbscan.hip) passes tj + 1 and ti, the banded walk (ahc/sd_ahc_grouped.hip) its own.
+// * gt_finish walks the slots of a row in ascending order with a strict >.
 // * Every function takes the lane coordinates (tid, wm, wn, fr, fq) from the kernel.  Deriving them from threadIdx.x in here costs
 //   ahc_nearest_kernel about 20 VGPRs and with them its third workgroup per CU.
 #pragma once
@@ -117,19 +118,20 @@ __device__ __forceinline__ void gt_tile(const float* __restrict__ rows, const lo
 }
 
 // The symmetric argmax of tile (ti, tj), ti <= tj, whose weights are in acc; cand(i, r, j) says whether the pair of acc[i][j][r] may be
-// taken at all (it must be symmetric in the pair).  red_v / red_i carry the reduction over the two waves of a row or column.
+// taken at all (it must be symmetric in the pair).  The row maxima go to slot `slot_row` of row block ti, the column maxima to slot
+// `slot_col` of row block tj.  red_v / red_i carry the reduction over the two waves of a row or column.
 template <class Cand>
-__device__ __forceinline__ void gt_sym_argmax(const f32x4 (&acc)[4][4], const Cand cand, const int ti, const int tj, const int n,
-                                              const int npad, float (&red_v)[2][GT_T], int (&red_i)[2][GT_T], float* __restrict__ ws_val,
-                                              int* __restrict__ ws_idx, const int tid, const int wm, const int wn, const int fr,
-                                              const int fq) {
+__device__ __forceinline__ void gt_sym_argmax(const f32x4 (&acc)[4][4], const Cand cand, const int ti, const int tj, const int slot_row,
+                                              const int slot_col, const int n, const int npad, float (&red_v)[2][GT_T],
+                                              int (&red_i)[2][GT_T], float* __restrict__ ws_val, int* __restrict__ ws_idx, const int tid,
+                                              const int wm, const int wn, const int fr, const int fq) {
   const int rbase = ti * GT_T + wm * 64, cbase = tj * GT_T + wn * 64;
   const bool diag = ti == tj;
   int col[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) col[j] = cbase + 16 * j + fr;
 
-  // row maxima over the tile's columns -> slot tj + 1 of row block ti
+  // row maxima over the tile's columns -> slot slot_row of row block ti
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -156,13 +158,13 @@ __device__ __forceinline__ void gt_sym_argmax(const f32x4 (&acc)[4][4], const Ca
     float bv = red_v[0][tid];
     int bi = red_i[0][tid];
     gt_take(bv, bi, red_v[1][tid], red_i[1][tid]);
-    const size_t at = (size_t)(tj + 1) * npad + (size_t)ti * GT_T + tid;
+    const size_t at = (size_t)slot_row * npad + (size_t)ti * GT_T + tid;
     ws_val[at] = bv;
     ws_idx[at] = bi == INT_MAX ? -1 : bi;
   }
   __syncthreads();
 
-  // column maxima over the tile's rows = row maxima of the mirrored tile -> slot ti of row block tj
+  // column maxima over the tile's rows = row maxima of the mirrored tile -> slot slot_col of row block tj
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float bv = -INFINITY;
@@ -190,7 +192,7 @@ __device__ __forceinline__ void gt_sym_argmax(const f32x4 (&acc)[4][4], const Ca
     float bv = red_v[0][tid];
     int bi = red_i[0][tid];
     gt_take(bv, bi, red_v[1][tid], red_i[1][tid]);
-    const size_t at = (size_t)ti * npad + (size_t)tj * GT_T + tid;
+    const size_t at = (size_t)slot_col * npad + (size_t)tj * GT_T + tid;
     ws_val[at] = bv;
     ws_idx[at] = bi == INT_MAX ? -1 : bi;
   }

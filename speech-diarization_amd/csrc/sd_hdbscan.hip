@@ -172,8 +172,8 @@ __global__ __launch_bounds__(256, 2) void hdb_outgoing_kernel(const float* __res
     }
 
   // only an edge into ANOTHER component is a candidate
-  gt_sym_argmax(acc, [&](int i, int r, int j) { return compr[i][r] != compc[j]; }, ti, tj, n, npad, red_v, red_i, ws_val, ws_idx, tid, wm,
-                wn, fr, fq);
+  gt_sym_argmax(acc, [&](int i, int r, int j) { return compr[i][r] != compc[j]; }, ti, tj, tj + 1, ti, n, npad, red_v, red_i, ws_val, ws_idx,
+                tid, wm, wn, fr, fq);
 }
 
 __global__ __launch_bounds__(256) void hdb_outgoing_finish_kernel(const float* __restrict__ ws_val, const int* __restrict__ ws_idx,

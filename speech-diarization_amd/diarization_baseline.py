@@ -168,11 +168,7 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
         from .speech_encode import ecapa_encode_batch
         encoder = ecapa_encode_batch
 
-    scorer = vad.SileroVAD(model=vad_scorer or vad.EnergyScorer())
-    probs = scorer.probs(y, sr)
-    mask = vad.morph_open_close(vad.hysteresis_binarize(probs, 0.6, 0.4), 10.0)
-    speech = vad.mask_to_segments(mask, 10.0, min_speech_ms=min_speech_duration_s * 1000.0,
-                                  min_gap_ms=min_silence_duration_s * 1000.0, speech_pad_ms=40.0)
+    speech = _speech_regions(y, sr, min_speech_duration_s, min_silence_duration_s, vad_scorer)
     segments: list[tuple[float, float, str | int]] = []
     details = {"speech": speech, "labels": np.zeros(0, dtype=int), "embeddings": np.zeros((0, 192), np.float32)}
     if speech:
@@ -214,6 +210,69 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
         with open(rttm_filepath, "w") as f:
             rttm.write_rttm(segments, uri, f)
     return (segments, details) if return_details else segments
+
+
+def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s: float, min_speakers: int, max_speakers: int,
+                   rttm_filepaths=None, *, clustering: str = "ahc_gpu", clustering_threshold: float = 0.70, window_s: float = 2.0,
+                   hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True, return_details: bool = False):
+    """`diarize_audio(..., clustering="ahc_gpu")` for a list of recordings at once -> one segment list per recording (with
+    `return_details`: a list of (segments, details)); the RTTM of recording i goes to `rttm_filepaths[i]` when that is given.
+
+    The host glue runs per recording as in `diarize_audio`.  The signals are then uploaded ONCE, concatenated with one window of zeros
+    after each (a window that hangs over a recording's end reads zeros, as it does for one recording), and all windows of all
+    recordings go through `encode_windows` together: the micro-batches are full whatever the recordings' sizes.  The rows, centred
+    per recording, are clustered by ONE driver (`ahc_gpu.ahc_cosine_groups`): one nearest pass and one host synchronisation per
+    round for all recordings.  HIP path only, and only clustering="ahc_gpu": the other routes have no grouped form."""
+    if clustering != "ahc_gpu":
+        raise ValueError(f"diarize_audios clusters all recordings in one driver, which exists for clustering='ahc_gpu' only, got {clustering!r}")
+    audios = list(audios)
+    rttm_filepaths = [None] * len(audios) if rttm_filepaths is None else list(rttm_filepaths)
+    if len(rttm_filepaths) != len(audios):
+        raise ValueError(f"{len(rttm_filepaths)} RTTM paths for {len(audios)} recordings")
+    from . import ahc_gpu
+    from .speech_encode import using_ecapa_encoder
+    sr, win = 16000, int(round(window_s * 16000))
+    recs, signal, starts_all, offset = [], [], [], 0
+    for audio in audios:
+        y, sr_, uri = _load(audio)
+        speech = _speech_regions(y, sr_, min_speech_duration_s, min_silence_duration_s, vad_scorer)
+        starts, centres, regions = speech_windows(speech, len(y), sr, window_s, hop_s) if speech else (np.zeros(0, np.int64), None, None)
+        recs.append({"uri": uri, "speech": speech, "starts": starts, "centres": centres, "regions": regions})
+        if len(starts):
+            signal += [y, np.zeros(win, np.float32)]
+            starts_all.append(starts + offset)
+            offset += len(y) + win
+    sizes = [len(r["starts"]) for r in recs]
+    bounds = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    labels = [np.zeros(0, dtype=int)] * len(recs)
+    embs = np.zeros((0, 192), np.float32)
+    if offset:
+        _device_rows(embs, True, clustering)                                            # the refusal without a visible GPU, before any work
+        embs = using_ecapa_encoder().encode_windows(np.concatenate(signal), np.concatenate(starts_all), win)
+        X = np.concatenate([cluster.center(embs[a:b]) if center_embeddings and b > a else embs[a:b] for a, b in zip(bounds[:-1], bounds[1:])])
+        labels = ahc_gpu.ahc_cosine_groups(_device_rows(X, True, clustering), sizes, clustering_threshold)
+    out = []
+    for r, a, b, lab, path in zip(recs, bounds[:-1], bounds[1:], labels, rttm_filepaths):
+        segments: list[tuple[float, float, str | int]] = []
+        details = {"speech": r["speech"], "labels": np.zeros(0, dtype=int), "embeddings": np.zeros((0, 192), np.float32)}
+        if r["speech"]:
+            lab = cluster.relabel_by_first_appearance(lab)
+            segments = [(s, e, rttm.speaker_label(k)) for s, e, k in labels_to_turns(r["speech"], r["centres"], r["regions"], lab)]
+            details.update(labels=lab, embeddings=embs[a:b], affinity=None, window_starts=r["starts"])
+        if path:
+            with open(path, "w") as f:
+                rttm.write_rttm(segments, r["uri"], f)
+        out.append((segments, details) if return_details else segments)
+    return out
+
+
+def _speech_regions(y: np.ndarray, sr: int, min_speech_duration_s: float, min_silence_duration_s: float, vad_scorer=None):
+    """The VAD chain of `diarize_audio`: frame probabilities -> hysteresis -> open / close -> [(start_s, end_s)] speech regions."""
+    scorer = vad.SileroVAD(model=vad_scorer or vad.EnergyScorer())
+    probs = scorer.probs(y, sr)
+    mask = vad.morph_open_close(vad.hysteresis_binarize(probs, 0.6, 0.4), 10.0)
+    return vad.mask_to_segments(mask, 10.0, min_speech_ms=min_speech_duration_s * 1000.0,
+                                min_gap_ms=min_silence_duration_s * 1000.0, speech_pad_ms=40.0)
 
 
 def _device_rows(X: np.ndarray, use_gpu: bool, clustering: str):
@@ -352,6 +411,16 @@ class Diarizer:
                                  clustering_threshold=hp.clustering_threshold)
         segments = [s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s]
         return sorted(segments)
+
+    def diarize_many(self, apaths, rttm_filepaths=None):
+        """`diarize` for a list of recordings through `diarize_audios` (clustering="ahc_gpu", the HIP path): one result per recording."""
+        hp = self.hparams
+        if self.encoder is not None:
+            raise RuntimeError("Diarizer.diarize_many runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+        many = diarize_audios(apaths, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
+                              min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepaths=rttm_filepaths,
+                              clustering=self.clustering, clustering_threshold=hp.clustering_threshold)
+        return [sorted(s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s) for segments in many]
 
     def merge_segments(self, segments):
         return merge_same_speaker(segments, self.hparams.same_speaker_gap_s, self.hparams.max_segment_s)

@@ -562,6 +562,31 @@ def ahc_nearest(sums: torch.Tensor, inv_count: torch.Tensor, ws: Workspace | tor
     return nn, best
 
 
+def ahc_nearest_grouped(sums: torch.Tensor, inv_count: torch.Tensor, group: torch.Tensor, max_group: int,
+                        ws: Workspace | torch.Tensor | None = None):
+    """`ahc_nearest` over the clusters of many recordings at once: group int32 [n], non-decreasing, names the recording of every
+    cluster, and only a cluster of the same recording is a neighbour; `max_group` bounds the clusters of any one recording
+    -> (nn int32 [n], indices into all n rows, -1 for a cluster alone in its recording; best f32 [n]; bad int32 [1], still on the
+    device: non-zero when `group` decreases somewhere or a group exceeds `max_group`, and nn / best mean nothing then).  The scores of
+    a recording are bit for bit those of `ahc_nearest` on its rows alone.  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_ahc_nearest_grouped_workspace_bytes(n, d, max_group), to reuse across calls (allocated when None)."""
+    _need_cuda(sums, inv_count, group)
+    sums, n, d, ld = rows4(sums, "cluster sums")
+    inv_count = inv_count.contiguous().float()
+    if inv_count.shape != (n,):
+        raise ValueError(f"inv_count {tuple(inv_count.shape)} does not match the {n} cluster sums")
+    if group.dtype != torch.int32 or group.shape != (n,) or not group.is_contiguous():
+        raise ValueError(f"group must be a contiguous {torch.int32} vector of {n} entries, got {tuple(group.shape)} {group.dtype}")
+    max_group = int(max_group)
+    nn = torch.empty((n,), dtype=torch.int32, device=sums.device)
+    best = torch.empty((n,), dtype=torch.float32, device=sums.device)
+    bad = torch.empty((1,), dtype=torch.int32, device=sums.device)
+    ws = _workspace(ws, int(N.load().sd_ahc_nearest_grouped_workspace_bytes(n, d, max_group)), sums.device)
+    launch("sd_ahc_nearest_grouped_f32", sums, sums.data_ptr(), ld, n, d, inv_count.data_ptr(), group.data_ptr(), max_group, nn.data_ptr(),
+           best.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return nn, best, bad
+
+
 def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, nn: torch.Tensor, best: torch.Tensor, cos_thr: float):
     """One round of merges IN PLACE: every reciprocal pair i < j (nn[i] == j, nn[j] == i) with best[i] > cos_thr adds row j of `sums`
     and its count into row i and refreshes inv_count[i] -> (target int32 [n]: i for the upper row of a pair, the row itself otherwise;
