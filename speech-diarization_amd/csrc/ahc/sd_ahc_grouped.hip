@@ -108,48 +108,26 @@ __global__ __launch_bounds__(256) void ahc_nearest_grouped_finish_kernel(const f
   gt_finish(ws_val, ws_idx, slots, npad, n, nn, best, i);
 }
 
-// W of the header: how many tiles to the right of the diagonal a group of max_group rows can reach
-inline int ag_band(int nt, int max_group) {
-  const long reach = ((long)max_group - 1 + GT_T - 1) / GT_T;
-  return (int)(reach < nt - 1 ? reach : nt - 1);
-}
-
 }  // namespace
 
 extern "C" size_t sd_ahc_nearest_grouped_workspace_bytes(int n, int d, int max_group) {
-  if (n <= 0 || d <= 0 || d > GT_MAX_D || max_group <= 0) return 0;
-  const size_t nt = (size_t)gt_tiles(n);
-  return (2 * (size_t)ag_band((int)nt, max_group) + 2) * nt * GT_T * (sizeof(float) + sizeof(int));
+  return sd_rows_workspace_bytes(SD_ROWS_BAND, n, d, 1, GT_MAX_D, max_group);
 }
 
 extern "C" int sd_ahc_nearest_grouped_f32(const float* sums, long ld, int n, int d, const float* inv_count, const int* group, int max_group,
                                           int* nn, float* best, int* bad, void* ws, size_t ws_bytes, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d, "sd_ahc_nearest_grouped_f32: n=%d d=%d ld=%ld", n, d, ld);
-  if (d > GT_MAX_D)
-    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_ahc_nearest_grouped_f32: d=%d, at most %d columns are supported", d, GT_MAX_D);
-  SD_CHECK_ARG(max_group > 0, "sd_ahc_nearest_grouped_f32: max_group=%d", max_group);
-  SD_CHECK_ARG(sums && inv_count && group && nn && best && bad && ws, "sd_ahc_nearest_grouped_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(sums) && ld % 4 == 0, "sd_ahc_nearest_grouped_f32: sums must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
-  SD_CHECK_ARG(sd_aligned16(ws), "sd_ahc_nearest_grouped_f32: workspace is not 16-byte aligned");
+  const SdRowsCall c = {"sd_ahc_nearest_grouped_f32", "sums", SD_ROWS_BAND, n, d, ld, 1, GT_MAX_D, max_group};
+  if (const int e = sd_rows_refused(c, sums, !(sums && inv_count && group && nn && best && bad && ws), ws, ws_bytes)) return e;
   const int nt = gt_tiles(n);
-  const int band = ag_band(nt, max_group);
-  if (band + 1 > GT_MAX_TILES)
-    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_ahc_nearest_grouped_f32: max_group=%d, a group of at most %d rows is supported", max_group,
-                        (GT_MAX_TILES - 1) * GT_T);
-  const size_t need = sd_ahc_nearest_grouped_workspace_bytes(n, d, max_group);
-  if (ws_bytes < need)
-    return sd_set_error(SD_ERR_WORKSPACE, "sd_ahc_nearest_grouped_f32: workspace of %zu bytes, n=%d d=%d max_group=%d needs %zu", ws_bytes, n,
-                        d, max_group, need);
-  const int npad = nt * GT_T, slots = 2 * band + 2;
-  float* const ws_val = static_cast<float*>(ws);
-  int* const ws_idx = reinterpret_cast<int*>(ws_val + (size_t)slots * npad);
+  const int band = ag_band(nt, max_group);      // W of the header
+  const GtSymWs w = gt_sym_ws(ws, nt, 2 * band + 2);
   SD_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), stream));
   hipLaunchKernelGGL(ahc_nearest_grouped_kernel, dim3((unsigned)nt, (unsigned)(band + 1)), dim3(256), 0, stream, sums, ld, n, d, inv_count,
-                     group, ws_val, ws_idx, npad, nt, band);
+                     group, w.val, w.idx, w.npad, nt, band);
   SD_CHECK_LAUNCH("ahc_nearest_grouped_kernel");
-  hipLaunchKernelGGL(ahc_nearest_grouped_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws_val, ws_idx, slots, npad, n,
-                     group, max_group, nn, best, bad);
+  hipLaunchKernelGGL(ahc_nearest_grouped_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w.val, w.idx, w.slots, w.npad,
+                     n, group, max_group, nn, best, bad);
   SD_CHECK_LAUNCH("ahc_nearest_grouped_finish_kernel");
   return SD_OK;
 }

@@ -9,18 +9,14 @@
 
 #include "sd_common.h"
 #include "sd_hip_diag.h"
+#include "sd_rows_check.h"
 
 namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr int DG_ROWS = SD_WHITEN_ROWS;
-constexpr int DG_MAX_D = 256;
-constexpr int DG_MAX_K = 1024;
+// DG_ROWS (SD_WHITEN_ROWS), DG_MAX_D (256), DG_MAX_K (1024), dg_tiles and dg_blocks: sd_rows_check.h, with the workspace they size
 constexpr int DG_MAX_TILES = DG_MAX_D / 16;
-
-inline int dg_tiles(int d) { return (d + 15) / 16; }
-inline int dg_blocks(int n) { return (n + DG_ROWS - 1) / DG_ROWS; }
 
 // one thread per column: the rows of block blockIdx.x in ascending order -> part[block][16 T]; columns [d, 16 T) stay unwritten, unread
 __global__ __launch_bounds__(256) void whiten_colsum_kernel(const float* __restrict__ x, const long ld, const int n, const int d,
@@ -183,24 +179,13 @@ __global__ __launch_bounds__(256) void label_centroids_kernel(const float* __res
 
 extern "C" int sd_diag_abi_version(void) { return SD_DIAG_ABI_VERSION; }
 
-extern "C" size_t sd_whiten_stats_workspace_bytes(int n, int d) {
-  if (n < 2 || d <= 0 || d > DG_MAX_D) return 0;
-  const size_t T = (size_t)dg_tiles(d);
-  return (size_t)dg_blocks(n) * (16 * T + 256 * (T * (T + 1) / 2)) * sizeof(double);
-}
+extern "C" size_t sd_whiten_stats_workspace_bytes(int n, int d) { return sd_rows_workspace_bytes(SD_ROWS_WHITEN, n, d, 2, DG_MAX_D); }
 
 extern "C" int sd_whiten_stats_f64(const float* x, long ld, int n, int d, double* mean, double* gram, long ldg, void* ws, size_t ws_bytes,
                                    sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n >= 2 && d > 0 && ld >= d && ldg >= d, "sd_whiten_stats_f64: n=%d d=%d ld=%ld ldg=%ld (n >= 2: one row has no covariance)", n, d, ld,
-               ldg);
-  if (d > DG_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_whiten_stats_f64: d=%d, at most %d columns are supported", d, DG_MAX_D);
-  SD_CHECK_ARG(x && mean && gram && ws, "sd_whiten_stats_f64: null pointer");
-  SD_CHECK_ARG(sd_aligned16(x) && ld % 4 == 0, "sd_whiten_stats_f64: x must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
-  SD_CHECK_ARG(sd_aligned16(ws), "sd_whiten_stats_f64: workspace is not 16-byte aligned");
-  const size_t need = sd_whiten_stats_workspace_bytes(n, d);
-  if (ws_bytes < need)
-    return sd_set_error(SD_ERR_WORKSPACE, "sd_whiten_stats_f64: workspace of %zu bytes, n=%d d=%d needs %zu", ws_bytes, n, d, need);
+  const SdRowsCall c = {"sd_whiten_stats_f64", "x", SD_ROWS_WHITEN, n, d, ld, 2, DG_MAX_D, 0, {{"ldg", ldg}}};
+  if (const int e = sd_rows_refused(c, x, !(x && mean && gram && ws), ws, ws_bytes)) return e;
   const int T = dg_tiles(d), nb = dg_blocks(n), P = T * (T + 1) / 2, dp = 16 * T;
   double* const colsum = static_cast<double*>(ws);                 // [nb][dp]
   double* const tiles = colsum + (size_t)nb * dp;                  // [nb][P][256]
@@ -218,10 +203,8 @@ extern "C" int sd_whiten_stats_f64(const float* x, long ld, int n, int d, double
 extern "C" int sd_whiten_apply_f64(const float* x, long ld, int n, int d, const double* mean, const double* w, long ldw, double eps_add,
                                    float* out, long ldo, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d && ldw >= d && ldo >= d, "sd_whiten_apply_f64: n=%d d=%d ld=%ld ldw=%ld ldo=%ld", n, d, ld, ldw, ldo);
-  if (d > DG_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_whiten_apply_f64: d=%d, at most %d columns are supported", d, DG_MAX_D);
-  SD_CHECK_ARG(x && mean && w && out, "sd_whiten_apply_f64: null pointer");
-  SD_CHECK_ARG(sd_aligned16(x) && ld % 4 == 0, "sd_whiten_apply_f64: x must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
+  const SdRowsCall c = {"sd_whiten_apply_f64", "x", SD_ROWS_ONLY, n, d, ld, 1, DG_MAX_D, 0, {{"ldw", ldw}, {"ldo", ldo}}};
+  if (const int e = sd_rows_refused(c, x, !(x && mean && w && out))) return e;
   hipLaunchKernelGGL(whiten_apply_kernel, dim3((unsigned)((n + 15) / 16)), dim3(64), 0, stream, x, ld, n, d, mean, w, ldw, eps_add, out, ldo);
   SD_CHECK_LAUNCH("whiten_apply_kernel");
   return SD_OK;
@@ -230,11 +213,8 @@ extern "C" int sd_whiten_apply_f64(const float* x, long ld, int n, int d, const 
 extern "C" int sd_label_centroids_f32(const float* x, long ld, int n, int d, const int* labels, int k, double eps_add, float* out, long ldo,
                                       int* count, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && k > 0 && ld >= d && ldo >= d, "sd_label_centroids_f32: n=%d d=%d k=%d ld=%ld ldo=%ld", n, d, k, ld, ldo);
-  if (d > DG_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_label_centroids_f32: d=%d, at most %d columns are supported", d, DG_MAX_D);
-  if (k > DG_MAX_K) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_label_centroids_f32: k=%d, at most %d labels are supported", k, DG_MAX_K);
-  SD_CHECK_ARG(x && labels && out && count, "sd_label_centroids_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(x) && ld % 4 == 0, "sd_label_centroids_f32: x must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
+  const SdRowsCall c = {"sd_label_centroids_f32", "x", SD_ROWS_LABELS, n, d, ld, 1, DG_MAX_D, k, {{"ldo", ldo}}};
+  if (const int e = sd_rows_refused(c, x, !(x && labels && out && count))) return e;
   hipLaunchKernelGGL(label_centroids_kernel, dim3((unsigned)k), dim3(256), 0, stream, x, ld, n, d, labels, eps_add, out, ldo, count);
   SD_CHECK_LAUNCH("label_centroids_kernel");
   return SD_OK;

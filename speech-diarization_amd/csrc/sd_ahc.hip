@@ -86,24 +86,15 @@ __global__ __launch_bounds__(64) void ahc_merge_kernel(float* __restrict__ sums,
 
 extern "C" int sd_ahc_abi_version(void) { return SD_AHC_ABI_VERSION; }
 
-extern "C" size_t sd_ahc_nearest_workspace_bytes(int n, int d) {
-  return gt_sym_workspace_bytes(n, d);
-}
+extern "C" size_t sd_ahc_nearest_workspace_bytes(int n, int d) { return sd_rows_workspace_bytes(SD_ROWS_SYM, n, d, 1, GT_MAX_D); }
 
 extern "C" int sd_ahc_nearest_f32(const float* sums, long ld, int n, int d, const float* inv_count, int* nn, float* best, void* ws,
                                   size_t ws_bytes, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d, "sd_ahc_nearest_f32: n=%d d=%d ld=%ld", n, d, ld);
-  if (d > GT_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_ahc_nearest_f32: d=%d, at most %d columns are supported", d, GT_MAX_D);
-  SD_CHECK_ARG(sums && inv_count && nn && best && ws, "sd_ahc_nearest_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(sums) && ld % 4 == 0, "sd_ahc_nearest_f32: sums must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
-  SD_CHECK_ARG(sd_aligned16(ws), "sd_ahc_nearest_f32: workspace is not 16-byte aligned");
+  const SdRowsCall c = {"sd_ahc_nearest_f32", "sums", SD_ROWS_SYM, n, d, ld, 1, GT_MAX_D};
+  if (const int e = sd_rows_refused(c, sums, !(sums && inv_count && nn && best && ws), ws, ws_bytes)) return e;
   const int nt = gt_tiles(n);
-  if (nt > GT_MAX_TILES) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_ahc_nearest_f32: n=%d, at most %d rows are supported", n, GT_MAX_TILES * GT_T);
-  const size_t need = sd_ahc_nearest_workspace_bytes(n, d);
-  if (ws_bytes < need)
-    return sd_set_error(SD_ERR_WORKSPACE, "sd_ahc_nearest_f32: workspace of %zu bytes, n=%d d=%d needs %zu", ws_bytes, n, d, need);
-  const GtSymWs w = gt_sym_ws(ws, nt);
+  const GtSymWs w = gt_sym_ws(ws, nt, nt + 1);
   hipLaunchKernelGGL(ahc_nearest_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, stream, sums, ld, n, d, inv_count, w.val, w.idx,
                      w.npad);
   SD_CHECK_LAUNCH("ahc_nearest_kernel");
@@ -116,9 +107,8 @@ extern "C" int sd_ahc_nearest_f32(const float* sums, long ld, int n, int d, cons
 extern "C" int sd_ahc_merge_f32(float* sums, long ld, int n, int d, float* count, float* inv_count, const int* nn, const float* best,
                                 float cos_thr, int* target, int* n_merged, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d, "sd_ahc_merge_f32: n=%d d=%d ld=%ld", n, d, ld);
-  SD_CHECK_ARG(sums && count && inv_count && nn && best && target && n_merged, "sd_ahc_merge_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(sums) && ld % 4 == 0, "sd_ahc_merge_f32: sums must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
+  const SdRowsCall c = {"sd_ahc_merge_f32", "sums", SD_ROWS_ONLY, n, d, ld, 1, INT_MAX};      // one thread walks a row: no limit on d
+  if (const int e = sd_rows_refused(c, sums, !(sums && count && inv_count && nn && best && target && n_merged))) return e;
   SD_CHECK_HIP(hipMemsetAsync(n_merged, 0, sizeof(int), stream));
   hipLaunchKernelGGL(ahc_merge_kernel, dim3((unsigned)n), dim3(64), 0, stream, sums, ld, n, d, count, inv_count, nn, best, cos_thr, target,
                      n_merged);

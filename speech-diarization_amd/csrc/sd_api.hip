@@ -3,6 +3,7 @@
 
 #include "sd_common.h"
 #include "sd_hip_trace.h"
+#include "sd_rows_check.h"
 #include <atomic>
 #include <cstring>
 #include <map>
@@ -25,6 +26,13 @@ int sd_set_error(int code, const char* fmt, ...) {
 }
 
 extern "C" const char* sd_last_error(void) { return g_err; }
+
+int sd_rows_refused(SdRowsCall c, const void* rows, bool any_null, const void* ws, size_t ws_bytes) {
+  c.any_null = any_null; c.rows_misaligned = !sd_aligned16(rows); c.ws_misaligned = !sd_aligned16(ws); c.ws_bytes = ws_bytes;
+  char why[SD_ROWS_WHY];
+  const int e = sd_rows_check(c, why);
+  return e == SD_OK ? SD_OK : sd_set_error(e, "%s", why);
+}
 extern "C" int sd_abi_version(void) { return SD_ABI_VERSION; }
 
 extern "C" size_t sd_sizeof(int which) {

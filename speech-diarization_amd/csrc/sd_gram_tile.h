@@ -27,12 +27,11 @@
 #include <cmath>
 
 #include "sd_common.h"
+#include "sd_rows_check.h"
 
-constexpr int GT_T = 128;                 // tile edge
+// GT_T (the tile edge, 128), GT_MAX_D, GT_MAX_TILES, gt_tiles and gt_sym_workspace_bytes: sd_rows_check.h, with the entries' check
 constexpr int GT_KC = 32;                 // k of one staged chunk
 constexpr int GT_LDS = GT_KC + 4;         // LDS row stride, floats: rows stay 16-byte aligned, consecutive rows shift by 4 banks
-constexpr int GT_MAX_D = 1024;
-constexpr int GT_MAX_TILES = 65535;       // grid.y
 
 // columns c .. c + 3 of a row (c % 4 == 0), zeros from column d on; nothing at or past d is read
 __device__ __forceinline__ f32x4 gt_load4(const float* __restrict__ row, int c, int d) {
@@ -215,22 +214,10 @@ __device__ __forceinline__ void gt_finish(const float* __restrict__ ws_val, cons
   best[i] = bv;
 }
 
-inline int gt_tiles(int n) { return (n + GT_T - 1) / GT_T; }
-
-// the workspace of the symmetric argmax: tiles + 1 slots of a (value, index) per padded row; 0 for a shape that is not supported
-inline size_t gt_sym_workspace_bytes(int n, int d) {
-  if (n <= 0 || d <= 0 || d > GT_MAX_D) return 0;
-  const size_t nt = (size_t)gt_tiles(n);
-  return (nt + 1) * nt * GT_T * (sizeof(float) + sizeof(int));
-}
-
-struct GtSymWs {
-  int npad, slots;
-  float* val;
-  int* idx;
-};
-inline GtSymWs gt_sym_ws(void* ws, int nt) {
-  const int npad = nt * GT_T, slots = nt + 1;
+// the workspace of the symmetric argmax as the kernels see it: `slots` slots of npad values, then as many indices
+struct GtSymWs { int npad, slots; float* val; int* idx; };
+inline GtSymWs gt_sym_ws(void* ws, int nt, int slots) {
+  const int npad = nt * GT_T;
   float* const val = static_cast<float*>(ws);
   return GtSymWs{npad, slots, val, reinterpret_cast<int*>(val + (size_t)slots * npad)};
 }

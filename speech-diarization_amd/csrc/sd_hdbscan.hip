@@ -23,8 +23,7 @@
 
 namespace {
 
-constexpr int HD_MAX_K = 16;
-constexpr int HD_CHUNK = 8;               // column tiles per workgroup of the core pass
+// HD_MAX_K (16) and HD_CHUNK (8 column tiles per workgroup of the core pass): sd_rows_check.h, with the workspace they size
 constexpr int HD_SC = 65;                 // row stride of the score half-tile in LDS: a wave's 64 rows fall into distinct banks
 static_assert(GT_T * HD_SC <= 2 * GT_T * GT_LDS, "the score half-tile reuses the staging buffer");
 static_assert(GT_T * (HD_MAX_K + 1) <= 2 * GT_T * GT_LDS, "so does the merge of the two threads of a row");
@@ -182,17 +181,15 @@ __global__ __launch_bounds__(256) void hdb_outgoing_finish_kernel(const float* _
   gt_finish(ws_val, ws_idx, slots, npad, n, nn, best, blockIdx.x * 256 + threadIdx.x);
 }
 
-inline int hd_chunks(int nt) { return (nt + HD_CHUNK - 1) / HD_CHUNK; }
-
+// the two launches of the core pass at KK = k rounded up to 1, 2, 4, 8, 16; the caller names the instantiation beside its number
 template <int KK>
-int hd_launch_core(const float* rows, long ld, int n, int d, int k, float* core, float* ws, int nt, hipStream_t stream) {
-  const int npad = nt * GT_T;
-  const int chunks = hd_chunks(nt);
-  hipLaunchKernelGGL(hdb_core_kernel<KK>, dim3((unsigned)chunks, (unsigned)nt), dim3(256), 0, stream, rows, ld, n, d, k, ws, npad, nt);
-  SD_CHECK_LAUNCH(KK == 1 ? "hdb_core_kernel<1>" : KK == 2 ? "hdb_core_kernel<2>" : KK == 4 ? "hdb_core_kernel<4>" : KK == 8 ? "hdb_core_kernel<8>" : "hdb_core_kernel<16>");
-  hipLaunchKernelGGL(hdb_core_finish_kernel<KK>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, chunks, npad, n, k, core);
-  SD_CHECK_LAUNCH(KK == 1 ? "hdb_core_finish_kernel<1>" : KK == 2 ? "hdb_core_finish_kernel<2>" : KK == 4 ? "hdb_core_finish_kernel<4>"
-                  : KK == 8 ? "hdb_core_finish_kernel<8>" : "hdb_core_finish_kernel<16>");
+int hd_launch_core(const float* rows, long ld, int n, int d, int k, float* core, void* ws, hipStream_t stream, const char* core_label,
+                   const char* finish_label) {
+  const int nt = gt_tiles(n), npad = nt * GT_T, chunks = hd_chunks(nt);
+  hipLaunchKernelGGL(hdb_core_kernel<KK>, dim3((unsigned)chunks, (unsigned)nt), dim3(256), 0, stream, rows, ld, n, d, k, static_cast<float*>(ws), npad, nt);
+  SD_CHECK_LAUNCH(core_label);
+  hipLaunchKernelGGL(hdb_core_finish_kernel<KK>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, static_cast<float*>(ws), chunks, npad, n, k, core);
+  SD_CHECK_LAUNCH(finish_label);
   return SD_OK;
 }
 
@@ -200,53 +197,28 @@ int hd_launch_core(const float* rows, long ld, int n, int d, int k, float* core,
 
 extern "C" int sd_hdbscan_abi_version(void) { return SD_HDBSCAN_ABI_VERSION; }
 
-extern "C" size_t sd_hdb_core_workspace_bytes(int n, int d, int k) {
-  if (n <= 1 || d <= 0 || d > GT_MAX_D || k <= 0 || k > HD_MAX_K || k > n - 1) return 0;
-  const size_t nt = (size_t)gt_tiles(n);
-  return (size_t)hd_chunks((int)nt) * nt * GT_T * (size_t)k * sizeof(float);
-}
+extern "C" size_t sd_hdb_core_workspace_bytes(int n, int d, int k) { return sd_rows_workspace_bytes(SD_ROWS_CORE, n, d, 1, GT_MAX_D, k); }
 
 extern "C" int sd_hdb_core_f32(const float* rows, long ld, int n, int d, int k, float* core, void* ws, size_t ws_bytes, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d, "sd_hdb_core_f32: n=%d d=%d ld=%ld", n, d, ld);
-  if (d > GT_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_hdb_core_f32: d=%d, at most %d columns are supported", d, GT_MAX_D);
-  if (k > HD_MAX_K) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_hdb_core_f32: k=%d, at most %d neighbours are supported", k, HD_MAX_K);
-  SD_CHECK_ARG(k >= 1 && k <= n - 1, "sd_hdb_core_f32: k=%d must lie in 1 .. n - 1 (n=%d)", k, n);
-  SD_CHECK_ARG(rows && core && ws, "sd_hdb_core_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(rows) && ld % 4 == 0, "sd_hdb_core_f32: rows must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
-  SD_CHECK_ARG(sd_aligned16(ws), "sd_hdb_core_f32: workspace is not 16-byte aligned");
-  const int nt = gt_tiles(n);
-  if (nt > GT_MAX_TILES) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_hdb_core_f32: n=%d, at most %d rows are supported", n, GT_MAX_TILES * GT_T);
-  const size_t need = sd_hdb_core_workspace_bytes(n, d, k);
-  if (ws_bytes < need)
-    return sd_set_error(SD_ERR_WORKSPACE, "sd_hdb_core_f32: workspace of %zu bytes, n=%d d=%d k=%d needs %zu", ws_bytes, n, d, k, need);
-  float* w = static_cast<float*>(ws);
-  if (k == 1) return hd_launch_core<1>(rows, ld, n, d, k, core, w, nt, stream);
-  if (k == 2) return hd_launch_core<2>(rows, ld, n, d, k, core, w, nt, stream);
-  if (k <= 4) return hd_launch_core<4>(rows, ld, n, d, k, core, w, nt, stream);
-  if (k <= 8) return hd_launch_core<8>(rows, ld, n, d, k, core, w, nt, stream);
-  return hd_launch_core<16>(rows, ld, n, d, k, core, w, nt, stream);
+  const SdRowsCall c = {"sd_hdb_core_f32", "rows", SD_ROWS_CORE, n, d, ld, 1, GT_MAX_D, k};
+  if (const int e = sd_rows_refused(c, rows, !(rows && core && ws), ws, ws_bytes)) return e;
+  if (k == 1) return hd_launch_core<1>(rows, ld, n, d, k, core, ws, stream, "hdb_core_kernel<1>", "hdb_core_finish_kernel<1>");
+  if (k == 2) return hd_launch_core<2>(rows, ld, n, d, k, core, ws, stream, "hdb_core_kernel<2>", "hdb_core_finish_kernel<2>");
+  if (k <= 4) return hd_launch_core<4>(rows, ld, n, d, k, core, ws, stream, "hdb_core_kernel<4>", "hdb_core_finish_kernel<4>");
+  if (k <= 8) return hd_launch_core<8>(rows, ld, n, d, k, core, ws, stream, "hdb_core_kernel<8>", "hdb_core_finish_kernel<8>");
+  return hd_launch_core<16>(rows, ld, n, d, k, core, ws, stream, "hdb_core_kernel<16>", "hdb_core_finish_kernel<16>");
 }
 
-extern "C" size_t sd_hdb_outgoing_workspace_bytes(int n, int d) {
-  return gt_sym_workspace_bytes(n, d);
-}
+extern "C" size_t sd_hdb_outgoing_workspace_bytes(int n, int d) { return sd_rows_workspace_bytes(SD_ROWS_SYM, n, d, 1, GT_MAX_D); }
 
 extern "C" int sd_hdb_outgoing_f32(const float* rows, long ld, int n, int d, const float* core, const int* comp, int* nn, float* best,
                                    void* ws, size_t ws_bytes, sd_stream_t stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  SD_CHECK_ARG(n > 0 && d > 0 && ld >= d, "sd_hdb_outgoing_f32: n=%d d=%d ld=%ld", n, d, ld);
-  if (d > GT_MAX_D) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_hdb_outgoing_f32: d=%d, at most %d columns are supported", d, GT_MAX_D);
-  SD_CHECK_ARG(rows && core && comp && nn && best && ws, "sd_hdb_outgoing_f32: null pointer");
-  SD_CHECK_ARG(sd_aligned16(rows) && ld % 4 == 0, "sd_hdb_outgoing_f32: rows must be 16-byte aligned with ld %% 4 == 0 (ld=%ld)", ld);
-  SD_CHECK_ARG(sd_aligned16(ws), "sd_hdb_outgoing_f32: workspace is not 16-byte aligned");
+  const SdRowsCall c = {"sd_hdb_outgoing_f32", "rows", SD_ROWS_SYM, n, d, ld, 1, GT_MAX_D};
+  if (const int e = sd_rows_refused(c, rows, !(rows && core && comp && nn && best && ws), ws, ws_bytes)) return e;
   const int nt = gt_tiles(n);
-  if (nt > GT_MAX_TILES)
-    return sd_set_error(SD_ERR_UNSUPPORTED, "sd_hdb_outgoing_f32: n=%d, at most %d rows are supported", n, GT_MAX_TILES * GT_T);
-  const size_t need = sd_hdb_outgoing_workspace_bytes(n, d);
-  if (ws_bytes < need)
-    return sd_set_error(SD_ERR_WORKSPACE, "sd_hdb_outgoing_f32: workspace of %zu bytes, n=%d d=%d needs %zu", ws_bytes, n, d, need);
-  const GtSymWs w = gt_sym_ws(ws, nt);
+  const GtSymWs w = gt_sym_ws(ws, nt, nt + 1);
   hipLaunchKernelGGL(hdb_outgoing_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, stream, rows, ld, n, d, core, comp, w.val, w.idx,
                      w.npad);
   SD_CHECK_LAUNCH("hdb_outgoing_kernel");

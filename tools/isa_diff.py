@@ -57,6 +57,7 @@ def compile_tree(tree, flags, sources, out_dir, pool):
 
     def one(src):
         out = os.path.join(out_dir, src + ".s")
+        os.makedirs(os.path.dirname(out), exist_ok=True)      # (a source in a subdirectory: diag/, ahc/)
         cmd = flags + inc + ["--offload-device-only", "-S", os.path.join(tree, PKG, "csrc", src), "-o", out]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
