@@ -38,6 +38,8 @@
 extern "C" {
 #endif
 
+/* The version moves when an existing entry changes its signature or its meaning.  An additive entry (the two grouped entries below)
+ * does not move it: a caller that needs one looks the symbol up. */
 #define SD_HDBSCAN_ABI_VERSION 1
 
 int sd_hdbscan_abi_version(void);
@@ -86,6 +88,62 @@ int sd_hdb_core_f32(const float* rows, long ld, int n, int d, int k, float* core
 size_t sd_hdb_outgoing_workspace_bytes(int n, int d);
 int sd_hdb_outgoing_f32(const float* rows, long ld, int n, int d, const float* core, const int* comp, int* nn, float* best, void* ws,
                         size_t ws_bytes, sd_stream_t stream);
+
+/* ---- many recordings at once -------------------------------------------------------------------------------------------------------
+ * The rows of all recordings stand one after another; a row's core value and every tree edge look only inside the row's own
+ * recording.  Conventions as for sd_ahc_nearest_grouped_f32 (sd_hip_ahc.h):
+ *
+ *   group      device int32 [n]: the recording of every row, NON-DECREASING
+ *   max_group  the caller's upper bound on the rows of any one group, >= 1
+ *   bad        device int32 [1]: set to 0 first; non-zero afterwards when `group` decreases somewhere or a group has more than
+ *              max_group rows (group is monotone, so that is group[i] == group[i + max_group] for some i).  The results mean nothing
+ *              then.  No index depends on the contents of `group`: a broken promise is reported and can never send a load or a store
+ *              out of bounds
+ *
+ * Every product comes from the tile of the entries above, with the same k order: the scores of a recording are bit for bit the ones
+ * it gets alone, so per group `core`, `nn` minus the group's first row and the bits of `best` equal those of sd_hdb_core_f32 and
+ * sd_hdb_outgoing_f32 on the group's rows alone.  No allocation, no synchronisation, no floating-point atomics: results are bitwise
+ * equal run to run.  Every refusal happens before anything is launched.
+ *
+ * The walk is a band.  Rows of one group lie at most max_group - 1 apart, so row block I can meet a row of one of its groups only in
+ * the column tiles I - W .. I + W, W = min(T - 1, ceil((max_group - 1) / 128)), T = ceil(n / 128).  A tile outside [0, T) and a tile
+ * whose column block shares no group with the row block (decided from two loads of `group`) load nothing. */
+
+/* core[i] = the k-th largest of the multiset { score(i, j) : j != i, group[j] == group[i] } padded with -inf: a row with fewer than k
+ * such j gets -inf (hdbscan_gpu.py never asks for it).
+ *
+ *   k      1 <= k <= 16 (SD_ERR_UNSUPPORTED above 16); there is no k <= n - 1 rule here
+ *   ws     device, at least sd_hdb_core_grouped_workspace_bytes(n, d, k, max_group) bytes, 16-byte aligned
+ *
+ * Grid (ceil((2 W + 1) / 8), T): workgroup (c, I) walks 8 column tiles of the band of row block I over the FULL Gram, I - W + 8 c
+ * onwards; the scan, the slots and the merge are those of sd_hdb_core_f32, and the second kernel also checks the two promises.
+ *
+ *     sd_hdb_core_grouped_workspace_bytes(n, d, k, max_group) = ceil((2 W + 1) / 8) · 128 T · k · 4      (linear in n at a fixed max_group);
+ *                                                               0 for n <= 0, d <= 0, d > 1024, k <= 0, k > 16 or max_group <= 0
+ *
+ * SD_ERR_ARG: a null pointer (group and bad included), n <= 0, d <= 0, ld < d, k <= 0, max_group <= 0, rows not 16-byte aligned,
+ * ld % 4 != 0, ws not 16-byte aligned.  SD_ERR_UNSUPPORTED: d > 1024, k > 16, n > 128 · 65535.  SD_ERR_WORKSPACE: a smaller workspace. */
+size_t sd_hdb_core_grouped_workspace_bytes(int n, int d, int k, int max_group);
+int sd_hdb_core_grouped_f32(const float* rows, long ld, int n, int d, int k, const int* group, int max_group, float* core, int* bad, void* ws,
+                            size_t ws_bytes, sd_stream_t stream);
+
+/* best[i] = max of w(i, j) over j with group[j] == group[i] and comp[j] != comp[i],    nn[i] = the lowest such j that attains it, as an
+ * index into all n rows.  A row with no such j (its component is its whole group) gets nn[i] = -1, best[i] = -inf.
+ *
+ *   core, comp, nn, best: as for sd_hdb_outgoing_f32 (component ids need not differ between groups: the group is looked at first)
+ *   ws     device, at least sd_hdb_outgoing_grouped_workspace_bytes(n, d, max_group) bytes, 16-byte aligned
+ *
+ * The grid (T, W + 1), the ownership of the empty tiles, the 2 W + 2 slots of a row block and the workspace are those of
+ * sd_ahc_nearest_grouped_f32; the weight is that of sd_hdb_outgoing_f32.
+ *
+ *     sd_hdb_outgoing_grouped_workspace_bytes(n, d, max_group) = (2 W + 2) · 128 T · 8;
+ *                                                                0 for n <= 0, d <= 0, d > 1024 or max_group <= 0
+ *
+ * SD_ERR_ARG: a null pointer (group and bad included), n <= 0, d <= 0, ld < d, max_group <= 0, rows not 16-byte aligned, ld % 4 != 0,
+ * ws not 16-byte aligned.  SD_ERR_UNSUPPORTED: d > 1024, W + 1 > 65535.  SD_ERR_WORKSPACE: a smaller workspace. */
+size_t sd_hdb_outgoing_grouped_workspace_bytes(int n, int d, int max_group);
+int sd_hdb_outgoing_grouped_f32(const float* rows, long ld, int n, int d, const float* core, const int* comp, const int* group, int max_group,
+                                int* nn, float* best, int* bad, void* ws, size_t ws_bytes, sd_stream_t stream);
 
 #ifdef __cplusplus
 }

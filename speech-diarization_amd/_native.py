@@ -197,6 +197,10 @@ HDBSCAN_PROTOTYPES = {
     "sd_hdb_core_f32": (_I, [_P, C.c_long, _I, _I, _I, _P, _P, _Z, _P]),
     "sd_hdb_outgoing_workspace_bytes": (_Z, [_I, _I]),
     "sd_hdb_outgoing_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "sd_hdb_core_grouped_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "sd_hdb_core_grouped_f32": (_I, [_P, C.c_long, _I, _I, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "sd_hdb_outgoing_grouped_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sd_hdb_outgoing_grouped_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
 }
 
 # include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own

@@ -401,20 +401,11 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     `packed_embeddings=True` embeds every segment as if alone (`embed_segments(..., packed=True)`) instead of in the reference's
     zero-padded batches of 32 (the default)."""
     from . import cluster
-    if isinstance(wav_path, np.ndarray):
-        y = np.ascontiguousarray(wav_path, dtype=np.float32)
-    else:
-        y, sr = diar_read_audio(wav_path, sr, lufs=target_lufs)
-        y = np.ascontiguousarray(y, dtype=np.float32)
-    vad_fn = vad_segments or silero_vad_segments
-    speech_t = vad_fn(y, sr, on_threshold=vad_on_thr, off_threshold=vad_off_thr, min_speech_ms=min_speech_ms,
-                      min_silence_ms=min_silence_ms, speech_pad_ms=speech_pad_ms, morph_open_ms=morph_open_ms,
-                      morph_close_ms=morph_close_ms)
-    if not speech_t:
+    front = _diarize_front(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                           morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings)
+    if front is None:
         return []
-    speech = [Segment(s, e) for s, e in speech_t]
-    speech2 = scd_split_segments(y, sr, speech, win_ms=scd_win_ms, hop_ms=scd_hop_ms, thr=scd_thr, encode=encode)
-    embs = embed_segments(y, sr, speech2, encode=encode, packed=packed_embeddings)
+    embs = front[4]
     if clusterer == "ahc_affinity":
         raw = cluster.ahc_cosine(cosine_affinity(embs, _on_gpu(encode)), cluster_cos)
     else:
@@ -427,6 +418,36 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
         if factory is not None and not callable(factory):
             raise ValueError(f"clusterer must be 'hdbscan_two_stage', 'ahc', 'hdbscan_gpu', 'ahc_affinity' or a factory, got {clusterer!r}")
         raw = cluster_hdbscan_two_stage(embs, min_cluster_size=2, clusterer_factory=factory)
+    return _diarize_tail(front, raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
+                         packed_embeddings)
+
+
+def _diarize_front(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                   morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings):
+    """`diarize` up to the embeddings: load, VAD, SCD split, embed -> (y, sr, speech, speech2, embs), or None when the VAD finds no
+    speech."""
+    if isinstance(wav_path, np.ndarray):
+        y = np.ascontiguousarray(wav_path, dtype=np.float32)
+    else:
+        y, sr = diar_read_audio(wav_path, sr, lufs=target_lufs)
+        y = np.ascontiguousarray(y, dtype=np.float32)
+    vad_fn = vad_segments or silero_vad_segments
+    speech_t = vad_fn(y, sr, on_threshold=vad_on_thr, off_threshold=vad_off_thr, min_speech_ms=min_speech_ms,
+                      min_silence_ms=min_silence_ms, speech_pad_ms=speech_pad_ms, morph_open_ms=morph_open_ms,
+                      morph_close_ms=morph_close_ms)
+    if not speech_t:
+        return None
+    speech = [Segment(s, e) for s, e in speech_t]
+    speech2 = scd_split_segments(y, sr, speech, win_ms=scd_win_ms, hop_ms=scd_hop_ms, thr=scd_thr, encode=encode)
+    embs = embed_segments(y, sr, speech2, encode=encode, packed=packed_embeddings)
+    return y, sr, speech, speech2, embs
+
+
+def _diarize_tail(front, raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
+                  packed_embeddings) -> list[Segment]:
+    """`diarize` from the raw cluster labels on: relabel, conservative merge, re-embed, frame reassignment, merge_adjacent."""
+    from . import cluster
+    y, sr, speech, speech2, embs = front
     labels = cluster.relabel_by_first_appearance(raw)
     for s, lab in zip(speech2, labels):
         s.spk = int(lab)
@@ -436,6 +457,35 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     embs3 = embed_segments(y, sr, speech3, encode=encode, packed=packed_embeddings)
     speech4 = frame_reassign(y, sr, speech, speech3, embs3, smooth_step=0.10, win=1.0, encode=encode) if reseg else speech3
     return merge_adjacent(speech4, gap=merge_max_gap_s)
+
+
+def diarize_many(wav_paths, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: float = 0.6, vad_off_thr: float = 0.4,
+                 min_speech_ms: float = 250, min_silence_ms: float = 100, speech_pad_ms: float = 70.0, morph_open_ms: float = 80.0,
+                 morph_close_ms: float = 40.0, scd_win_ms: float = 1000.0, scd_hop_ms: float = 200, scd_thr: float = 1.50,
+                 merge_max_gap_s: float = 0.5, merge_max_speech_s: float = 30.0, merge_mincos: float = 0.8, reseg: int = 1, *,
+                 cluster_cos: float = 0.70, encode: Encoder | None = None, vad_segments: Callable | None = None,
+                 compat_reference_bugs: bool = False, clusterer: str = "hdbscan_gpu", packed_embeddings: bool = False) -> list[list[Segment]]:
+    """`diarize(..., clusterer="hdbscan_gpu")` for a list of recordings (each a path, an `(array, sample_rate)` tuple or a conditioned
+    array, as for `diarize`) -> the list of their segment lists, each equal to `diarize` on that recording alone.
+
+    Per recording the front of `diarize` (load, VAD, SCD split, embed); then ONE `cluster_hdbscan_two_stage_many` over the embeddings
+    of all recordings (`hdbscan_gpu.hdbscan_rows_groups`: one grouped core pass and one Boruvka loop for stage 1, one more for the
+    centroids); then per recording the tail (relabel, conservative merge, re-embed, frame reassignment, merge_adjacent).  A recording
+    without speech gives [].  Only the "hdbscan_gpu" clusterer has a grouped driver; any other raises ValueError (`cluster_cos` is
+    accepted for the parameter list of `diarize` and not used by it).  The embedding launches are not shared across recordings."""
+    from . import cluster, hdbscan_gpu
+    if clusterer != "hdbscan_gpu":
+        raise ValueError(f"diarize_many clusters with 'hdbscan_gpu' alone (the clusterer that has a grouped driver), got {clusterer!r}")
+    fronts = [_diarize_front(w, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                             morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings) for w in wav_paths]
+    live = [i for i, f in enumerate(fronts) if f is not None]
+    raws = cluster.cluster_hdbscan_two_stage_many([fronts[i][4] for i in live], min_cluster_size=2,
+                                                  clusterer_factory=hdbscan_gpu.HdbscanGpuClusterer.factory())
+    out: list[list[Segment]] = [[] for _ in fronts]
+    for i, raw in zip(live, raws):
+        out[i] = _diarize_tail(fronts[i], raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
+                               packed_embeddings)
+    return out
 
 
 def main(wav_path: str, sr: int = 16000, target_lufs: float = -18.0, vad_thr: float = 0.55, min_speech: float = 0.15,
@@ -479,6 +529,12 @@ def cluster_hdbscan_two_stage(embs: np.ndarray, min_cluster_size: int = 2, clust
     """[REF anti_stick_diarize.py:189-270] (restated in `cluster.cluster_hdbscan_two_stage`)."""
     from . import cluster
     return cluster.cluster_hdbscan_two_stage(embs, min_cluster_size, clusterer_factory)
+
+
+def cluster_hdbscan_two_stage_many(embs_list, min_cluster_size: int = 2, clusterer_factory=None) -> list:
+    """`cluster_hdbscan_two_stage` for a list of recordings (restated in `cluster.cluster_hdbscan_two_stage_many`)."""
+    from . import cluster
+    return cluster.cluster_hdbscan_two_stage_many(embs_list, min_cluster_size, clusterer_factory)
 
 
 def cosine_affinity(embs: np.ndarray, use_gpu: bool) -> np.ndarray:

@@ -192,23 +192,83 @@ def cluster_hdbscan_two_stage(embs: np.ndarray, min_cluster_size: int = 2, clust
         return np.zeros(num_segments, dtype=int) if num_segments > 0 else np.array([])
     factory = clusterer_factory or default_hdbscan_factory
     settings = dict(min_cluster_size=min_cluster_size, min_samples=None, metric="euclidean", allow_single_cluster=True)
-    embs_norm = embs / (np.linalg.norm(embs, axis=1, keepdims=True) + 1e-8)
-    stage1 = np.asarray(factory(**settings).fit_predict(embs_norm))
-    n_micro = int(np.max(stage1)) + 1
-    if n_micro < 1:
-        return np.zeros(num_segments, dtype=int) if num_segments > 0 else np.array([])
-    member_rows = [np.flatnonzero(stage1 == i) for i in range(n_micro)]
-    kept = [(i, rows) for i, rows in enumerate(member_rows) if rows.size]     # labels that actually occur
+    stage1 = np.asarray(factory(**settings).fit_predict(_scaled_rows(embs)))
+    kept, centroids = _micro_centroids(embs, stage1)
     if not kept:
-        return np.zeros(num_segments, dtype=int)
-    centroids = np.array([np.mean(embs[rows], axis=0) for _, rows in kept])
+        return np.zeros(num_segments, dtype=int) if num_segments > 0 else np.array([])
     if len(centroids) < min_cluster_size:
         stage2 = np.zeros(len(centroids), dtype=int)
     else:
-        cents_norm = centroids / (np.linalg.norm(centroids, axis=1, keepdims=True) + 1e-8)
-        stage2 = np.asarray(factory(**settings).fit_predict(cents_norm))
+        stage2 = np.asarray(factory(**settings).fit_predict(_scaled_rows(centroids)))
+    return _inherit(num_segments, kept, stage2)
+
+
+def _scaled_rows(embs: np.ndarray) -> np.ndarray:
+    """Rows scaled by 1 / (norm + 1e-8) [REF anti_stick_diarize.py:199, :246]."""
+    return embs / (np.linalg.norm(embs, axis=1, keepdims=True) + 1e-8)
+
+
+def _micro_centroids(embs: np.ndarray, stage1: np.ndarray):
+    """Step 2 of the two-stage glue -> ([member rows of every micro-cluster label that occurs, in label order], their centroids: the
+    mean of the UN-normalised member rows); ([], None) when stage 1 found no micro-cluster."""
+    n_micro = int(np.max(stage1)) + 1
+    if n_micro < 1:
+        return [], None
+    member_rows = [np.flatnonzero(stage1 == i) for i in range(n_micro)]
+    kept = [rows for rows in member_rows if rows.size]               # labels that actually occur
+    if not kept:
+        return [], None
+    return kept, np.array([np.mean(embs[rows], axis=0) for rows in kept])
+
+
+def _inherit(num_segments: int, kept, stage2) -> np.ndarray:
+    """Step 4: members inherit their centroid's label; members of a noise centroid and stage-1 noise stay -1."""
     final = np.full(num_segments, -1, dtype=int)
-    for (_, rows), lab in zip(kept, stage2):
+    for rows, lab in zip(kept, stage2):
         if lab != -1:
             final[rows] = lab
     return final
+
+
+def cluster_hdbscan_two_stage_many(embs_list, min_cluster_size: int = 2, clusterer_factory=None) -> list:
+    """`cluster_hdbscan_two_stage` for a list of recordings -> a list of label arrays, each equal to `cluster_hdbscan_two_stage` on
+    that recording alone.  When the clusterer has `fit_predict_many` (`hdbscan_gpu.HdbscanGpuClusterer`: one grouped driver for all
+    matrices), stage 1 is ONE call over all recordings that have at least two rows and stage 2 ONE call over the centroids of all
+    recordings that reach it; otherwise both loop `fit_predict`.  The early exits of the glue apply per recording: fewer than 2 rows,
+    no micro-cluster, fewer centroids than `min_cluster_size`."""
+    embs_list = [np.asarray(e) for e in embs_list]
+    factory = clusterer_factory or default_hdbscan_factory
+    settings = dict(min_cluster_size=min_cluster_size, min_samples=None, metric="euclidean", allow_single_cluster=True)
+
+    def fit_many(mats):
+        if not mats:
+            return []
+        clu = factory(**settings)
+        if hasattr(clu, "fit_predict_many"):
+            return [np.asarray(lab) for lab in clu.fit_predict_many(mats)]
+        return [np.asarray(clu.fit_predict(mats[0]))] + [np.asarray(factory(**settings).fit_predict(m)) for m in mats[1:]]
+
+    out = [None] * len(embs_list)
+    big = []
+    for r, embs in enumerate(embs_list):
+        n = embs.shape[0]
+        if n < 2:
+            out[r] = np.zeros(n, dtype=int) if n > 0 else np.array([])
+        else:
+            big.append(r)
+    stage1 = fit_many([_scaled_rows(embs_list[r]) for r in big])
+    second = []                                                      # (recording, kept) of the recordings whose centroids are re-clustered
+    cents = []
+    for r, s1 in zip(big, stage1):
+        n = embs_list[r].shape[0]
+        kept, centroids = _micro_centroids(embs_list[r], s1)
+        if not kept:
+            out[r] = np.zeros(n, dtype=int)
+        elif len(centroids) < min_cluster_size:
+            out[r] = _inherit(n, kept, np.zeros(len(centroids), dtype=int))
+        else:
+            second.append((r, kept))
+            cents.append(_scaled_rows(centroids))
+    for (r, kept), s2 in zip(second, fit_many(cents)):
+        out[r] = _inherit(embs_list[r].shape[0], kept, s2)
+    return out

@@ -18,32 +18,16 @@
 #include <cmath>
 
 #include "sd_common.h"
+#include "hdbscan/sd_hdb_scan.h"
 #include "sd_gram_tile.h"
 #include "sd_hip_hdbscan.h"
 
 namespace {
 
-// HD_MAX_K (16) and HD_CHUNK (8 column tiles per workgroup of the core pass): sd_rows_check.h, with the workspace they size
-constexpr int HD_SC = 65;                 // row stride of the score half-tile in LDS: a wave's 64 rows fall into distinct banks
-static_assert(GT_T * HD_SC <= 2 * GT_T * GT_LDS, "the score half-tile reuses the staging buffer");
-static_assert(GT_T * (HD_MAX_K + 1) <= 2 * GT_T * GT_LDS, "so does the merge of the two threads of a row");
+// HD_SC, hd_insert, the scan of a tile and the merges: hdbscan/sd_hdb_scan.h and the two body files beside it, shared with the grouped
+// core pass (hdbscan/sd_hdb_grouped.hip)
 
 // ----------------------------------------------------------------------------------------------------------------- core values
-
-// v into the descending list top[0 .. KK): equal values are kept as often as they come (a multiset)
-template <int KK>
-__device__ __forceinline__ void hd_insert(float (&top)[KK], float v) {
-  if (v > top[KK - 1]) {
-#pragma unroll
-    for (int q = 0; q < KK; ++q) {
-      if (v > top[q]) {
-        const float t = top[q];
-        top[q] = v;
-        v = t;
-      }
-    }
-  }
-}
 
 template <int KK>
 __global__ __launch_bounds__(256, 2) void hdb_core_kernel(const float* __restrict__ rows, const long ld, const int n, const int d, const int k,
@@ -67,59 +51,18 @@ __global__ __launch_bounds__(256, 2) void hdb_core_kernel(const float* __restric
   for (int tj = tj0; tj < tj1; ++tj) {
     f32x4 acc[4][4];
     gt_tile(rows, ld, n, d, ti, tj, lds, acc, tid, wm, wn, fr, fq);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      __syncthreads();                      // the operands (h = 0) or the previous half (h = 1) have been read
-      if (wn == h) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) lds[(wm * 64 + 16 * i + 4 * fq + r) * HD_SC + 16 * j + fr] = acc[i][j][r];
-      }
-      __syncthreads();
-      const int c0 = half * 32;
-      const int col0 = tj * GT_T + h * 64 + c0;
-      const float* const src = lds + lrow * HD_SC + c0;
-      for (int c = 0; c < 32; ++c) {
-        const int col = col0 + c;
-        if (col < n && col != row) hd_insert<KK>(top, src[c]);
-      }
-    }
+#define HD_SCAN_CAND(col, at) ((col) != row)
+#include "hdbscan/sd_hdb_scan_body.h"
+#undef HD_SCAN_CAND
   }
 
-  // the two threads of a row: the upper one hands its list over, the lower one merges and writes the k best of this chunk
-  __syncthreads();
-  if (half == 1) {
-#pragma unroll
-    for (int q = 0; q < KK; ++q) lds[lrow * (KK + 1) + q] = top[q];
-  }
-  __syncthreads();
-  if (half == 0) {
-#pragma unroll
-    for (int q = 0; q < KK; ++q) hd_insert<KK>(top, lds[lrow * (KK + 1) + q]);
-    float* const out = ws + (size_t)blockIdx.x * k * npad + row;       // slot [chunk][q][padded row]
-#pragma unroll
-    for (int q = 0; q < KK; ++q)
-      if (q < k) out[(size_t)q * npad] = top[q];
-  }
+#include "hdbscan/sd_hdb_halves_body.h"
 }
 
 template <int KK>
 __global__ __launch_bounds__(256) void hdb_core_finish_kernel(const float* __restrict__ ws, const int chunks, const int npad, const int n,
                                                               const int k, float* __restrict__ core) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float top[KK];
-#pragma unroll
-  for (int q = 0; q < KK; ++q) top[q] = -INFINITY;
-  for (int s = 0; s < chunks * k; ++s) hd_insert<KK>(top, ws[(size_t)s * npad + i]);
-  float out = top[0];
-#pragma unroll
-  for (int q = 1; q < KK; ++q)
-    if (q == k - 1) out = top[q];
-  core[i] = out;
+  hd_finish<KK>(ws, chunks, npad, n, k, core, blockIdx.x * 256 + threadIdx.x);
 }
 
 // ----------------------------------------------------------------------------------------------------------------- outgoing edges

@@ -1,7 +1,7 @@
 // What an entry that takes "f32 rows" (const float* rows, long ld, int n, int d) refuses, and the bytes of its workspace: CHECK, pure
-// and host-only.  The eight entries of sd_ahc.hip, ahc/sd_ahc_grouped.hip, sd_hdbscan.hip and diag/sd_diag.hip
+// and host-only.  The ten entries of sd_ahc.hip, ahc/sd_ahc_grouped.hip, sd_hdbscan.hip, hdbscan/sd_hdb_grouped.hip and diag/sd_diag.hip
 // describe their call (SdRowsCall); sd_rows_check returns the status code and writes the message, in the one order every entry has
-// always used; the five *_workspace_bytes functions are sd_rows_workspace_bytes of the same kind and range.  Nothing else is read: no
+// always used; the seven *_workspace_bytes functions are sd_rows_workspace_bytes of the same kind and range.  Nothing else is read: no
 // pointer is followed, no environment, no device query.  No HIP header, so the same functions compile into a plain C++ program
 // (tests/test_rows_check_rules.py).  The geometry the sizes follow from stands here; the kernels read it from here.
 #pragma once
@@ -25,6 +25,8 @@ inline int dg_blocks(int n) { return (int)(((long)n + DG_ROWS - 1) / DG_ROWS); }
 // ---------------------------------------------------------------- host arithmetic (in long / size_t: n, k and max_group up to INT_MAX)
 inline int gt_tiles(int n) { return (int)(((long)n + GT_T - 1) / GT_T); }
 inline int hd_chunks(int nt) { return (nt + HD_CHUNK - 1) / HD_CHUNK; }
+// the banded core pass (hdbscan/sd_hdb_grouped.hip): the chunks of the 2 W + 1 column tiles of a row block
+inline int hd_band_chunks(int band) { return (2 * band + 1 + HD_CHUNK - 1) / HD_CHUNK; }
 // the banded walk (ahc/sd_ahc_grouped.hip): how many tiles to the right of the diagonal a group of max_group rows can reach, at most nt - 1
 inline int ag_band(int nt, int max_group) { const long reach = ((long)max_group - 1 + GT_T - 1) / GT_T; return (int)(reach < nt - 1 ? reach : nt - 1); }
 // the workspace of the symmetric argmax: `slots` slots of a (value, index) per padded row.  The full walk has nt + 1, the banded 2 W + 2
@@ -34,10 +36,11 @@ inline size_t gt_sym_workspace_bytes(int nt, int slots) { return (size_t)slots *
 // SD_ROWS_ONLY    no workspace, no rule of its own: sd_ahc_merge_f32, sd_whiten_apply_f64
 // SD_ROWS_LABELS  no workspace; k labels, named in the first message: sd_label_centroids_f32
 // SD_ROWS_SYM     the symmetric argmax over every tile: sd_ahc_nearest_f32, sd_hdb_outgoing_f32
-// SD_ROWS_BAND    ... over a band; k is max_group: sd_ahc_nearest_grouped_f32
+// SD_ROWS_BAND    ... over a band; k is max_group: sd_ahc_nearest_grouped_f32, sd_hdb_outgoing_grouped_f32
 // SD_ROWS_CORE    the k best of every row: sd_hdb_core_f32
 // SD_ROWS_WHITEN  block partials of the f64 statistics: sd_whiten_stats_f64
-enum SdRowsKind { SD_ROWS_ONLY, SD_ROWS_LABELS, SD_ROWS_SYM, SD_ROWS_BAND, SD_ROWS_CORE, SD_ROWS_WHITEN };
+// SD_ROWS_BAND_CORE  the k best of every row over a band; k and max_group: sd_hdb_core_grouped_f32 (sd_hdb_outgoing_grouped_f32 is _BAND)
+enum SdRowsKind { SD_ROWS_ONLY, SD_ROWS_LABELS, SD_ROWS_SYM, SD_ROWS_BAND, SD_ROWS_CORE, SD_ROWS_WHITEN, SD_ROWS_BAND_CORE };
 struct SdRowsCall {
   const char *entry, *operand;      // the name in front of every message; what the alignment message calls the rows: "sums", "rows", "x"
   int kind, n, d;
@@ -46,6 +49,7 @@ struct SdRowsCall {
   struct { const char* name; long v; } more[2];       // further leading dimensions (name null: none); they stand in the first message
   bool any_null, rows_misaligned, ws_misaligned;      // what the entry read off its pointers
   size_t ws_bytes;
+  int max_group;                    // of SD_ROWS_BAND_CORE, whose k is k
 };
 
 // the bytes a call of supported shape needs (0: the entry has no workspace)
@@ -53,6 +57,7 @@ inline size_t sd_rows_need(const SdRowsCall& c) {
   const int nt = gt_tiles(c.n);
   if (c.kind == SD_ROWS_SYM || c.kind == SD_ROWS_BAND) return gt_sym_workspace_bytes(nt, c.kind == SD_ROWS_SYM ? nt + 1 : 2 * ag_band(nt, c.k) + 2);
   if (c.kind == SD_ROWS_CORE) return (size_t)hd_chunks(nt) * (size_t)nt * GT_T * (size_t)c.k * sizeof(float);
+  if (c.kind == SD_ROWS_BAND_CORE) return (size_t)hd_band_chunks(ag_band(nt, c.max_group)) * (size_t)nt * GT_T * (size_t)c.k * sizeof(float);
   if (c.kind != SD_ROWS_WHITEN) return 0;
   const size_t T = (size_t)dg_tiles(c.d);
   return (size_t)dg_blocks(c.n) * (16 * T + 256 * (T * (T + 1) / 2)) * sizeof(double);
@@ -61,7 +66,7 @@ inline size_t sd_rows_need(const SdRowsCall& c) {
 constexpr size_t SD_ROWS_WHY = 192;
 #define SD_ROWS_NEED(code, cond, ...) do { if (!(cond)) { snprintf(why, SD_ROWS_WHY, __VA_ARGS__); return code; } } while (0)
 
-// Every refusal of the eight entries, in the order the entries have always made them: the supported range (the rules on the numbers
+// Every refusal of the ten entries, in the order the entries have always made them: the supported range (the rules on the numbers
 // alone; `numbers_only` stops after them), the pointers, the rows' alignment and, for an entry with a workspace, its alignment, the grid
 // limit and its size.  SD_OK, or the status code with the text in why[SD_ROWS_WHY].
 inline int sd_rows_check(const SdRowsCall& c, char* why, bool numbers_only = false) {
@@ -79,6 +84,11 @@ inline int sd_rows_check(const SdRowsCall& c, char* why, bool numbers_only = fal
   if (c.kind == SD_ROWS_CORE) SD_ROWS_NEED(SD_ERR_UNSUPPORTED, c.k <= HD_MAX_K, "%s: k=%d, at most %d neighbours are supported", c.entry, c.k, HD_MAX_K);
   if (c.kind == SD_ROWS_CORE) SD_ROWS_NEED(SD_ERR_ARG, c.k >= 1 && c.k <= c.n - 1, "%s: k=%d must lie in 1 .. n - 1 (n=%d)", c.entry, c.k, c.n);
   if (c.kind == SD_ROWS_BAND) SD_ROWS_NEED(SD_ERR_ARG, c.k > 0, "%s: max_group=%d", c.entry, c.k);
+  if (c.kind == SD_ROWS_BAND_CORE) {    // no k <= n - 1 rule: a row with fewer than k others in its group gets -inf
+    SD_ROWS_NEED(SD_ERR_UNSUPPORTED, c.k <= HD_MAX_K, "%s: k=%d, at most %d neighbours are supported", c.entry, c.k, HD_MAX_K);
+    SD_ROWS_NEED(SD_ERR_ARG, c.k >= 1, "%s: k=%d must be at least 1", c.entry, c.k);
+    SD_ROWS_NEED(SD_ERR_ARG, c.max_group > 0, "%s: max_group=%d", c.entry, c.max_group);
+  }
   if (labels) SD_ROWS_NEED(SD_ERR_UNSUPPORTED, c.k <= DG_MAX_K, "%s: k=%d, at most %d labels are supported", c.entry, c.k, DG_MAX_K);
   if (numbers_only) return SD_OK;
   SD_ROWS_NEED(SD_ERR_ARG, !c.any_null, "%s: null pointer", c.entry);
@@ -86,13 +96,14 @@ inline int sd_rows_check(const SdRowsCall& c, char* why, bool numbers_only = fal
   if (c.kind < SD_ROWS_SYM) return SD_OK;       // no workspace
   SD_ROWS_NEED(SD_ERR_ARG, !c.ws_misaligned, "%s: workspace is not 16-byte aligned", c.entry);
   const int nt = gt_tiles(c.n);
-  if (c.kind == SD_ROWS_SYM || c.kind == SD_ROWS_CORE)
+  if (c.kind == SD_ROWS_SYM || c.kind == SD_ROWS_CORE || c.kind == SD_ROWS_BAND_CORE)
     SD_ROWS_NEED(SD_ERR_UNSUPPORTED, nt <= GT_MAX_TILES, "%s: n=%d, at most %d rows are supported", c.entry, c.n, GT_MAX_TILES * GT_T);
   if (c.kind == SD_ROWS_BAND)
     SD_ROWS_NEED(SD_ERR_UNSUPPORTED, ag_band(nt, c.k) < GT_MAX_TILES, "%s: max_group=%d, a group of at most %d rows is supported", c.entry, c.k, (GT_MAX_TILES - 1) * GT_T);
   const size_t need = sd_rows_need(c);
   char k[32] = "";
   if (c.kind == SD_ROWS_BAND || c.kind == SD_ROWS_CORE) snprintf(k, sizeof(k), c.kind == SD_ROWS_BAND ? " max_group=%d" : " k=%d", c.k);
+  if (c.kind == SD_ROWS_BAND_CORE) snprintf(k, sizeof(k), " k=%d max_group=%d", c.k, c.max_group);
   SD_ROWS_NEED(SD_ERR_WORKSPACE, c.ws_bytes >= need, "%s: workspace of %zu bytes, n=%d d=%d%s needs %zu", c.entry, c.ws_bytes, c.n, c.d, k, need);
   return SD_OK;
 }
@@ -100,8 +111,9 @@ inline int sd_rows_check(const SdRowsCall& c, char* why, bool numbers_only = fal
 
 // *_workspace_bytes(n, d[, k | max_group]): the need of a call whose numbers the check accepts, 0 for every other one.  A size function
 // has no leading dimension; d stands in.
-inline size_t sd_rows_workspace_bytes(int kind, int n, int d, int min_n, int max_d, int k = 0) {
-  const SdRowsCall c = {"", "", kind, n, d, d, min_n, max_d, k};
+inline size_t sd_rows_workspace_bytes(int kind, int n, int d, int min_n, int max_d, int k = 0, int max_group = 0) {
+  SdRowsCall c = {"", "", kind, n, d, d, min_n, max_d, k};
+  c.max_group = max_group;
   char why[SD_ROWS_WHY];
   return sd_rows_check(c, why, true) == SD_OK ? sd_rows_need(c) : 0;
 }

@@ -30,6 +30,10 @@ The operator is injectable (`operator=`): an object with `device`, `normalise(X)
 over torch tensors.  `DeviceRows` is the product one; the tests run the same driver on the CPU against a numpy operator.  There is no
 implicit CPU route: without an operator a host tensor raises the product path's RuntimeError.
 
+Many recordings at once: `hdbscan_rows_groups` (one grouped core pass, one Boruvka loop over the rows of all recordings; an operator
+for it also has `core_grouped(rows, k, group, max_group) -> (core, bad)` and `outgoing_grouped(rows, core, comp, group, max_group) ->
+(nn, best, bad)`), `HdbscanGpuClusterer.fit_predict_many`, `cluster.cluster_hdbscan_two_stage_many`, `anti_stick_diarize.diarize_many`.
+
 Two differences from the host route
 * the host works on f64 distances (of f32 or f64 rows); here a weight is an f32 dot product of f32 unit rows, about 1e-7 away;
 * equal partitions are a property of inputs without ties among the weights the tree compares, not a guarantee.  Near-ties (two
@@ -76,27 +80,48 @@ class DeviceRows(DeviceRoute):
     def outgoing(self, rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor):
         return ops.hdb_outgoing(rows, core, comp, ws=self.ws)
 
+    def core_grouped(self, rows: torch.Tensor, k: int, group: torch.Tensor, max_group: int):
+        return ops.hdb_core_grouped(rows, k, group, max_group, ws=self.ws)
+
+    def outgoing_grouped(self, rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, group: torch.Tensor, max_group: int):
+        return ops.hdb_outgoing_grouped(rows, core, comp, group, max_group, ws=self.ws)
+
 
 def _by_lowest_member(comp: np.ndarray) -> np.ndarray:
     """The same partition with ids 0, 1, ... in the order of each component's lowest row."""
+    comp = comp.reshape(-1)
+    if comp.size and comp.min() >= 0 and comp.max() < 4 * comp.size:      # dense ids (what connected_components hands out): no sort of the rows
+        first = np.full(int(comp.max()) + 1, comp.size, dtype=np.int64)
+        np.minimum.at(first, comp, np.arange(comp.size, dtype=np.int64))
+        present = np.flatnonzero(first < comp.size)
+        rank = np.empty(first.size, dtype=np.int64)
+        rank[present[np.argsort(first[present], kind="stable")]] = np.arange(present.size)
+        return rank[comp]
     _, first, inverse = np.unique(comp, return_index=True, return_inverse=True)
     rank = np.empty(first.size, dtype=np.int64)
     rank[np.argsort(first, kind="stable")] = np.arange(first.size)
     return rank[inverse.reshape(-1)]
 
 
-def _component_edges(comp: np.ndarray, nn: np.ndarray, best: np.ndarray):
+def _component_edges(comp: np.ndarray, nn: np.ndarray, best: np.ndarray, rows: np.ndarray | None = None):
     """The edge each component keeps: the first under (best descending, min(i, nn) ascending, max(i, nn) ascending); an edge two
-    components both chose is kept once -> (lo, hi, weight)."""
-    i = np.arange(comp.size, dtype=np.int64)
-    nn = nn.astype(np.int64)
-    lo, hi = np.minimum(i, nn), np.maximum(i, nn)
-    order = np.lexsort((hi, lo, -best, comp))                      # the last key is the primary one
-    c_sorted = comp[order]
-    first = order[np.concatenate(([True], c_sorted[1:] != c_sorted[:-1]))]
-    _, keep = np.unique(lo[first] * comp.size + hi[first], return_index=True)
-    first = first[keep]
-    return lo[first], hi[first], best[first]
+    components both chose is kept once -> (lo, hi, weight), in ascending (lo, hi).  `comp` holds ids in [0, number of components).
+    `rows`: the rows that have an edge at all (the grouped driver: a row whose component is its whole recording has none); every row
+    when None.  Two reductions per component instead of a sort of all rows: the heaviest weight, then the lowest (lo, hi) among the
+    rows that attain it."""
+    n = comp.size
+    i = np.arange(n, dtype=np.int64) if rows is None else rows.astype(np.int64)
+    c, w = comp[i], best[i]
+    j = nn[i].astype(np.int64)
+    key = np.minimum(i, j) * n + np.maximum(i, j)
+    top = np.full(int(c.max()) + 1 if c.size else 0, -np.inf, dtype=best.dtype)
+    np.maximum.at(top, c, w)
+    at = np.flatnonzero(w == top[c])                               # one row per component unless weights tie
+    lowest = np.full(top.size, np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(lowest, c[at], key[at])
+    at = at[key[at] == lowest[c[at]]]                              # exactly one row per component: an edge leaves a component at one of its ends
+    key, keep = np.unique(key[at], return_index=True)
+    return key // n, key % n, w[at[keep]]
 
 
 def spanning_edges(rows: torch.Tensor, core: torch.Tensor, operator, info: dict | None = None):
@@ -189,6 +214,164 @@ def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, a
     return (labels, info) if return_info else labels
 
 
+def _labels_of_tree(lo, hi, w, n, min_cluster_size, allow_single_cluster, metric, sk):
+    """Labels of the n rows whose maximum spanning tree of w is (lo, hi, w), by scikit-learn's routines -> (labels, the tree's f64
+    weight): steps 4 and 5 of the module's list."""
+    MST_edge_dtype, process_mst, tree_to_labels = sk
+    w = w.astype(np.float64)
+    dist = np.sqrt(np.maximum(0.0, 2.0 - 2.0 * w)) if metric == "euclidean" else np.maximum(0.0, 1.0 - w)
+    mst = np.empty(n - 1, dtype=MST_edge_dtype)
+    mst["current_node"], mst["next_node"], mst["distance"] = lo, hi, dist
+    labels = tree_to_labels(process_mst(mst), min_cluster_size, "eom", bool(allow_single_cluster), 0.0, None)[0]
+    return np.asarray(labels).astype(int), float(dist.sum())
+
+
+def _shared_tiles(group: np.ndarray):
+    """(tiles on the diagonal, tiles above it whose row block and column block share a group) of the 128 x 128 tiling of the rows: what
+    the grouped passes do not skip.  The outgoing pass computes the first plus the second, the core pass the first plus twice the second."""
+    T = -(-group.size // 128)
+    first, last = group[::128], group[np.minimum(np.arange(T) * 128 + 127, group.size - 1)]
+    above = np.searchsorted(first, last, side="right") - (np.arange(T) + 1)             # the J > I with group[first row of J] == group[last row of I]
+    return T, int(np.maximum(above, 0).sum())
+
+
+def spanning_edges_groups(rows: torch.Tensor, core: torch.Tensor, sizes, operator, info: dict | None = None, core_bad=None):
+    """`spanning_edges` for many recordings in one Boruvka loop: rows [N, d] holds the rows of all recordings one after another, `sizes`
+    the rows of each -> a list with one (lo, hi, w) per recording, indices counted from the recording's first row: exactly the edge list
+    `spanning_edges` builds for that recording alone (the module's docstring has the argument).  One `operator.outgoing_grouped` pass
+    and one host read per round; `bad` (and `core_bad`, the verdict of the grouped core pass, in the first round) comes back in the
+    same read."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    sizes = np.asarray(sizes, dtype=np.int64)
+    N = int(sizes.sum())
+    dev = operator.device
+    max_group = int(sizes.max(initial=0))
+    group_h = np.repeat(np.arange(sizes.size, dtype=np.int32), sizes)
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    size_of_row = sizes[group_h]
+    group = torch.from_numpy(group_h).to(dev)
+    comp = np.arange(N, dtype=np.int64)
+    n_comp, n_groups = N, int((sizes > 0).sum())
+    los, his, ws = [], [], []
+    max_rounds = max(1, math.ceil(math.log2(max(max_group, 1))))
+    rounds = 0
+    while n_comp > n_groups:
+        assert rounds < max_rounds, f"{rounds} Boruvka rounds over recordings of at most {max_group} rows: the weights are not symmetric"
+        nn, best, bad = operator.outgoing_grouped(rows, core, torch.from_numpy(comp.astype(np.int32)).to(dev), group, max_group)
+        parts = [nn, best.view(torch.int32), bad.reshape(1)] + ([core_bad.reshape(1)] if core_bad is not None else [])
+        got = torch.cat(parts).cpu().numpy()                       # the host synchronisation of the round
+        nn, best, broken = got[:N], got[N:2 * N].view(np.float32), bool(got[2 * N:].any())
+        core_bad = None
+        if broken:
+            raise RuntimeError(f"grouped pass over {N} rows: `group` decreases or a group exceeds max_group={max_group}")
+        has = np.flatnonzero(nn >= 0)                              # a row whose component is its whole recording has no edge and is left out
+        whole = np.bincount(comp, minlength=n_comp)[comp] == size_of_row      # rows whose component is their whole recording
+        if not np.array_equal(nn < 0, whole):
+            raise RuntimeError("a row has no outgoing edge although its recording is not one component yet, or has one although it "
+                               "is: the operator's group or component mask is wrong")
+        lo, hi, w = _component_edges(comp, nn, best, has)
+        graph = coo_matrix((np.ones(lo.size, dtype=np.int8), (comp[lo], comp[hi])), shape=(n_comp, n_comp))
+        n_next, merged = connected_components(graph, directed=False)
+        assert n_comp - n_next == lo.size, "the chosen edges close a cycle: the weights are not symmetric"
+        comp = _by_lowest_member(merged[comp])
+        n_comp = n_next
+        rounds += 1
+        los.append(lo), his.append(hi), ws.append(w)
+        if info is not None:
+            info["rounds"] = rounds
+            info["components_per_round"].append(int(n_comp))
+    if not los:
+        los, his, ws = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+    lo, hi, w = (np.concatenate(a) for a in (los, his, ws))
+    rec = group_h[lo].astype(np.int64)
+    assert np.array_equal(rec, group_h[hi]), "an edge joins two recordings: the operator's group mask is wrong"
+    order = np.argsort(rec, kind="stable")                          # within a recording the order stays (round, lo, hi)
+    lo, hi, w, rec = lo[order], hi[order], w[order], rec[order]
+    cuts = np.searchsorted(rec, np.arange(sizes.size + 1))
+    assert np.array_equal(np.diff(cuts), np.maximum(sizes - 1, 0)), "a recording's edges do not span it"
+    return [(lo[a:b] - off, hi[a:b] - off, w[a:b]) for a, b, off in zip(cuts[:-1], cuts[1:], offsets[:-1])]
+
+
+def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | None = None, allow_single_cluster: bool = True,
+                        metric: str = "euclidean", *, operator=None, return_info: bool = False):
+    """`hdbscan_rows` for many recordings in one driver: X [N, D] holds the rows of all recordings one after another, `sizes` the number
+    of rows of each (0 and 1 are legal and return as the host glue does) -> a list with one label array per recording, equal to
+    `hdbscan_rows` on that recording's rows alone, exactly.
+
+    A row's core value and every tree edge look only inside the row's own recording, so ONE grouped core pass
+    (`operator.core_grouped`, `sd_hdb_core_grouped_f32`) and ONE Boruvka loop (`operator.outgoing_grouped`,
+    `sd_hdb_outgoing_grouped_f32`: one pass and one host read per round) serve all recordings; the rounds are the maximum over the
+    recordings, at most ceil(log2(max(sizes))) (asserted), not their sum.  Why the labels are equal with no condition on ties: per
+    recording the grouped entries return the `core`, the `nn` (minus the recording's first row) and the bits of `best` of the
+    ungrouped ones on its rows alone (include/sd_hip_hdbscan.h); by induction over the rounds every recording's components are those
+    of its lone run, a round keeps the same edge per component (the order (best, lo, hi) does not change when every index moves by
+    the same offset) and lists them in ascending (lo, hi); so a recording's edges, taken out in (round, lo, hi) order with its offset
+    subtracted, ARE the array `spanning_edges` builds for it alone, and the same array goes into the same scikit-learn routines.
+
+    A non-finite row, a row that is not a unit row under "euclidean", and `min_samples` above a recording's size (sizes >= 2) raise
+    ValueError naming the recording before anything is launched.  `bad` of the kernels (a broken promise about `group`) raises
+    RuntimeError.  info = {"rounds", "components_per_round" (over all rows), "gram_tiles": the 128 x 128 tiles the passes did not skip,
+    "gram_tiles_per_pass", "mst_weight": per recording}; the tile counts are computed on the host and only when info is asked for."""
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError(f"hdbscan_rows_groups clusters rows under metric 'euclidean' or 'cosine'; metric={metric!r} has no rows to work on")
+    sizes = [int(s) for s in sizes]
+    info = {"rounds": 0, "components_per_round": [], "gram_tiles": 0, "gram_tiles_per_pass": [], "mst_weight": [0.0] * len(sizes)}
+    operator = operator_for(X, operator, DeviceRows)
+    X = torch.as_tensor(X)
+    if X.dim() != 2:
+        raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
+    if int(min_cluster_size) < 2:
+        raise ValueError(f"min_cluster_size must be at least 2, got {min_cluster_size}")
+    min_cluster_size = int(min_cluster_size)
+    min_samples = min_cluster_size if min_samples is None else int(min_samples)
+    if min_samples < 1:
+        raise ValueError(f"min_samples must be at least 1, got {min_samples}")
+    N = X.shape[0]
+    if min(sizes, default=0) < 0 or sum(sizes) != N:
+        raise ValueError(f"sizes {sizes} do not add up to the {N} rows")
+    labels = [np.zeros(s, dtype=int) for s in sizes]                # what sizes 0 and 1 keep
+    if max(sizes, default=0) <= 1:
+        return (labels, info) if return_info else labels
+    for g, s in enumerate(sizes):
+        if s >= 2 and min_samples > s:
+            raise ValueError(f"recording {g}: min_samples ({min_samples}) must be at most the number of rows ({s})")
+    if X.shape[1] == 0:
+        raise ValueError("rows must be finite and have at least one column")
+    group_h = np.repeat(np.arange(len(sizes)), sizes)
+    finite = torch.isfinite(X).all(dim=1)
+    if not bool(finite.all()):
+        row = int(torch.nonzero(~finite)[0])
+        raise ValueError(f"recording {int(group_h[row])}: rows must be finite (row {row} of all rows is not)")
+    if metric == "euclidean":
+        off = (torch.linalg.vector_norm(X.double(), dim=1) - 1.0).abs()
+        in_play = torch.from_numpy(np.asarray(sizes)[group_h] >= 2).to(off.device)     # a lone row is never looked at, as in hdbscan_rows
+        off = torch.where(in_play, off, torch.zeros_like(off))
+        if float(off.max()) > 1e-3:
+            row = int(off.argmax())
+            raise ValueError(f"recording {int(group_h[row])}: metric 'euclidean' takes unit rows (a norm is {float(off[row]):.3g} away "
+                             "from 1); pass metric='cosine' for other rows")
+    sk = _sklearn_tree()
+    dev = operator.device
+    rows = operator.normalise(X.to(dev).float())
+    max_group = max(sizes)
+    core_bad = None
+    if min_samples == 1:
+        core = torch.full((N,), float("inf"), dtype=torch.float32, device=dev)
+    else:
+        group = torch.from_numpy(group_h.astype(np.int32)).to(dev)
+        core, core_bad = operator.core_grouped(rows, min_samples - 1, group, max_group)
+    edges = spanning_edges_groups(rows, core, sizes, operator, info, core_bad)
+    for g, (s, (lo, hi, w)) in enumerate(zip(sizes, edges)):
+        if s >= 2:
+            labels[g], info["mst_weight"][g] = _labels_of_tree(lo, hi, w, s, min_cluster_size, allow_single_cluster, metric, sk)
+    if return_info:
+        diagonal, above = _shared_tiles(group_h)
+        info["gram_tiles_per_pass"] = ([diagonal + 2 * above] if min_samples > 1 else []) + [diagonal + above] * info["rounds"]
+        info["gram_tiles"] = sum(info["gram_tiles_per_pass"])
+    return (labels, info) if return_info else labels
+
+
 class HdbscanGpuClusterer:
     """A scikit-learn `HDBSCAN` stand-in on the device route, for the `clusterer_factory=` argument of
     `cluster.cluster_hdbscan_two_stage`: `fit_predict` takes L2-normalised rows (metric "euclidean") or any rows (metric "cosine").
@@ -214,3 +397,18 @@ class HdbscanGpuClusterer:
         if self.operator is None:
             X = upload_rows(X, "HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
         return hdbscan_rows(X, self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric, operator=self.operator)
+
+    def fit_predict_many(self, list_of_X) -> list:
+        """`fit_predict` of every matrix of the list (all of one width) through ONE grouped driver (`hdbscan_rows_groups`) -> a list of
+        label arrays, each equal to `fit_predict` on its matrix alone."""
+        mats = [np.ascontiguousarray(X, dtype=np.float32) for X in list_of_X]
+        if not mats:
+            return []
+        widths = {m.shape[1] for m in mats if m.ndim == 2}
+        if any(m.ndim != 2 for m in mats) or len(widths) != 1:
+            raise ValueError(f"fit_predict_many takes matrices [n, D] of one width, got {[m.shape for m in mats]}")
+        X = torch.from_numpy(np.concatenate(mats))
+        if self.operator is None:
+            X = upload_rows(X, "HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
+        return hdbscan_rows_groups(X, [len(m) for m in mats], self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric,
+                                   operator=self.operator)

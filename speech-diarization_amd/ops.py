@@ -640,6 +640,51 @@ def hdb_outgoing(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, ws:
     return nn, best
 
 
+def _group_vector(group: torch.Tensor, n: int) -> None:
+    if group.dtype != torch.int32 or group.shape != (n,) or not group.is_contiguous():
+        raise ValueError(f"group must be a contiguous {torch.int32} vector of {n} entries, got {tuple(group.shape)} {group.dtype}")
+
+
+def hdb_core_grouped(rows: torch.Tensor, k: int, group: torch.Tensor, max_group: int, ws: Workspace | torch.Tensor | None = None):
+    """`hdb_core` over the rows of many recordings at once: group int32 [n], non-decreasing, names the recording of every row, and only
+    a row of the same recording counts; `max_group` bounds the rows of any one recording -> (core f32 [n], -inf for a row with fewer
+    than k others in its recording; bad int32 [1], still on the device: non-zero when `group` decreases somewhere or a group exceeds
+    `max_group`, and core means nothing then).  1 <= k <= 16.  A recording's values are bit for bit those of `hdb_core` on its rows
+    alone.  `ws`: a `Workspace`, or a uint8 tensor of at least sd_hdb_core_grouped_workspace_bytes(n, d, k, max_group)."""
+    _need_cuda(rows, group)
+    rows, n, d, ld = rows4(rows)
+    _group_vector(group, n)
+    k, max_group = int(k), int(max_group)
+    core = torch.empty((n,), dtype=torch.float32, device=rows.device)
+    bad = torch.empty((1,), dtype=torch.int32, device=rows.device)
+    ws = _workspace(ws, int(N.load().sd_hdb_core_grouped_workspace_bytes(n, d, k, max_group)), rows.device)
+    launch("sd_hdb_core_grouped_f32", rows, rows.data_ptr(), ld, n, d, k, group.data_ptr(), max_group, core.data_ptr(), bad.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
+    return core, bad
+
+
+def hdb_outgoing_grouped(rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, group: torch.Tensor, max_group: int,
+                         ws: Workspace | torch.Tensor | None = None):
+    """`hdb_outgoing` over the rows of many recordings at once (group, max_group and bad as for `hdb_core_grouped`): the heaviest edge
+    into another component of the row's OWN recording -> (nn int32 [n], indices into all n rows, -1 for a row whose component is its
+    whole recording; best f32 [n]; bad int32 [1], still on the device).  A recording's weights are bit for bit those of `hdb_outgoing`
+    on its rows alone.  `ws`: a `Workspace`, or a uint8 tensor of at least sd_hdb_outgoing_grouped_workspace_bytes(n, d, max_group)."""
+    _need_cuda(rows, core, comp, group)
+    rows, n, d, ld = rows4(rows)
+    for name, t, dt in (("core", core, torch.float32), ("comp", comp, torch.int32)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    _group_vector(group, n)
+    max_group = int(max_group)
+    nn = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    best = torch.empty((n,), dtype=torch.float32, device=rows.device)
+    bad = torch.empty((1,), dtype=torch.int32, device=rows.device)
+    ws = _workspace(ws, int(N.load().sd_hdb_outgoing_grouped_workspace_bytes(n, d, max_group)), rows.device)
+    launch("sd_hdb_outgoing_grouped_f32", rows, rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), group.data_ptr(), max_group,
+           nn.data_ptr(), best.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return nn, best, bad
+
+
 # ----------------------------------------------------------------------------- f64 whitening and cluster centres (include/sd_hip_diag.h)
 
 def whiten_stats(rows: torch.Tensor, ws: Workspace | torch.Tensor | None = None):
