@@ -203,6 +203,16 @@ HDBSCAN_PROTOTYPES = {
     "sd_hdb_outgoing_grouped_f32": (_I, [_P, C.c_long, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_tree.h: from a spanning tree's edges to HDBSCAN's labels, same shared object, a table and a version of their own.
+# The table is named TREE_ENTRIES, not *_PROTOTYPES: the six tables of that name are a closed set (ops._ENTRIES is their union, and
+# tests/test_binding_rules.py counts them); `ops.launch` looks a name up in this table beside them
+SD_TREE_ABI_VERSION = 1
+TREE_ENTRIES = {
+    "sd_tree_abi_version": (_I, []),
+    "sd_tree_labels_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sd_tree_labels_grouped": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+}
+
 # include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own
 SD_DIAG_ABI_VERSION = 1
 _D = C.c_double
@@ -254,6 +264,7 @@ def load() -> C.CDLL:
                 ("sd_hip_spectral.h", SPECTRAL_PROTOTYPES, "sd_spectral_abi_version", SD_SPECTRAL_ABI_VERSION, "spectral "),
                 ("sd_hip_ahc.h", AHC_PROTOTYPES, "sd_ahc_abi_version", SD_AHC_ABI_VERSION, "AHC "),
                 ("sd_hip_hdbscan.h", HDBSCAN_PROTOTYPES, "sd_hdbscan_abi_version", SD_HDBSCAN_ABI_VERSION, "HDBSCAN "),
+                ("sd_hip_tree.h", TREE_ENTRIES, "sd_tree_abi_version", SD_TREE_ABI_VERSION, "tree "),
                 ("sd_hip_diag.h", DIAG_PROTOTYPES, "sd_diag_abi_version", SD_DIAG_ABI_VERSION, "diag "),
                 ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
             missing = [name for name in table if not hasattr(lib, name)]

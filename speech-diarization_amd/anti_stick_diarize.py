@@ -395,8 +395,10 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     `clusterer` selects what sits inside the reference's `cluster_hdbscan_two_stage(embs, min_cluster_size=2)`
     [REF :536]: "hdbscan_two_stage" (default: the two-stage glue over `cluster.default_hdbscan_factory`),
     "ahc" (the same glue with average-linkage AHC cut at `cluster_cos` injected as the clusterer), "hdbscan_gpu" (the same glue
-    over `hdbscan_gpu.HdbscanGpuClusterer.factory()`: HDBSCAN from the rows on the device, no N x N matrix), "ahc_affinity"
-    (single-stage AHC on the GPU cosine affinity), or a `clusterer_factory(**kwargs)` callable.
+    over `hdbscan_gpu.HdbscanGpuClusterer.factory()`: HDBSCAN from the rows on the device, no N x N matrix), "hdbscan_device"
+    (the same over `HdbscanGpuClusterer.factory(labelling="device")`: the labels of both stages come from the device as well, and
+    scikit-learn is not called), "ahc_affinity" (single-stage AHC on the GPU cosine affinity), or a `clusterer_factory(**kwargs)`
+    callable.
 
     `packed_embeddings=True` embeds every segment as if alone (`embed_segments(..., packed=True)`) instead of in the reference's
     zero-padded batches of 32 (the default)."""
@@ -412,11 +414,15 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
         if clusterer == "hdbscan_gpu":
             from . import hdbscan_gpu
             factory = hdbscan_gpu.HdbscanGpuClusterer.factory()
+        elif clusterer == "hdbscan_device":
+            from . import hdbscan_gpu
+            factory = hdbscan_gpu.HdbscanGpuClusterer.factory(labelling="device")
         else:
             factory = (None if clusterer == "hdbscan_two_stage" else
                        cluster.AhcClusterer.factory(cluster_cos) if clusterer == "ahc" else clusterer)
         if factory is not None and not callable(factory):
-            raise ValueError(f"clusterer must be 'hdbscan_two_stage', 'ahc', 'hdbscan_gpu', 'ahc_affinity' or a factory, got {clusterer!r}")
+            raise ValueError(f"clusterer must be 'hdbscan_two_stage', 'ahc', 'hdbscan_gpu', 'hdbscan_device', 'ahc_affinity' or a factory, "
+                             f"got {clusterer!r}")
         raw = cluster_hdbscan_two_stage(embs, min_cluster_size=2, clusterer_factory=factory)
     return _diarize_tail(front, raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
                          packed_embeddings)
@@ -465,22 +471,26 @@ def diarize_many(wav_paths, sr: int = 16000, target_lufs: float = -18.0, vad_on_
                  merge_max_gap_s: float = 0.5, merge_max_speech_s: float = 30.0, merge_mincos: float = 0.8, reseg: int = 1, *,
                  cluster_cos: float = 0.70, encode: Encoder | None = None, vad_segments: Callable | None = None,
                  compat_reference_bugs: bool = False, clusterer: str = "hdbscan_gpu", packed_embeddings: bool = False) -> list[list[Segment]]:
-    """`diarize(..., clusterer="hdbscan_gpu")` for a list of recordings (each a path, an `(array, sample_rate)` tuple or a conditioned
+    """`diarize(..., clusterer="hdbscan_gpu")` (or "hdbscan_device") for a list of recordings (each a path, an `(array, sample_rate)` tuple or a conditioned
     array, as for `diarize`) -> the list of their segment lists, each equal to `diarize` on that recording alone.
 
     Per recording the front of `diarize` (load, VAD, SCD split, embed); then ONE `cluster_hdbscan_two_stage_many` over the embeddings
     of all recordings (`hdbscan_gpu.hdbscan_rows_groups`: one grouped core pass and one Boruvka loop for stage 1, one more for the
     centroids); then per recording the tail (relabel, conservative merge, re-embed, frame reassignment, merge_adjacent).  A recording
-    without speech gives [].  Only the "hdbscan_gpu" clusterer has a grouped driver; any other raises ValueError (`cluster_cos` is
-    accepted for the parameter list of `diarize` and not used by it).  The embedding launches are not shared across recordings."""
+    without speech gives [].  Only the "hdbscan_gpu" clusterer has a grouped driver ("hdbscan_device" is the same clusterer with
+    `labelling="device"`: each stage labels all recordings in one launch); any other raises ValueError (`cluster_cos` is accepted
+    for the parameter list of `diarize` and not used by it).  The embedding launches are not shared across recordings."""
     from . import cluster, hdbscan_gpu
-    if clusterer != "hdbscan_gpu":
-        raise ValueError(f"diarize_many clusters with 'hdbscan_gpu' alone (the clusterer that has a grouped driver), got {clusterer!r}")
+    if clusterer not in ("hdbscan_gpu", "hdbscan_device"):
+        raise ValueError("diarize_many clusters with 'hdbscan_gpu' alone (the clusterer that has a grouped driver; 'hdbscan_device' is the "
+                         f"same with its labels from the device), got {clusterer!r}")
+    make = hdbscan_gpu.HdbscanGpuClusterer.factory
+    factory = make() if clusterer == "hdbscan_gpu" else make(labelling="device")
     fronts = [_diarize_front(w, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
                              morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings) for w in wav_paths]
     live = [i for i, f in enumerate(fronts) if f is not None]
     raws = cluster.cluster_hdbscan_two_stage_many([fronts[i][4] for i in live], min_cluster_size=2,
-                                                  clusterer_factory=hdbscan_gpu.HdbscanGpuClusterer.factory())
+                                                  clusterer_factory=factory)
     out: list[list[Segment]] = [[] for _ in fronts]
     for i, raw in zip(live, raws):
         out[i] = _diarize_tail(fronts[i], raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
@@ -506,13 +516,14 @@ def main(wav_path: str, sr: int = 16000, target_lufs: float = -18.0, vad_thr: fl
 
 def cluster_hdbscan(embs: np.ndarray, min_cluster_size: int = 2, clusterer_factory=None, use_gpu: bool | str = False) -> np.ndarray:
     """[REF anti_stick_diarize.py:175-186]; the N x N cosine on the GPU when `use_gpu` is True.  `use_gpu="rows"`: the whole
-    clustering from the rows on the device (`hdbscan_gpu.hdbscan_rows`, metric "cosine"), no matrix and no `clusterer_factory`."""
+    clustering from the rows on the device (`hdbscan_gpu.hdbscan_rows`, metric "cosine"), no matrix and no `clusterer_factory`;
+    `use_gpu="rows_device"`: the same with `labelling="device"` (the labels come from the device too)."""
     from . import cluster
     if isinstance(use_gpu, str):
-        if use_gpu != "rows":
-            raise ValueError(f"use_gpu must be False, True or 'rows', got {use_gpu!r}")
+        if use_gpu not in ("rows", "rows_device"):
+            raise ValueError(f"use_gpu must be False, True or 'rows' ('rows_device' for device labels), got {use_gpu!r}")
         if clusterer_factory is not None:
-            raise ValueError("use_gpu='rows' is a clusterer of its own; it takes no clusterer_factory")
+            raise ValueError(f"use_gpu='rows' is a clusterer of its own; it takes no clusterer_factory (use_gpu={use_gpu!r})")
         from . import hdbscan_gpu
         from .device_rows import upload_rows
         embs = np.asarray(embs)
@@ -520,7 +531,8 @@ def cluster_hdbscan(embs: np.ndarray, min_cluster_size: int = 2, clusterer_facto
             return np.zeros(embs.shape[0], dtype=int)
         embs_norm = embs / (np.linalg.norm(embs, axis=1, keepdims=True) + 1e-8)
         rows = upload_rows(embs_norm, "use_gpu='rows' runs on the HIP path (a visible GPU); there is no CPU fallback")
-        return hdbscan_gpu.hdbscan_rows(rows, min_cluster_size, None, True, metric="cosine")
+        return hdbscan_gpu.hdbscan_rows(rows, min_cluster_size, None, True, metric="cosine",
+                                        labelling="device" if use_gpu == "rows_device" else "sklearn")
     aff = (lambda x: cosine_affinity(x, True)) if use_gpu else None
     return cluster.cluster_hdbscan(embs, min_cluster_size, clusterer_factory, affinity=aff)
 

@@ -24,11 +24,19 @@ The steps
 4. the edges as scikit-learn's `MST_edge_dtype` with f64 distances: "euclidean" sqrt(max(0, 2 - 2 w)), "cosine" max(0, 1 - w) (what
    `cluster.cluster_hdbscan` feeds its clusterer as a precomputed matrix);
 5. labels from `_process_mst` and `tree_to_labels(..., "eom", allow_single_cluster, 0.0, None)`, private functions of
-   scikit-learn 1.7.2 imported in `_sklearn_tree()` alone.
+   scikit-learn 1.7.2 imported in `_sklearn_tree()` alone (`labelling="sklearn"`, the default), or on the device
+   (`labelling="device"`: `operator.tree_labels`, `sd_tree_labels_grouped` of include/sd_hip_tree.h: the edges of all recordings go
+   up in one copy, one launch labels them with one workgroup per recording, one read brings `labels` and `bad` back, and
+   scikit-learn is not imported).  The device labels are scikit-learn's on the STABLY sorted edge list; where no two edges of a
+   recording have the same distance that is `_process_mst`'s own order and the two labellings are equal, and where distances tie
+   `_process_mst`'s unstable argsort is platform-dependent (the last paragraph below) and the stable order is what this route defines.
 
 The operator is injectable (`operator=`): an object with `device`, `normalise(X)`, `core(rows, k)` and `outgoing(rows, core, comp)`
-over torch tensors.  `DeviceRows` is the product one; the tests run the same driver on the CPU against a numpy operator.  There is no
-implicit CPU route: without an operator a host tensor raises the product path's RuntimeError.
+over torch tensors; optionally `tree_labels(lo, hi, dist, first_edge, max_edges, min_cluster_size, allow_single_cluster) ->
+(labels, bad)` (what `labelling="device"` calls: int32 edge ends counted from each recording's first row, f64 distances, int32
+first_edge [G + 1] -> int32 labels [E + G], the rows of recording g from first_edge[g] + g on, and int32 bad [G]).  `DeviceRows` is
+the product one; the tests run the same driver on the CPU against a numpy operator.  There is no implicit CPU route: without an
+operator a host tensor raises the product path's RuntimeError.
 
 Many recordings at once: `hdbscan_rows_groups` (one grouped core pass, one Boruvka loop over the rows of all recordings; an operator
 for it also has `core_grouped(rows, k, group, max_group) -> (core, bad)` and `outgoing_grouped(rows, core, comp, group, max_group) ->
@@ -85,6 +93,10 @@ class DeviceRows(DeviceRoute):
 
     def outgoing_grouped(self, rows: torch.Tensor, core: torch.Tensor, comp: torch.Tensor, group: torch.Tensor, max_group: int):
         return ops.hdb_outgoing_grouped(rows, core, comp, group, max_group, ws=self.ws)
+
+    def tree_labels(self, lo: torch.Tensor, hi: torch.Tensor, dist: torch.Tensor, first_edge: torch.Tensor, max_edges: int,
+                    min_cluster_size: int, allow_single_cluster: bool):
+        return ops.tree_labels_grouped(lo, hi, dist, first_edge, max_edges, min_cluster_size, allow_single_cluster, ws=self.ws)
 
 
 def _by_lowest_member(comp: np.ndarray) -> np.ndarray:
@@ -159,14 +171,56 @@ def spanning_edges(rows: torch.Tensor, core: torch.Tensor, operator, info: dict 
     return lo, hi, w
 
 
+LABELLINGS = ("sklearn", "device")
+
+
+def _check_labelling(labelling: str, operator) -> None:
+    if labelling not in LABELLINGS:
+        raise ValueError(f"labelling must be one of {LABELLINGS}, got {labelling!r}")
+    if labelling == "device" and not hasattr(operator, "tree_labels"):
+        raise TypeError(f"labelling='device' needs an operator with tree_labels(...); {type(operator).__name__} has none")
+
+
+def _tree_distances(w: np.ndarray, metric: str) -> np.ndarray:
+    """Step 4: the f64 distances of the tree's f32 weights."""
+    w = w.astype(np.float64)
+    return np.sqrt(np.maximum(0.0, 2.0 - 2.0 * w)) if metric == "euclidean" else np.maximum(0.0, 1.0 - w)
+
+
+def _labels_on_device(trees, min_cluster_size, allow_single_cluster, metric, operator, names=None):
+    """Step 5 on the device for the spanning trees [(lo, hi, w)] of recordings of two rows or more -> ([labels], [the tree's f64
+    weight]).  One upload (the distances, both ends and `first_edge` in one buffer), one `operator.tree_labels`, one read of labels and
+    `bad`; a recording whose `bad` is set raises RuntimeError naming it (`names`: what to call each, its position when None)."""
+    counts = np.array([len(w) for _, _, w in trees], dtype=np.int64)
+    E, G = int(counts.sum()), len(trees)
+    dists = [_tree_distances(w, metric) for _, _, w in trees]
+    buf = np.empty(4 * E + G + 1, dtype=np.int32)                  # f64 [E] | lo [E] | hi [E] | first_edge [G + 1]
+    buf[:2 * E].view(np.float64)[:] = np.concatenate(dists)
+    buf[2 * E:3 * E] = np.concatenate([lo for lo, _, _ in trees])
+    buf[3 * E:4 * E] = np.concatenate([hi for _, hi, _ in trees])
+    buf[4 * E:] = np.concatenate([[0], np.cumsum(counts)])
+    up = torch.from_numpy(buf).to(operator.device)
+    labels, bad = operator.tree_labels(up[2 * E:3 * E], up[3 * E:4 * E], up[:2 * E].view(torch.float64), up[4 * E:], int(counts.max()),
+                                       int(min_cluster_size), bool(allow_single_cluster))
+    got = torch.cat([labels, bad]).cpu().numpy()                   # the one read
+    labels, bad = got[:E + G], got[E + G:]
+    if bad.any():
+        g = int(np.flatnonzero(bad)[0])
+        raise RuntimeError(f"recording {g if names is None else names[g]}: its {int(counts[g])} edges are not a spanning tree of its "
+                           f"{int(counts[g]) + 1} rows with finite distances >= 0 (sd_tree_labels_grouped reported bad={int(bad[g])})")
+    starts = np.concatenate([[0], np.cumsum(counts)])[:-1] + np.arange(G)
+    return [labels[a:a + c + 1].astype(int) for a, c in zip(starts, counts)], [float(d.sum()) for d in dists]
+
+
 def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, allow_single_cluster: bool = True,
-                 metric: str = "euclidean", *, operator=None, return_info: bool = False):
+                 metric: str = "euclidean", *, operator=None, return_info: bool = False, labelling: str = "sklearn"):
     """`HDBSCAN(min_cluster_size, min_samples, allow_single_cluster, metric).fit_predict` of scikit-learn from the rows X [N, D]
     themselves -> labels int [N], -1 for noise.  metric "euclidean": X holds unit rows (what the reference's call sites pass; a row
     whose norm is not within 1e-3 of 1 raises ValueError: a zero row has no cosine equivalent of its Euclidean distance);
     metric "cosine": any rows, the result is that of the host clusterer on the precomputed matrix 1 - cosine_similarity(X).
     info = {"rounds": Boruvka rounds, "gram_rows": sum of n^2 over every pass (the core pass included), "components_per_round",
-    "mst_weight": the sum of the tree's f64 distances}.
+    "mst_weight": the sum of the tree's f64 distances}.  labelling: "sklearn" (scikit-learn's private routines on the host) or "device"
+    (`operator.tree_labels`; scikit-learn is not imported; the module's step 5).
 
     N = 0 and N = 1 return early as the host glue does.  min_samples > N, min_cluster_size < 2, a metric other than the two and a
     non-finite row raise ValueError before anything is launched."""
@@ -174,6 +228,7 @@ def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, a
     if metric not in ("euclidean", "cosine"):
         raise ValueError(f"hdbscan_rows clusters rows under metric 'euclidean' or 'cosine'; metric={metric!r} has no rows to work on")
     operator = operator_for(X, operator, DeviceRows)
+    _check_labelling(labelling, operator)
     X = torch.as_tensor(X)
     if X.dim() != 2:
         raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
@@ -195,7 +250,7 @@ def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, a
         off = float((torch.linalg.vector_norm(X.double(), dim=1) - 1.0).abs().max())
         if off > 1e-3:
             raise ValueError(f"metric 'euclidean' takes unit rows (a norm is {off:.3g} away from 1); pass metric='cosine' for other rows")
-    MST_edge_dtype, process_mst, tree_to_labels = _sklearn_tree()
+    sk = _sklearn_tree() if labelling == "sklearn" else None
     dev = operator.device
     rows = operator.normalise(X.to(dev).float())
     if min_samples == 1:
@@ -204,13 +259,10 @@ def hdbscan_rows(X, min_cluster_size: int = 2, min_samples: int | None = None, a
         core = operator.core(rows, min_samples - 1)
         info["gram_rows"] += N * N
     lo, hi, w = spanning_edges(rows, core, operator, info)
-    w = w.astype(np.float64)
-    dist = np.sqrt(np.maximum(0.0, 2.0 - 2.0 * w)) if metric == "euclidean" else np.maximum(0.0, 1.0 - w)
-    mst = np.empty(N - 1, dtype=MST_edge_dtype)
-    mst["current_node"], mst["next_node"], mst["distance"] = lo, hi, dist
-    info["mst_weight"] = float(dist.sum())
-    labels = tree_to_labels(process_mst(mst), min_cluster_size, "eom", bool(allow_single_cluster), 0.0, None)[0]
-    labels = np.asarray(labels).astype(int)
+    if labelling == "device":
+        (labels,), (info["mst_weight"],) = _labels_on_device([(lo, hi, w)], min_cluster_size, allow_single_cluster, metric, operator)
+    else:
+        labels, info["mst_weight"] = _labels_of_tree(lo, hi, w, N, min_cluster_size, allow_single_cluster, metric, sk)
     return (labels, info) if return_info else labels
 
 
@@ -218,8 +270,7 @@ def _labels_of_tree(lo, hi, w, n, min_cluster_size, allow_single_cluster, metric
     """Labels of the n rows whose maximum spanning tree of w is (lo, hi, w), by scikit-learn's routines -> (labels, the tree's f64
     weight): steps 4 and 5 of the module's list."""
     MST_edge_dtype, process_mst, tree_to_labels = sk
-    w = w.astype(np.float64)
-    dist = np.sqrt(np.maximum(0.0, 2.0 - 2.0 * w)) if metric == "euclidean" else np.maximum(0.0, 1.0 - w)
+    dist = _tree_distances(w, metric)
     mst = np.empty(n - 1, dtype=MST_edge_dtype)
     mst["current_node"], mst["next_node"], mst["distance"] = lo, hi, dist
     labels = tree_to_labels(process_mst(mst), min_cluster_size, "eom", bool(allow_single_cluster), 0.0, None)[0]
@@ -294,10 +345,11 @@ def spanning_edges_groups(rows: torch.Tensor, core: torch.Tensor, sizes, operato
 
 
 def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | None = None, allow_single_cluster: bool = True,
-                        metric: str = "euclidean", *, operator=None, return_info: bool = False):
+                        metric: str = "euclidean", *, operator=None, return_info: bool = False, labelling: str = "sklearn"):
     """`hdbscan_rows` for many recordings in one driver: X [N, D] holds the rows of all recordings one after another, `sizes` the number
     of rows of each (0 and 1 are legal and return as the host glue does) -> a list with one label array per recording, equal to
-    `hdbscan_rows` on that recording's rows alone, exactly.
+    `hdbscan_rows` on that recording's rows alone, exactly.  labelling as for `hdbscan_rows`; "device" labels ALL recordings in one
+    launch (one upload of the edges, one read of labels and `bad`; a recording whose `bad` is set raises RuntimeError naming it).
 
     A row's core value and every tree edge look only inside the row's own recording, so ONE grouped core pass
     (`operator.core_grouped`, `sd_hdb_core_grouped_f32`) and ONE Boruvka loop (`operator.outgoing_grouped`,
@@ -318,6 +370,7 @@ def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | 
     sizes = [int(s) for s in sizes]
     info = {"rounds": 0, "components_per_round": [], "gram_tiles": 0, "gram_tiles_per_pass": [], "mst_weight": [0.0] * len(sizes)}
     operator = operator_for(X, operator, DeviceRows)
+    _check_labelling(labelling, operator)
     X = torch.as_tensor(X)
     if X.dim() != 2:
         raise ValueError(f"rows must be a matrix [N, D], got {tuple(X.shape)}")
@@ -351,7 +404,7 @@ def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | 
             row = int(off.argmax())
             raise ValueError(f"recording {int(group_h[row])}: metric 'euclidean' takes unit rows (a norm is {float(off[row]):.3g} away "
                              "from 1); pass metric='cosine' for other rows")
-    sk = _sklearn_tree()
+    sk = _sklearn_tree() if labelling == "sklearn" else None
     dev = operator.device
     rows = operator.normalise(X.to(dev).float())
     max_group = max(sizes)
@@ -362,9 +415,15 @@ def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | 
         group = torch.from_numpy(group_h.astype(np.int32)).to(dev)
         core, core_bad = operator.core_grouped(rows, min_samples - 1, group, max_group)
     edges = spanning_edges_groups(rows, core, sizes, operator, info, core_bad)
-    for g, (s, (lo, hi, w)) in enumerate(zip(sizes, edges)):
-        if s >= 2:
-            labels[g], info["mst_weight"][g] = _labels_of_tree(lo, hi, w, s, min_cluster_size, allow_single_cluster, metric, sk)
+    if labelling == "device":
+        which = [g for g, s in enumerate(sizes) if s >= 2]
+        got, weights = _labels_on_device([edges[g] for g in which], min_cluster_size, allow_single_cluster, metric, operator, names=which)
+        for g, lab, weight in zip(which, got, weights):
+            labels[g], info["mst_weight"][g] = lab, weight
+    else:
+        for g, (s, (lo, hi, w)) in enumerate(zip(sizes, edges)):
+            if s >= 2:
+                labels[g], info["mst_weight"][g] = _labels_of_tree(lo, hi, w, s, min_cluster_size, allow_single_cluster, metric, sk)
     if return_info:
         diagonal, above = _shared_tiles(group_h)
         info["gram_tiles_per_pass"] = ([diagonal + 2 * above] if min_samples > 1 else []) + [diagonal + above] * info["rounds"]
@@ -375,28 +434,32 @@ def hdbscan_rows_groups(X, sizes, min_cluster_size: int = 2, min_samples: int | 
 class HdbscanGpuClusterer:
     """A scikit-learn `HDBSCAN` stand-in on the device route, for the `clusterer_factory=` argument of
     `cluster.cluster_hdbscan_two_stage`: `fit_predict` takes L2-normalised rows (metric "euclidean") or any rows (metric "cosine").
-    A "precomputed" distance matrix raises ValueError: the route needs the rows, not a matrix."""
+    A "precomputed" distance matrix raises ValueError: the route needs the rows, not a matrix.  labelling: as for `hdbscan_rows`."""
 
     def __init__(self, min_cluster_size: int = 2, min_samples: int | None = None, allow_single_cluster: bool = True,
-                 metric: str = "euclidean", operator=None):
+                 metric: str = "euclidean", operator=None, labelling: str = "sklearn"):
         if metric not in ("euclidean", "cosine"):
             raise ValueError(f"HdbscanGpuClusterer clusters rows (metric 'euclidean' or 'cosine'); metric={metric!r} has no rows to work on")
         self.min_cluster_size = min_cluster_size
         self.min_samples = min_samples
         self.allow_single_cluster = allow_single_cluster
         self.metric = metric
+        if labelling not in LABELLINGS:
+            raise ValueError(f"labelling must be one of {LABELLINGS}, got {labelling!r}")
         self.operator = operator
+        self.labelling = labelling
 
     @classmethod
-    def factory(cls, operator=None):
+    def factory(cls, operator=None, labelling: str = "sklearn"):
         return lambda **kw: cls(kw.get("min_cluster_size", 2), kw.get("min_samples"), kw.get("allow_single_cluster", True),
-                                kw.get("metric", "euclidean"), operator=operator)
+                                kw.get("metric", "euclidean"), operator=operator, labelling=labelling)
 
     def fit_predict(self, X) -> np.ndarray:
         X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
         if self.operator is None:
             X = upload_rows(X, "HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
-        return hdbscan_rows(X, self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric, operator=self.operator)
+        return hdbscan_rows(X, self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric, operator=self.operator,
+                            labelling=self.labelling)
 
     def fit_predict_many(self, list_of_X) -> list:
         """`fit_predict` of every matrix of the list (all of one width) through ONE grouped driver (`hdbscan_rows_groups`) -> a list of
@@ -411,4 +474,4 @@ class HdbscanGpuClusterer:
         if self.operator is None:
             X = upload_rows(X, "HdbscanGpuClusterer runs on the HIP path (a visible GPU); there is no CPU fallback")
         return hdbscan_rows_groups(X, [len(m) for m in mats], self.min_cluster_size, self.min_samples, self.allow_single_cluster, self.metric,
-                                   operator=self.operator)
+                                   operator=self.operator, labelling=self.labelling)

@@ -18,6 +18,7 @@ _ACT = {None: N.SD_ACT_NONE, "none": N.SD_ACT_NONE, "relu": N.SD_ACT_RELU, "tanh
 
 
 _ENTRIES = frozenset(name for key, table in vars(N).items() if key.endswith("PROTOTYPES") for name in table)
+_LAUNCHABLE = _ENTRIES | frozenset(N.TREE_ENTRIES)      # what `launch` accepts: the six *_PROTOTYPES tables and the table of sd_hip_tree.h
 
 
 def _current_stream(index: int) -> int:
@@ -32,7 +33,7 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
 def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
-    if name not in _ENTRIES:
+    if name not in _LAUNCHABLE:
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -683,6 +684,33 @@ def hdb_outgoing_grouped(rows: torch.Tensor, core: torch.Tensor, comp: torch.Ten
     launch("sd_hdb_outgoing_grouped_f32", rows, rows.data_ptr(), ld, n, d, core.data_ptr(), comp.data_ptr(), group.data_ptr(), max_group,
            nn.data_ptr(), best.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
     return nn, best, bad
+
+
+# ----------------------------------------------------------------------------- from the tree's edges to the labels (include/sd_hip_tree.h)
+
+def tree_labels_grouped(lo: torch.Tensor, hi: torch.Tensor, dist: torch.Tensor, first_edge: torch.Tensor, max_edges: int,
+                        min_cluster_size: int, allow_single_cluster: bool, ws: Workspace | torch.Tensor | None = None):
+    """HDBSCAN's labels from the spanning trees of many recordings in one launch: lo, hi int32 [E] (rows counted from the recording's
+    first), dist f64 [E] (finite, >= 0), first_edge int32 [G + 1] (non-decreasing, 0 first, E last; recording g owns the edges
+    [first_edge[g], first_edge[g + 1]), at least one), `max_edges` a bound on the edges of any one recording -> (labels int32 [E + G],
+    the rows of recording g from first_edge[g] + g on; bad int32 [G], still on the device: non-zero where a recording's edges are no
+    spanning tree of its rows or a distance is negative or not finite, and that recording's labels are all -1).  Per recording exactly
+    scikit-learn 1.7.2's `tree_to_labels(make_single_linkage(mst[argsort(dist, kind="stable")]), min_cluster_size, "eom",
+    allow_single_cluster, 0.0, None)[0]`.  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_tree_labels_workspace_bytes(E, G, max_edges), to reuse across calls (allocated when None)."""
+    _need_cuda(lo, hi, dist, first_edge)
+    E, G = dist.numel(), first_edge.numel() - 1
+    for name, t, dt, n in (("lo", lo, torch.int32, E), ("hi", hi, torch.int32, E), ("dist", dist, torch.float64, E),
+                           ("first_edge", first_edge, torch.int32, G + 1)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    max_edges = int(max_edges)
+    labels = torch.empty((E + max(G, 0),), dtype=torch.int32, device=dist.device)
+    bad = torch.empty((max(G, 0),), dtype=torch.int32, device=dist.device)
+    ws = _workspace(ws, int(N.load().sd_tree_labels_workspace_bytes(E, G, max_edges)), dist.device)
+    launch("sd_tree_labels_grouped", dist, lo.data_ptr(), hi.data_ptr(), dist.data_ptr(), first_edge.data_ptr(), G, E, max_edges,
+           int(min_cluster_size), int(bool(allow_single_cluster)), labels.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return labels, bad
 
 
 # ----------------------------------------------------------------------------- f64 whitening and cluster centres (include/sd_hip_diag.h)
