@@ -151,7 +151,8 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
                   min_speakers: int, max_speakers: int, rttm_filepath: str | Path | None = None, *,
                   encoder: Encoder | None = None, clustering: str = "spectral", clustering_threshold: float = 0.70,
                   window_s: float = 2.0, hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True,
-                  return_details: bool = False, world: str | None = None) -> list[tuple[float, float, str | int]]:
+                  return_details: bool = False, world: str | None = None,
+                  speaker_bounds: bool = False) -> list[tuple[float, float, str | int]]:
     """-> [(start_s, end_s, "SPEAKER_xx")], RTTM written to `rttm_filepath` when given.
 
     `world="dist"` (under torchrun, after `dist.init_from_env()`): BASELINE.json configs[2].  Every rank runs the
@@ -161,7 +162,12 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 
     `clustering`: "spectral" (default; eigengap + scikit-learn SpectralClustering on the host), "ahc", "spectral_gpu": the two
     spectral steps on the device (`cluster_gpu`), or "ahc_gpu": the AHC of "ahc" on the device from the rows themselves (`ahc_gpu`; no
-    affinity is formed, `details["affinity"]` is None).  The two device routes are HIP path only."""
+    affinity is formed, `details["affinity"]` is None).  The two device routes are HIP path only.
+
+    `speaker_bounds=True` (clustering="ahc_gpu" only; ValueError with any other, since the spectral routes honour the bounds already and
+    "ahc" stays the reference's threshold cut): the AHC's cluster count is the threshold's, clamped into [min_speakers, max_speakers]
+    (each clamped to the number of windows) by a dendrogram cut on the device (`ahc_gpu`, include/sd_hip_cut.h)."""
+    _check_speaker_bounds(speaker_bounds, clustering)
     y, sr, uri = _load(audio_filepath)
     use_gpu = encoder is None
     if encoder is None:
@@ -200,7 +206,8 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
             labels = cluster.ahc_cosine(K, clustering_threshold)
         elif clustering == "ahc_gpu":
             from . import ahc_gpu
-            labels = ahc_gpu.ahc_cosine_rows(_device_rows(X, use_gpu, clustering), clustering_threshold)
+            labels = ahc_gpu.ahc_cosine_rows(_device_rows(X, use_gpu, clustering), clustering_threshold,
+                                             **_cluster_bounds(speaker_bounds, min_speakers, max_speakers, [len(X)], one=True))
         else:
             raise ValueError(f"unknown clustering {clustering!r}")
         labels = cluster.relabel_by_first_appearance(labels)
@@ -214,7 +221,8 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 
 def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s: float, min_speakers: int, max_speakers: int,
                    rttm_filepaths=None, *, clustering: str = "ahc_gpu", clustering_threshold: float = 0.70, window_s: float = 2.0,
-                   hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True, return_details: bool = False):
+                   hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True, return_details: bool = False,
+                   speaker_bounds: bool = False):
     """`diarize_audio(..., clustering="ahc_gpu")` for a list of recordings at once -> one segment list per recording (with
     `return_details`: a list of (segments, details)); the RTTM of recording i goes to `rttm_filepaths[i]` when that is given.
 
@@ -222,9 +230,12 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
     after each (a window that hangs over a recording's end reads zeros, as it does for one recording), and all windows of all
     recordings go through `encode_windows` together: the micro-batches are full whatever the recordings' sizes.  The rows, centred
     per recording, are clustered by ONE driver (`ahc_gpu.ahc_cosine_groups`): one nearest pass and one host synchronisation per
-    round for all recordings.  HIP path only, and only clustering="ahc_gpu": the other routes have no grouped form."""
+    round for all recordings.  HIP path only, and only clustering="ahc_gpu": the other routes have no grouped form.
+    `speaker_bounds=True`: every recording's cluster count is clamped into [min_speakers, max_speakers] as in `diarize_audio`, all
+    recordings by one launch of the cut."""
     if clustering != "ahc_gpu":
         raise ValueError(f"diarize_audios clusters all recordings in one driver, which exists for clustering='ahc_gpu' only, got {clustering!r}")
+    _check_speaker_bounds(speaker_bounds, clustering)
     audios = list(audios)
     rttm_filepaths = [None] * len(audios) if rttm_filepaths is None else list(rttm_filepaths)
     if len(rttm_filepaths) != len(audios):
@@ -250,7 +261,8 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
         _device_rows(embs, True, clustering)                                            # the refusal without a visible GPU, before any work
         embs = using_ecapa_encoder().encode_windows(np.concatenate(signal), np.concatenate(starts_all), win)
         X = np.concatenate([cluster.center(embs[a:b]) if center_embeddings and b > a else embs[a:b] for a, b in zip(bounds[:-1], bounds[1:])])
-        labels = ahc_gpu.ahc_cosine_groups(_device_rows(X, True, clustering), sizes, clustering_threshold)
+        labels = ahc_gpu.ahc_cosine_groups(_device_rows(X, True, clustering), sizes, clustering_threshold,
+                                           **_cluster_bounds(speaker_bounds, min_speakers, max_speakers, sizes))
     out = []
     for r, a, b, lab, path in zip(recs, bounds[:-1], bounds[1:], labels, rttm_filepaths):
         segments: list[tuple[float, float, str | int]] = []
@@ -264,6 +276,24 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
                 rttm.write_rttm(segments, r["uri"], f)
         out.append((segments, details) if return_details else segments)
     return out
+
+
+def _check_speaker_bounds(speaker_bounds: bool, clustering: str) -> None:
+    if speaker_bounds and clustering != "ahc_gpu":
+        raise ValueError(f"speaker_bounds=True bounds the cluster count of clustering='ahc_gpu'; clustering={clustering!r} "
+                         "(the spectral routes honour min_speakers / max_speakers already, 'ahc' is the reference's threshold cut)")
+
+
+def _cluster_bounds(speaker_bounds: bool, min_speakers: int, max_speakers: int, sizes, one: bool = False) -> dict:
+    """The keyword arguments of the `ahc_gpu` drivers: nothing without `speaker_bounds`; otherwise min_speakers and max_speakers, each
+    clamped to the number of windows of its recording (at least 1).  1 <= min_speakers <= max_speakers is checked by the driver."""
+    if not speaker_bounds:
+        return {}
+    if not 1 <= int(min_speakers) <= int(max_speakers):
+        raise ValueError(f"speaker_bounds=True needs 1 <= min_speakers <= max_speakers, got {min_speakers} and {max_speakers}")
+    lo = [max(1, min(int(min_speakers), n)) for n in sizes]
+    hi = [max(1, min(int(max_speakers), n)) for n in sizes]
+    return {"min_clusters": lo[0] if one else lo, "max_clusters": hi[0] if one else hi}
 
 
 def _speech_regions(y: np.ndarray, sr: int, min_speech_duration_s: float, min_silence_duration_s: float, vad_scorer=None):
@@ -398,17 +428,20 @@ def extract_speaker_stems(audio: str | Path | dict, segments: list[tuple[float, 
 
 
 class Diarizer:
-    def __init__(self, hparams: DiarizationParameters, encoder: Encoder | None = None, clustering: str = "spectral"):
+    def __init__(self, hparams: DiarizationParameters, encoder: Encoder | None = None, clustering: str = "spectral",
+                 speaker_bounds: bool = False):
+        _check_speaker_bounds(speaker_bounds, clustering)
         self.hparams = hparams
         self.encoder = encoder
         self.clustering = clustering
+        self.speaker_bounds = speaker_bounds
 
     def diarize(self, apath: str | Path | dict, rttm_filepath: str | Path | None):
         hp = self.hparams
         segments = diarize_audio(apath, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                                  min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepath=rttm_filepath,
                                  encoder=self.encoder, clustering=self.clustering,
-                                 clustering_threshold=hp.clustering_threshold)
+                                 clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds)
         segments = [s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s]
         return sorted(segments)
 
@@ -419,7 +452,7 @@ class Diarizer:
             raise RuntimeError("Diarizer.diarize_many runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
         many = diarize_audios(apaths, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                               min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepaths=rttm_filepaths,
-                              clustering=self.clustering, clustering_threshold=hp.clustering_threshold)
+                              clustering=self.clustering, clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds)
         return [sorted(s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s) for segments in many]
 
     def merge_segments(self, segments):

@@ -19,6 +19,7 @@ _ACT = {None: N.SD_ACT_NONE, "none": N.SD_ACT_NONE, "relu": N.SD_ACT_RELU, "tanh
 
 _ENTRIES = frozenset(name for key, table in vars(N).items() if key.endswith("PROTOTYPES") for name in table)
 _LAUNCHABLE = _ENTRIES | frozenset(N.TREE_ENTRIES)      # what `launch` accepts: the six *_PROTOTYPES tables and the table of sd_hip_tree.h
+_CUT_LAUNCHABLE = frozenset(N.CUT_ENTRIES)              # ... and, in a set of its own, the table of sd_hip_cut.h
 
 
 def _current_stream(index: int) -> int:
@@ -33,7 +34,7 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
 def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
-    if name not in _LAUNCHABLE:
+    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE:
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -605,6 +606,42 @@ def ahc_merge(sums: torch.Tensor, count: torch.Tensor, inv_count: torch.Tensor, 
     launch("sd_ahc_merge_f32", sums, sums.data_ptr(), ld, n, d, count.data_ptr(), inv_count.data_ptr(), nn.data_ptr(), best.data_ptr(),
            C.c_float(cos_thr), target.data_ptr(), n_merged.data_ptr())
     return target, n_merged
+
+
+# ----------------------------------------------------------------------------- the bounded cut of the AHC merge log (include/sd_hip_cut.h)
+
+def ahc_cut_grouped(lo: torch.Tensor, hi: torch.Tensor, key: torch.Tensor, first_merge: torch.Tensor, first_row: torch.Tensor,
+                    cos_thr: float, min_clusters: torch.Tensor, max_clusters: torch.Tensor, ws: Workspace | torch.Tensor | None = None):
+    """The labels of many recordings at a bounded cluster count from their merge logs, in one launch: lo, hi int32 [M] (the lowest
+    rows of the kept and the absorbed cluster, counted from the recording's first row), key f32 [M] (finite), first_merge and first_row
+    int32 [G + 1] (non-decreasing, 0 first, M and the number of rows last), min_clusters and max_clusters int32 [G]
+    -> (labels int32 [rows], the rows of recording g from first_row[g] on, numbered by first appearance; clusters int32 [G]; bad
+    int32 [G]; all still on the device).  Per recording the m = max(0, min(max(c, n - max), n - min)) first merges in the order (key
+    descending, position ascending) are applied, c the merges with key > cos_thr; bad is non-zero, and the labels all -1, where the
+    log of a recording is broken (include/sd_hip_cut.h has the list).  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_ahc_cut_workspace_bytes(rows, G), to reuse across calls (allocated when None).  The number of rows is read from
+    first_row[G]: one synchronisation, which the caller's read of `bad` would make anyway."""
+    _need_cuda(lo, hi, key, first_merge, first_row, min_clusters, max_clusters)
+    M, G = key.numel(), first_row.numel() - 1
+    for name, t, dt, n in (("lo", lo, torch.int32, M), ("hi", hi, torch.int32, M), ("key", key, torch.float32, M),
+                           ("first_merge", first_merge, torch.int32, G + 1), ("first_row", first_row, torch.int32, G + 1),
+                           ("min_clusters", min_clusters, torch.int32, G), ("max_clusters", max_clusters, torch.int32, G)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} vector of {n} entries, got {tuple(t.shape)} {t.dtype}")
+    if G < 1:
+        raise ValueError("first_row must name at least one recording")
+    rows = int(first_row[-1])                       # the one number the output's size hangs on
+    if rows < 0:
+        raise ValueError(f"first_row ends at {rows}")
+    dev = key.device
+    labels = torch.empty((rows,), dtype=torch.int32, device=dev)
+    clusters = torch.empty((G,), dtype=torch.int32, device=dev)
+    bad = torch.empty((G,), dtype=torch.int32, device=dev)
+    ws = _workspace(ws, int(N.load().sd_ahc_cut_workspace_bytes(rows, G)), dev)
+    launch("sd_ahc_cut_grouped", first_row, _ptr(lo) or None, _ptr(hi) or None, _ptr(key) or None, first_merge.data_ptr(), first_row.data_ptr(), G, M,
+           rows, C.c_float(cos_thr), min_clusters.data_ptr(), max_clusters.data_ptr(), labels.data_ptr() or None, clusters.data_ptr(), bad.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
+    return labels, clusters, bad
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)

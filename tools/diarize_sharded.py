@@ -30,8 +30,12 @@ def main():
     ap.add_argument("--clustering", default="spectral", choices=("spectral", "ahc", "spectral_gpu", "ahc_gpu"),
                     help="spectral_gpu: speaker count and spectral embedding on the device (cluster_gpu.py); "
                          "ahc_gpu: average-linkage AHC on the device from the embeddings themselves (ahc_gpu.py)")
+    ap.add_argument("--speaker-bounds", action="store_true",
+                    help="with --clustering ahc_gpu: clamp the cluster count into [--min-speakers, --max-speakers] by a dendrogram cut on the device")
     ap.add_argument("--gpus", type=int, default=1, help="ranks to start (one per GPU) when not already under torchrun")
     a = ap.parse_args()
+    if a.speaker_bounds and a.clustering != "ahc_gpu":
+        ap.error("--speaker-bounds needs --clustering ahc_gpu")
     from speech_diarization_amd import launch
     if launch.needs_self_launch(a.gpus):
         raise SystemExit(launch.self_launch(os.path.abspath(__file__), sys.argv[1:], a.gpus))
@@ -49,7 +53,8 @@ def main():
             tdist.barrier()
     t0 = time.time()
     segs, det = db.diarize_audio(a.audio, 0.35, 0.1, a.min_speakers, a.max_speakers, rttm_filepath=a.rttm or os.path.splitext(a.audio)[0] + ".rttm",
-                                 clustering=a.clustering, return_details=True, world="dist" if world > 1 else None)
+                                 clustering=a.clustering, return_details=True, world="dist" if world > 1 else None,
+                                 speaker_bounds=a.speaker_bounds)
     if rank == 0:
         print(f"world={world} backend={tdist.get_backend() if world > 1 else 'none'} windows={det['embeddings'].shape[0]} "
               f"speakers={len({k for _, _, k in segs})} turns={len(segs)} wall={time.time() - t0:.2f}s")
