@@ -222,6 +222,16 @@ CUT_ENTRIES = {
     "sd_ahc_cut_grouped": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_kmeans.h: scikit-learn's k-means labels for many recordings in one launch, same shared object, a table and a version of
+# their own.  KMEANS_ENTRIES for the reason TREE_ENTRIES has its name: the *_PROTOTYPES tables are a closed set
+SD_KMEANS_ABI_VERSION = 1
+SD_KMEANS_U_STRIDE = 155
+KMEANS_ENTRIES = {
+    "sd_kmeans_abi_version": (_I, []),
+    "sd_kmeans_grouped_workspace_bytes": (_Z, [_I, _I, _I]),
+    "sd_kmeans_grouped_f64": (_I, [_P, C.c_long, _I, _I, _P, _I, _P, _I, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+}
+
 # include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own
 SD_DIAG_ABI_VERSION = 1
 _D = C.c_double
@@ -275,6 +285,7 @@ def load() -> C.CDLL:
                 ("sd_hip_hdbscan.h", HDBSCAN_PROTOTYPES, "sd_hdbscan_abi_version", SD_HDBSCAN_ABI_VERSION, "HDBSCAN "),
                 ("sd_hip_tree.h", TREE_ENTRIES, "sd_tree_abi_version", SD_TREE_ABI_VERSION, "tree "),
                 ("sd_hip_cut.h", CUT_ENTRIES, "sd_cut_abi_version", SD_CUT_ABI_VERSION, "cut "),
+                ("sd_hip_kmeans.h", KMEANS_ENTRIES, "sd_kmeans_abi_version", SD_KMEANS_ABI_VERSION, "k-means "),
                 ("sd_hip_diag.h", DIAG_PROTOTYPES, "sd_diag_abi_version", SD_DIAG_ABI_VERSION, "diag "),
                 ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
             missing = [name for name in table if not hasattr(lib, name)]

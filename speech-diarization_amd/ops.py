@@ -20,6 +20,7 @@ _ACT = {None: N.SD_ACT_NONE, "none": N.SD_ACT_NONE, "relu": N.SD_ACT_RELU, "tanh
 _ENTRIES = frozenset(name for key, table in vars(N).items() if key.endswith("PROTOTYPES") for name in table)
 _LAUNCHABLE = _ENTRIES | frozenset(N.TREE_ENTRIES)      # what `launch` accepts: the six *_PROTOTYPES tables and the table of sd_hip_tree.h
 _CUT_LAUNCHABLE = frozenset(N.CUT_ENTRIES)              # ... and, in a set of its own, the table of sd_hip_cut.h
+_KMEANS_LAUNCHABLE = frozenset(N.KMEANS_ENTRIES)        # ... and the table of sd_hip_kmeans.h
 
 
 def _current_stream(index: int) -> int:
@@ -34,7 +35,7 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
 def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
-    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE:
+    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE:
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -642,6 +643,40 @@ def ahc_cut_grouped(lo: torch.Tensor, hi: torch.Tensor, key: torch.Tensor, first
            rows, C.c_float(cos_thr), min_clusters.data_ptr(), max_clusters.data_ptr(), labels.data_ptr() or None, clusters.data_ptr(), bad.data_ptr(),
            ws.data_ptr(), ws.numel() * ws.element_size())
     return labels, clusters, bad
+
+
+# ----------------------------------------------------------------------------- k-means (include/sd_hip_kmeans.h)
+
+def kmeans_grouped(rows: torch.Tensor, first_row: torch.Tensor, k: torch.Tensor, first: torch.Tensor, u: torch.Tensor, n_init: int,
+                   max_iter: int, tol: float, max_k: int = 32, max_rows: int | None = None, ws: Workspace | torch.Tensor | None = None):
+    """scikit-learn's `k_means(rows_g, k[g], n_init=n_init, max_iter=max_iter, tol=tol)` labels for many recordings in two launches
+    (the restarts, then the selection among them), the random numbers supplied: rows f64 [n, dim <= 32] read in place (contiguous
+    columns, any row stride), first_row int32 [G + 1] (non-decreasing, 0 first, n last), k int32 [G] (2 <= k <= max_k <= 32, k below
+    the recording's rows), first int32 [G, n_init] (the row of every restart's first centre), u f64 [G, n_init, 31, 5] (the uniform
+    numbers of the seeding; `kmeans_gpu.kmeans_draws` makes both) -> (labels int32 [n], chosen int32 [G], inertia f64 [G], iters
+    int32 [G], flags int32 [G]; all still on the device).  `flags` is non-zero, and the recording's labels all -1, where a cluster ran
+    empty, a row is not finite or an argument of the recording is out of range (include/sd_hip_kmeans.h has the values).  `max_rows`:
+    a bound on the rows of one recording, up to which they are kept in LDS (default: all n).  `ws`: a `Workspace`, or a uint8 tensor
+    of at least sd_kmeans_grouped_workspace_bytes(n, G, n_init), to reuse across calls (allocated when None)."""
+    _need_cuda(rows, first_row, k, first, u)
+    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] == 0 or rows.stride(1) != 1 and rows.shape[1] > 1:
+        raise ValueError(f"rows must be an f64 matrix with contiguous columns, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
+    n, dim = rows.shape
+    G, n_init = k.numel(), int(n_init)
+    ld = max(rows.stride(0), dim) if n > 1 else dim
+    for name, t, dt, shape in (("first_row", first_row, torch.int32, (G + 1,)), ("k", k, torch.int32, (G,)),
+                               ("first", first, torch.int32, (G, n_init)), ("u", u, torch.float64, (G, n_init, 31, 5))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+    dev = rows.device
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    chosen, iters, flags = (torch.empty((G,), dtype=torch.int32, device=dev) for _ in range(3))
+    inertia = torch.empty((G,), dtype=torch.float64, device=dev)
+    ws = _workspace(ws, int(N.load().sd_kmeans_grouped_workspace_bytes(n, G, n_init)), dev)
+    launch("sd_kmeans_grouped_f64", rows, rows.data_ptr() or None, ld, n, dim, first_row.data_ptr(), G, k.data_ptr(), n_init, int(max_iter),
+           C.c_double(tol), int(max_k), int(n if max_rows is None else max_rows) or 1, first.data_ptr(), u.data_ptr(), labels.data_ptr() or None,
+           chosen.data_ptr(), inertia.data_ptr(), iters.data_ptr(), flags.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return labels, chosen, inertia, iters, flags
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)

@@ -27,8 +27,9 @@ def main():
     ap.add_argument("--synthetic", type=float, default=0.0, help="generate this many seconds of an 8-speaker meeting at AUDIO (rank 0)")
     ap.add_argument("--min-speakers", type=int, default=2)
     ap.add_argument("--max-speakers", type=int, default=8)
-    ap.add_argument("--clustering", default="spectral", choices=("spectral", "ahc", "spectral_gpu", "ahc_gpu"),
+    ap.add_argument("--clustering", default="spectral", choices=("spectral", "ahc", "spectral_gpu", "spectral_device", "ahc_gpu"),
                     help="spectral_gpu: speaker count and spectral embedding on the device (cluster_gpu.py); "
+                         "spectral_device: the same with the k-means labels from the device too (kmeans_gpu.py); "
                          "ahc_gpu: average-linkage AHC on the device from the embeddings themselves (ahc_gpu.py)")
     ap.add_argument("--speaker-bounds", action="store_true",
                     help="with --clustering ahc_gpu: clamp the cluster count into [--min-speakers, --max-speakers] by a dendrogram cut on the device")
