@@ -152,7 +152,7 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
                   encoder: Encoder | None = None, clustering: str = "spectral", clustering_threshold: float = 0.70,
                   window_s: float = 2.0, hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True,
                   return_details: bool = False, world: str | None = None,
-                  speaker_bounds: bool = False) -> list[tuple[float, float, str | int]]:
+                  speaker_bounds: bool = False, vad: str = "host") -> list[tuple[float, float, str | int]]:
     """-> [(start_s, end_s, "SPEAKER_xx")], RTTM written to `rttm_filepath` when given.
 
     `world="dist"` (under torchrun, after `dist.init_from_env()`): BASELINE.json configs[2].  Every rank runs the
@@ -170,24 +170,37 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 
     `speaker_bounds=True` (clustering="ahc_gpu" only; ValueError with any other, since the spectral routes honour the bounds already and
     "ahc" stays the reference's threshold cut): the AHC's cluster count is the threshold's, clamped into [min_speakers, max_speakers]
-    (each clamped to the number of windows) by a dendrogram cut on the device (`ahc_gpu`, include/sd_hip_cut.h)."""
+    (each clamped to the number of windows) by a dendrogram cut on the device (`ahc_gpu`, include/sd_hip_cut.h).
+
+    `vad="device"` (default "host"): the speech regions come from the two launches of `vad_gpu` (include/sd_hip_vad.h) on the signal,
+    which is uploaded once and embedded from the same buffer; the same regions wherever no frame probability lies within a few 1e-7
+    of a threshold.  `vad_scorer` must then be None or a `vad.EnergyScorer` (ValueError otherwise: hand device probabilities of your
+    own to `vad_gpu.segments_from_probs_groups`).  HIP path only."""
     _check_speaker_bounds(speaker_bounds, clustering)
+    _check_vad(vad, vad_scorer, encoder is None)
     y, sr, uri = _load(audio_filepath)
     use_gpu = encoder is None
     if encoder is None:
         from .speech_encode import ecapa_encode_batch
         encoder = ecapa_encode_batch
 
-    speech = _speech_regions(y, sr, min_speech_duration_s, min_silence_duration_s, vad_scorer)
+    y_embed = y                                          # what the windows are read from: the host signal, or its one device copy
+    if vad == "device":
+        from . import vad_gpu
+        vad_gpu.frame_counts([len(y)], *vad_gpu.frame_sizes(sr, 30.0, 10.0))       # the host's refusal of a short recording, before the upload
+        y_embed, first_sample, n_samples = vad_gpu.upload_signals([y])
+        speech = _speech_regions_device(y_embed, first_sample, n_samples, sr, min_speech_duration_s, min_silence_duration_s, vad_scorer)[0]
+    else:
+        speech = _speech_regions(y, sr, min_speech_duration_s, min_silence_duration_s, vad_scorer)
     segments: list[tuple[float, float, str | int]] = []
     details = {"speech": speech, "labels": np.zeros(0, dtype=int), "embeddings": np.zeros((0, 192), np.float32)}
     if speech:
         win = int(round(window_s * sr))
         starts, centres, regions = speech_windows(speech, len(y), sr, window_s, hop_s)
         if world is None:
-            embs = _embed_windows(encoder, y, starts, win, use_gpu)
+            embs = _embed_windows(encoder, y_embed, starts, win, use_gpu)
         elif world == "dist":
-            embs = _embed_sharded(encoder, y, starts, win, use_gpu)
+            embs = _embed_sharded(encoder, y_embed, starts, win, use_gpu)
         else:
             raise ValueError(f"world must be None or 'dist', got {world!r}")
         # recording-level mean removal (first step of the reference's whiten_l2, [REF diar_diag.py:187-188]):
@@ -226,7 +239,7 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s: float, min_speakers: int, max_speakers: int,
                    rttm_filepaths=None, *, clustering: str = "ahc_gpu", clustering_threshold: float = 0.70, window_s: float = 2.0,
                    hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True, return_details: bool = False,
-                   speaker_bounds: bool = False):
+                   speaker_bounds: bool = False, vad: str = "host"):
     """`diarize_audio(..., clustering="ahc_gpu")` for a list of recordings at once -> one segment list per recording (with
     `return_details`: a list of (segments, details)); the RTTM of recording i goes to `rttm_filepaths[i]` when that is given.
 
@@ -236,10 +249,15 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
     per recording, are clustered by ONE driver (`ahc_gpu.ahc_cosine_groups`): one nearest pass and one host synchronisation per
     round for all recordings.  HIP path only, and only clustering="ahc_gpu": the other routes have no grouped form.
     `speaker_bounds=True`: every recording's cluster count is clamped into [min_speakers, max_speakers] as in `diarize_audio`, all
-    recordings by one launch of the cut."""
+    recordings by one launch of the cut.
+
+    `vad="device"` (default "host"): every recording is uploaded first (the same buffer, one window of zeros after each), the speech
+    regions of all of them come from the two launches of `vad_gpu` on that buffer, and the windows are embedded from it: the signal is
+    never framed on the host.  `vad_scorer`: None or a `vad.EnergyScorer`, as in `diarize_audio`."""
     if clustering != "ahc_gpu":
         raise ValueError(f"diarize_audios clusters all recordings in one driver, which exists for clustering='ahc_gpu' only, got {clustering!r}")
     _check_speaker_bounds(speaker_bounds, clustering)
+    _check_vad(vad, vad_scorer, True)
     audios = list(audios)
     rttm_filepaths = [None] * len(audios) if rttm_filepaths is None else list(rttm_filepaths)
     if len(rttm_filepaths) != len(audios):
@@ -248,12 +266,25 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
     from .speech_encode import using_ecapa_encoder
     sr, win = 16000, int(round(window_s * 16000))
     recs, signal, starts_all, offset = [], [], [], 0
-    for audio in audios:
-        y, sr_, uri = _load(audio)
-        speech = _speech_regions(y, sr_, min_speech_duration_s, min_silence_duration_s, vad_scorer)
+    loaded = [_load(audio) for audio in audios] if vad == "device" and audios else []
+    if loaded:
+        from . import vad_gpu
+        _device_rows(np.zeros((0, 192), np.float32), True, clustering)                 # the refusal without a visible GPU, before any work
+        vad_gpu.frame_counts([len(y) for y, _, _ in loaded], *vad_gpu.frame_sizes(sr, 30.0, 10.0))
+        signal_dev, first_sample, n_samples = vad_gpu.upload_signals([y for y, _, _ in loaded], gap=win)
+        regions_all = _speech_regions_device(signal_dev, first_sample, n_samples, sr, min_speech_duration_s, min_silence_duration_s, vad_scorer)
+    for i, audio in enumerate(audios):
+        if loaded:
+            (y, sr_, uri), speech = loaded[i], regions_all[i]
+        else:
+            y, sr_, uri = _load(audio)
+            speech = _speech_regions(y, sr_, min_speech_duration_s, min_silence_duration_s, vad_scorer)
         starts, centres, regions = speech_windows(speech, len(y), sr, window_s, hop_s) if speech else (np.zeros(0, np.int64), None, None)
         recs.append({"uri": uri, "speech": speech, "starts": starts, "centres": centres, "regions": regions})
-        if len(starts):
+        if loaded:                                       # every recording is in the device buffer, at first_sample[i]
+            starts_all.append(starts + int(first_sample[i]))
+            offset += len(starts)
+        elif len(starts):
             signal += [y, np.zeros(win, np.float32)]
             starts_all.append(starts + offset)
             offset += len(y) + win
@@ -263,7 +294,7 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
     embs = np.zeros((0, 192), np.float32)
     if offset:
         _device_rows(embs, True, clustering)                                            # the refusal without a visible GPU, before any work
-        embs = using_ecapa_encoder().encode_windows(np.concatenate(signal), np.concatenate(starts_all), win)
+        embs = using_ecapa_encoder().encode_windows(signal_dev if loaded else np.concatenate(signal), np.concatenate(starts_all), win)
         X = np.concatenate([cluster.center(embs[a:b]) if center_embeddings and b > a else embs[a:b] for a, b in zip(bounds[:-1], bounds[1:])])
         labels = ahc_gpu.ahc_cosine_groups(_device_rows(X, True, clustering), sizes, clustering_threshold,
                                            **_cluster_bounds(speaker_bounds, min_speakers, max_speakers, sizes))
@@ -298,6 +329,24 @@ def _cluster_bounds(speaker_bounds: bool, min_speakers: int, max_speakers: int, 
     lo = [max(1, min(int(min_speakers), n)) for n in sizes]
     hi = [max(1, min(int(max_speakers), n)) for n in sizes]
     return {"min_clusters": lo[0] if one else lo, "max_clusters": hi[0] if one else hi}
+
+
+def _check_vad(vad_route: str, vad_scorer, hip_path: bool) -> None:
+    if vad_route not in ("host", "device"):
+        raise ValueError(f"vad must be 'host' or 'device', got {vad_route!r}")
+    if vad_route == "device":
+        from . import vad_gpu
+        vad_gpu.energy_scorer(vad_scorer)
+        if not hip_path:
+            raise RuntimeError("vad='device' runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+
+
+def _speech_regions_device(signal_dev, first_sample, n_samples, sr: int, min_speech_duration_s: float, min_silence_duration_s: float,
+                           vad_scorer=None):
+    """`_speech_regions` for every recording of a signal buffer on the device, in the two launches of `vad_gpu` -> one list each."""
+    from . import vad_gpu
+    return vad_gpu.vad_segments_device(signal_dev, first_sample, n_samples, sr, 0.6, 0.4, min_speech_duration_s * 1000.0,
+                                       min_silence_duration_s * 1000.0, 40.0, 30.0, 10.0, 80.0, 40.0, vad_scorer)
 
 
 def _speech_regions(y: np.ndarray, sr: int, min_speech_duration_s: float, min_silence_duration_s: float, vad_scorer=None):
@@ -433,8 +482,10 @@ def extract_speaker_stems(audio: str | Path | dict, segments: list[tuple[float, 
 
 class Diarizer:
     def __init__(self, hparams: DiarizationParameters, encoder: Encoder | None = None, clustering: str = "spectral",
-                 speaker_bounds: bool = False):
+                 speaker_bounds: bool = False, vad: str = "host"):
         _check_speaker_bounds(speaker_bounds, clustering)
+        _check_vad(vad, None, encoder is None)
+        self.vad = vad
         self.hparams = hparams
         self.encoder = encoder
         self.clustering = clustering
@@ -445,7 +496,7 @@ class Diarizer:
         segments = diarize_audio(apath, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                                  min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepath=rttm_filepath,
                                  encoder=self.encoder, clustering=self.clustering,
-                                 clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds)
+                                 clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds, vad=self.vad)
         segments = [s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s]
         return sorted(segments)
 
@@ -456,7 +507,8 @@ class Diarizer:
             raise RuntimeError("Diarizer.diarize_many runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
         many = diarize_audios(apaths, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                               min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepaths=rttm_filepaths,
-                              clustering=self.clustering, clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds)
+                              clustering=self.clustering, clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds,
+                              vad=self.vad)
         return [sorted(s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s) for segments in many]
 
     def merge_segments(self, segments):

@@ -21,6 +21,7 @@ _ENTRIES = frozenset(name for key, table in vars(N).items() if key.endswith("PRO
 _LAUNCHABLE = _ENTRIES | frozenset(N.TREE_ENTRIES)      # what `launch` accepts: the six *_PROTOTYPES tables and the table of sd_hip_tree.h
 _CUT_LAUNCHABLE = frozenset(N.CUT_ENTRIES)              # ... and, in a set of its own, the table of sd_hip_cut.h
 _KMEANS_LAUNCHABLE = frozenset(N.KMEANS_ENTRIES)        # ... and the table of sd_hip_kmeans.h
+_VAD_LAUNCHABLE = frozenset(N.VAD_ENTRIES)              # ... and the table of sd_hip_vad.h
 
 
 def _current_stream(index: int) -> int:
@@ -35,7 +36,7 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
 def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
-    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE:
+    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE and name not in _VAD_LAUNCHABLE:
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -677,6 +678,61 @@ def kmeans_grouped(rows: torch.Tensor, first_row: torch.Tensor, k: torch.Tensor,
            C.c_double(tol), int(max_k), int(n if max_rows is None else max_rows) or 1, first.data_ptr(), u.data_ptr(), labels.data_ptr() or None,
            chosen.data_ptr(), inertia.data_ptr(), iters.data_ptr(), flags.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
     return labels, chosen, inertia, iters, flags
+
+
+# ----------------------------------------------------------------------------- voice activity (include/sd_hip_vad.h)
+
+def _table(name: str, t: torch.Tensor, dt, n: int) -> None:
+    if t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n},), got {tuple(t.shape)} {t.dtype}")
+
+
+def vad_energy_grouped(signal: torch.Tensor, first_sample: torch.Tensor, n_samples: torch.Tensor, first_frame: torch.Tensor, n_frames: int,
+                       win: int, hop: int, threshold_db: float, slope: float):
+    """`vad.EnergyScorer(threshold_db, slope)` over `vad.frame_audio` for many recordings in one launch: signal f32 [n] (1-d,
+    contiguous), recording g its samples [first_sample[g], first_sample[g] + n_samples[g]) (int64 [G], int32 [G]), frames of `win`
+    samples every `hop`, first_frame int32 [G + 1] the prefix sums of the frame counts 1 + (n_samples - win) // hop, n_frames their
+    total -> (probs f32 [n_frames], bad int32 [G]; both still on the device).  `bad` is non-zero, and the recording's probabilities
+    NaN, where a recording is shorter than a frame, leaves the signal or disagrees with first_frame (include/sd_hip_vad.h)."""
+    _need_cuda(signal, first_sample, n_samples, first_frame)
+    if signal.dtype != torch.float32 or signal.dim() != 1 or not signal.is_contiguous():
+        raise ValueError(f"signal must be a contiguous 1-d f32 tensor, got {tuple(signal.shape)} {signal.dtype}")
+    G = n_samples.numel()
+    _table("first_sample", first_sample, torch.int64, G)
+    _table("n_samples", n_samples, torch.int32, G)
+    _table("first_frame", first_frame, torch.int32, G + 1)
+    probs = torch.empty((int(n_frames),), dtype=torch.float32, device=signal.device)
+    bad = torch.empty((G,), dtype=torch.int32, device=signal.device)
+    launch("sd_vad_energy_grouped_f32", signal, signal.data_ptr() or None, signal.numel(), first_sample.data_ptr(), n_samples.data_ptr(), G,
+           int(win), int(hop), float(threshold_db), float(slope), first_frame.data_ptr(), int(n_frames), probs.data_ptr() or None, bad.data_ptr())
+    return probs, bad
+
+
+def vad_segments_grouped(probs: torch.Tensor, first_frame: torch.Tensor, first_seg: torch.Tensor, seg_cap: int, on: float, off: float,
+                         open_len: int, close_len: int, min_run: int, max_gap: int, want_mask: bool = False,
+                         ws: Workspace | torch.Tensor | None = None):
+    """Frame probabilities to speech runs for many recordings in one launch (`vad.hysteresis_binarize`, `vad.morph_open_close` with
+    lines of open_len and close_len frames, and the run rules of `vad.mask_to_segments` before its padding): probs f32 [n_frames],
+    first_frame int32 [G + 1] (non-decreasing, 0 first, n_frames last), first_seg int32 [G + 1] likewise with seg_cap last, every
+    recording's share at least (its frames + 1) // 2 -> (n_segs int32 [G], seg_start int32 [seg_cap], seg_end int32 [seg_cap],
+    mask uint8 [n_frames] or None, bad int32 [G]; all still on the device).  `ws`: a `Workspace`, or a uint8 tensor of at least
+    sd_vad_segments_workspace_bytes(seg_cap, G), to reuse across calls (allocated when None)."""
+    _need_cuda(probs, first_frame, first_seg)
+    if probs.dtype != torch.float32 or probs.dim() != 1 or not probs.is_contiguous():
+        raise ValueError(f"probs must be a contiguous 1-d f32 tensor, got {tuple(probs.shape)} {probs.dtype}")
+    G, n_frames, seg_cap = first_frame.numel() - 1, probs.numel(), int(seg_cap)
+    _table("first_frame", first_frame, torch.int32, G + 1)
+    _table("first_seg", first_seg, torch.int32, G + 1)
+    dev = probs.device
+    n_segs, bad = (torch.empty((G,), dtype=torch.int32, device=dev) for _ in range(2))
+    seg_start, seg_end = (torch.empty((seg_cap,), dtype=torch.int32, device=dev) for _ in range(2))
+    mask = torch.empty((n_frames,), dtype=torch.uint8, device=dev) if want_mask else None
+    ws = _workspace(ws, int(N.load().sd_vad_segments_workspace_bytes(seg_cap, G)), dev)
+    launch("sd_vad_segments_grouped", first_frame, probs.data_ptr() or None, first_frame.data_ptr(), G, n_frames, float(on), float(off),
+           int(open_len), int(close_len), int(min_run), int(max_gap), first_seg.data_ptr(), seg_cap, n_segs.data_ptr(),
+           seg_start.data_ptr() or None, seg_end.data_ptr() or None, (_ptr(mask) or None) if want_mask else None, bad.data_ptr(),
+           ws.data_ptr(), ws.numel() * ws.element_size())
+    return n_segs, seg_start, seg_end, mask, bad
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)

@@ -5,7 +5,8 @@ Same public names and signatures as the reference's `vad.py`
 `morph_open_close`, `mask_to_segments`, `silero_vad_segments`
 [REF vad.py:9,19-50,53-55,59-74,77-87,90-163,167-187]).  These are tiny sequential
 host computations (360 k frames per hour of audio); they stay on the host, written
-here as whole-array numpy instead of per-frame loops.  The Silero network itself is a
+here as whole-array numpy instead of per-frame loops (vad_gpu.py has the opt-in device route for a folder of recordings: the same
+chain in two launches, include/sd_hip_vad.h).  The Silero network itself is a
 remote `torch.hub` download in the reference and out of scope: `SileroVAD` accepts any
 frame scorer and ships an energy-based stand-in for synthetic audio.
 """
