@@ -243,6 +243,17 @@ VAD_ENTRIES = {
     "sd_vad_segments_grouped": (_I, [_P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
+# include/sd_hip_scd.h: window embeddings to split pieces for the segments of many recordings in one launch, same shared object, a table
+# and a version of their own.  SCD_ENTRIES for the reason TREE_ENTRIES has its name: the *_PROTOTYPES tables are a closed set
+SD_SCD_ABI_VERSION = 1
+SD_SCD_LDS_ROWS = 2048
+SCD_ENTRIES = {
+    "sd_scd_abi_version": (_I, []),
+    "sd_scd_split_workspace_bytes": (_Z, [_I, _I]),
+    "sd_scd_split_grouped_f32": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, C.c_double, C.c_double, C.c_double, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P,
+                                      _P, _Z, _P]),
+}
+
 # include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own
 SD_DIAG_ABI_VERSION = 1
 _D = C.c_double
@@ -298,6 +309,7 @@ def load() -> C.CDLL:
                 ("sd_hip_cut.h", CUT_ENTRIES, "sd_cut_abi_version", SD_CUT_ABI_VERSION, "cut "),
                 ("sd_hip_kmeans.h", KMEANS_ENTRIES, "sd_kmeans_abi_version", SD_KMEANS_ABI_VERSION, "k-means "),
                 ("sd_hip_vad.h", VAD_ENTRIES, "sd_vad_abi_version", SD_VAD_ABI_VERSION, "VAD "),
+                ("sd_hip_scd.h", SCD_ENTRIES, "sd_scd_abi_version", SD_SCD_ABI_VERSION, "SCD "),
                 ("sd_hip_diag.h", DIAG_PROTOTYPES, "sd_diag_abi_version", SD_DIAG_ABI_VERSION, "diag "),
                 ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
             missing = [name for name in table if not hasattr(lib, name)]

@@ -131,9 +131,13 @@ def _encode_rows(snippets: np.ndarray, encode: Encoder, rows_per_call: int) -> n
 
 def scd_split_segments(y: np.ndarray, sr: int, segments: list[Segment], win_ms: float = 1000.0, hop_ms: float = 200.0,
                        thr: float = 1.25, min_speech_ms: float = 1000.0, encode: Encoder | None = None,
-                       rows_per_call: int = 2048) -> list[Segment]:
+                       rows_per_call: int = 2048, *, scd: str = "host") -> list[Segment]:
     """Split long VAD segments where the speaker embedding changes: sliding-window embeddings,
-    adjacent cosine distance, z-score, peaks above `thr`; keep pieces >= min_speech_ms."""
+    adjacent cosine distance, z-score, peaks above `thr`; keep pieces >= min_speech_ms.
+    `scd="device"` (default "host"): pass 1 leaves the window embeddings on the device and pass 2 is the one launch of `scd_gpu`
+    (`scd_split_segments_many` for this recording alone); it needs the HIP encoder, so an injected `encode` raises ValueError."""
+    if scd != "host":
+        return scd_split_segments_many([y], sr, [segments], win_ms, hop_ms, thr, min_speech_ms, encode, rows_per_call, scd=scd)[0]
     assert y.ndim == 1 and y.dtype == np.float32
     use_gpu = _on_gpu(encode)
     encode = encode or _default_encode()
@@ -184,6 +188,69 @@ def scd_split_segments(y: np.ndarray, sr: int, segments: list[Segment], win_ms: 
                 last = cut
         if seg.end - last >= min_speech_s:
             out.append(Segment(last, seg.end))
+    return out
+
+
+def _check_scd(scd: str, encode: Encoder | None) -> None:
+    if scd not in ("host", "device"):
+        raise ValueError(f"scd must be 'host' or 'device', got {scd!r}")
+    if scd == "device" and encode is not None:
+        raise ValueError("scd='device' splits the window embeddings of the HIP encoder where they are, on the device; an injected "
+                         "`encode` returns host rows (use scd='host' with it)")
+
+
+def scd_split_segments_many(ys, sr: int, segments_list, win_ms: float = 1000.0, hop_ms: float = 200.0, thr: float = 1.25,
+                            min_speech_ms: float = 1000.0, encode: Encoder | None = None, rows_per_call: int = 2048, *,
+                            scd: str = "device") -> list[list[Segment]]:
+    """`scd_split_segments(y, sr, segments, ..., scd=scd)` for a list of recordings -> the list of their segment lists.
+
+    scd="device": pass 1 per recording, as in `scd_split_segments` but with the window embeddings kept on the device (the window
+    launches are not shared across recordings: a shared launch would change their bits); then ONE split launch and ONE download
+    for all segments of all recordings (`scd_gpu.split_rows_groups`).  A segment without a peak is returned as the same object."""
+    _check_scd(scd, encode)
+    ys, segments_list = list(ys), [list(segs) for segs in segments_list]
+    if len(ys) != len(segments_list):
+        raise ValueError(f"{len(ys)} recordings and {len(segments_list)} segment lists")
+    if scd == "host":
+        return [scd_split_segments(y, sr, segs, win_ms, hop_ms, thr, min_speech_ms, encode, rows_per_call) for y, segs in zip(ys, segments_list)]
+    win = int(round(win_ms / 1000.0 * sr))
+    hop = int(round(hop_ms / 1000.0 * sr))
+    if hop < 1:
+        raise ValueError(f"Invalid hop_length: {hop}")
+    counts, rows = [], []
+    for y, segments in zip(ys, segments_list):
+        assert y.ndim == 1 and y.dtype == np.float32
+        starts = []
+        for seg in segments:                             # pass 1 of `scd_split_segments`: the same windows, counted the same way
+            a = int(seg.start * sr)
+            length = y[a: int(seg.end * sr)].shape[0]
+            n = 1 + (length - win) // hop if length >= win else 0     # the rows of `frame_audio`
+            if n < 3:
+                counts.append(0)
+                continue
+            counts.append(n)
+            starts.append(a + hop * np.arange(n, dtype=np.int64))
+        if starts:
+            from .speech_encode import using_ecapa_encoder
+            rows.append(using_ecapa_encoder().encode_windows(y, np.concatenate(starts), win, rows_per_call=rows_per_call, to_host=False))
+    flat = [seg for segments in segments_list for seg in segments]
+    if rows:
+        import torch
+        from . import scd_gpu
+        split = scd_gpu.split_rows_groups(rows[0] if len(rows) == 1 else torch.cat(rows), np.concatenate([[0], np.cumsum(counts)]),
+                                          [seg.start for seg in flat], [seg.end for seg in flat], hop_ms, thr, min_speech_ms)
+    else:
+        split = [(0, None)] * len(flat)
+    out, at = [], 0
+    for segments in segments_list:
+        pieces: list[Segment] = []
+        for seg, (n_peaks, times) in zip(segments, split[at: at + len(segments)]):
+            if n_peaks == 0:
+                pieces.append(seg)
+            else:
+                pieces.extend(Segment(a, b) for a, b in times)
+        out.append(pieces)
+        at += len(segments)
     return out
 
 
@@ -383,7 +450,7 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
             merge_max_gap_s: float = 0.5, merge_max_speech_s: float = 30.0, merge_mincos: float = 0.8, reseg: int = 1, *,
             cluster_cos: float = 0.70, encode: Encoder | None = None, vad_segments: Callable | None = None,
             compat_reference_bugs: bool = False, clusterer: str | Callable = "hdbscan_two_stage",
-            packed_embeddings: bool = False) -> list[Segment]:
+            packed_embeddings: bool = False, scd: str = "host") -> list[Segment]:
     """VAD -> SCD split -> embed -> cluster -> conservative merge -> re-embed -> frame reassignment ->
     merge_adjacent: the stage order and the positional parameters of [REF anti_stick_diarize.py:493-511] (the 17
     parameters up to `reseg`, same order and defaults; what this build adds is keyword-only).
@@ -401,10 +468,14 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
     callable.
 
     `packed_embeddings=True` embeds every segment as if alone (`embed_segments(..., packed=True)`) instead of in the reference's
-    zero-padded batches of 32 (the default)."""
+    zero-padded batches of 32 (the default).
+
+    `scd="device"` (default "host") splits the VAD segments with the one launch of `scd_gpu` (`scd_split_segments(..., scd="device")`:
+    the HIP encoder only)."""
     from . import cluster
+    _check_scd(scd, encode)
     front = _diarize_front(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
-                           morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings)
+                           morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings, scd)
     if front is None:
         return []
     embs = front[4]
@@ -429,9 +500,22 @@ def diarize(wav_path, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: f
 
 
 def _diarize_front(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
-                   morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings):
+                   morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings, scd="host"):
     """`diarize` up to the embeddings: load, VAD, SCD split, embed -> (y, sr, speech, speech2, embs), or None when the VAD finds no
     speech."""
+    loaded = _diarize_load_vad(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                               morph_close_ms, vad_segments)
+    if loaded is None:
+        return None
+    y, sr, speech = loaded
+    speech2 = scd_split_segments(y, sr, speech, win_ms=scd_win_ms, hop_ms=scd_hop_ms, thr=scd_thr, encode=encode, scd=scd)
+    embs = embed_segments(y, sr, speech2, encode=encode, packed=packed_embeddings)
+    return y, sr, speech, speech2, embs
+
+
+def _diarize_load_vad(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                      morph_close_ms, vad_segments):
+    """The first two stages of `diarize`: load, VAD -> (y, sr, speech), or None when the VAD finds no speech."""
     if isinstance(wav_path, np.ndarray):
         y = np.ascontiguousarray(wav_path, dtype=np.float32)
     else:
@@ -443,10 +527,7 @@ def _diarize_front(wav_path, sr, target_lufs, vad_on_thr, vad_off_thr, min_speec
                       morph_close_ms=morph_close_ms)
     if not speech_t:
         return None
-    speech = [Segment(s, e) for s, e in speech_t]
-    speech2 = scd_split_segments(y, sr, speech, win_ms=scd_win_ms, hop_ms=scd_hop_ms, thr=scd_thr, encode=encode)
-    embs = embed_segments(y, sr, speech2, encode=encode, packed=packed_embeddings)
-    return y, sr, speech, speech2, embs
+    return y, sr, [Segment(s, e) for s, e in speech_t]
 
 
 def _diarize_tail(front, raw, merge_max_gap_s, merge_max_speech_s, merge_mincos, reseg, encode, compat_reference_bugs,
@@ -465,12 +546,38 @@ def _diarize_tail(front, raw, merge_max_gap_s, merge_max_speech_s, merge_mincos,
     return merge_adjacent(speech4, gap=merge_max_gap_s)
 
 
+def _diarize_fronts(wav_paths, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                    morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings, scd):
+    """`_diarize_front` for every recording of a folder.  scd="device": in stages, so that the split is ONE launch for the folder:
+    load and VAD of every recording, `scd_split_segments_many` (the window launches per recording, then the split), then the
+    segment embeddings per recording."""
+    if scd == "host":
+        return [_diarize_front(w, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                               morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings) for w in wav_paths]
+    loaded = [_diarize_load_vad(w, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                                morph_close_ms, vad_segments) for w in wav_paths]
+    have = [v for v in loaded if v is not None]
+    if len({v[1] for v in have}) > 1:
+        raise ValueError(f"scd='device' splits a folder at one sample rate, got {sorted({v[1] for v in have})}")
+    split = iter(scd_split_segments_many([v[0] for v in have], have[0][1], [v[2] for v in have], win_ms=scd_win_ms, hop_ms=scd_hop_ms,
+                                         thr=scd_thr, scd=scd) if have else [])
+    fronts = []
+    for v in loaded:
+        if v is None:
+            fronts.append(None)
+            continue
+        speech2 = next(split)
+        fronts.append((v[0], v[1], v[2], speech2, embed_segments(v[0], v[1], speech2, encode=encode, packed=packed_embeddings)))
+    return fronts
+
+
 def diarize_many(wav_paths, sr: int = 16000, target_lufs: float = -18.0, vad_on_thr: float = 0.6, vad_off_thr: float = 0.4,
                  min_speech_ms: float = 250, min_silence_ms: float = 100, speech_pad_ms: float = 70.0, morph_open_ms: float = 80.0,
                  morph_close_ms: float = 40.0, scd_win_ms: float = 1000.0, scd_hop_ms: float = 200, scd_thr: float = 1.50,
                  merge_max_gap_s: float = 0.5, merge_max_speech_s: float = 30.0, merge_mincos: float = 0.8, reseg: int = 1, *,
                  cluster_cos: float = 0.70, encode: Encoder | None = None, vad_segments: Callable | None = None,
-                 compat_reference_bugs: bool = False, clusterer: str = "hdbscan_gpu", packed_embeddings: bool = False) -> list[list[Segment]]:
+                 compat_reference_bugs: bool = False, clusterer: str = "hdbscan_gpu", packed_embeddings: bool = False,
+                 scd: str = "host") -> list[list[Segment]]:
     """`diarize(..., clusterer="hdbscan_gpu")` (or "hdbscan_device") for a list of recordings (each a path, an `(array, sample_rate)` tuple or a conditioned
     array, as for `diarize`) -> the list of their segment lists, each equal to `diarize` on that recording alone.
 
@@ -479,15 +586,20 @@ def diarize_many(wav_paths, sr: int = 16000, target_lufs: float = -18.0, vad_on_
     centroids); then per recording the tail (relabel, conservative merge, re-embed, frame reassignment, merge_adjacent).  A recording
     without speech gives [].  Only the "hdbscan_gpu" clusterer has a grouped driver ("hdbscan_device" is the same clusterer with
     `labelling="device"`: each stage labels all recordings in one launch); any other raises ValueError (`cluster_cos` is accepted
-    for the parameter list of `diarize` and not used by it).  The embedding launches are not shared across recordings."""
+    for the parameter list of `diarize` and not used by it).  The embedding launches are not shared across recordings.
+
+    `scd="device"` (default "host") runs the front in stages: load, VAD and the window launches of every recording, then ONE split
+    launch for all segments of the folder (`scd_split_segments_many`), then the segment embeddings per recording.  Each recording
+    gets what `diarize(..., scd="device")` gives it alone: the same window launches, and a split that decides every segment by itself."""
     from . import cluster, hdbscan_gpu
+    _check_scd(scd, encode)
     if clusterer not in ("hdbscan_gpu", "hdbscan_device"):
         raise ValueError("diarize_many clusters with 'hdbscan_gpu' alone (the clusterer that has a grouped driver; 'hdbscan_device' is the "
                          f"same with its labels from the device), got {clusterer!r}")
     make = hdbscan_gpu.HdbscanGpuClusterer.factory
     factory = make() if clusterer == "hdbscan_gpu" else make(labelling="device")
-    fronts = [_diarize_front(w, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
-                             morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings) for w in wav_paths]
+    fronts = _diarize_fronts(wav_paths, sr, target_lufs, vad_on_thr, vad_off_thr, min_speech_ms, min_silence_ms, speech_pad_ms, morph_open_ms,
+                             morph_close_ms, scd_win_ms, scd_hop_ms, scd_thr, encode, vad_segments, packed_embeddings, scd)
     live = [i for i, f in enumerate(fronts) if f is not None]
     raws = cluster.cluster_hdbscan_two_stage_many([fronts[i][4] for i in live], min_cluster_size=2,
                                                   clusterer_factory=factory)

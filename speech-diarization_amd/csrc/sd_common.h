@@ -171,3 +171,22 @@ __device__ __forceinline__ float sd_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// <a, b> / (|a| |b| + eps) of two rows of D floats, by one wave (every lane calls it and every lane gets the value): lane l adds the
+// products of the elements l, l + 64, ... in that order, then the 64 partial sums meet in the butterfly of sd_wave_sum.  The ONE
+// statement of the pair cosine on the device: adjacent_cosine_kernel (sd_pool.hip) and scd_split_kernel (scd/sd_scd.hip) both call
+// it, so the two give the same bits for the same rows and eps.  Which operations are fused is WRITTEN here and not left to the
+// compiler, which contracts a * b + c in one kernel and not in another: the three sums are fused multiply-adds, the denominator is a
+// rounded product plus eps (what adjacent_cosine_kernel compiled to before the statement was shared).
+__device__ __forceinline__ float sd_wave_pair_cosine(const float* a, const float* b, int D, float eps, int lane) {
+#pragma clang fp contract(off)
+  float dot = 0.f, na = 0.f, nb = 0.f;
+  for (int d = lane; d < D; d += 64) {
+    dot = __builtin_fmaf(a[d], b[d], dot);
+    na = __builtin_fmaf(a[d], a[d], na);
+    nb = __builtin_fmaf(b[d], b[d], nb);
+  }
+  dot = sd_wave_sum(dot); na = sd_wave_sum(na); nb = sd_wave_sum(nb);
+  const float nn = sqrtf(na) * sqrtf(nb);
+  return dot / (nn + eps);
+}

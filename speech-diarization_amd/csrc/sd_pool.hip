@@ -350,14 +350,8 @@ __global__ __launch_bounds__(256) void adjacent_cosine_kernel(const float* x, in
   if (i >= N - 1) return;
   const float* a = x + (size_t)i * ldx;
   const float* b = a + ldx;
-  float dot = 0.f, na = 0.f, nb = 0.f;
-  for (int d = lane; d < D; d += 64) {
-    dot += a[d] * b[d];
-    na += a[d] * a[d];
-    nb += b[d] * b[d];
-  }
-  dot = sd_wave_sum(dot); na = sd_wave_sum(na); nb = sd_wave_sum(nb);
-  if (lane == 0) sims[i] = dot / (sqrtf(na) * sqrtf(nb) + eps);
+  const float s = sd_wave_pair_cosine(a, b, D, eps, lane);
+  if (lane == 0) sims[i] = s;
 }
 
 __global__ __launch_bounds__(256) void sim_argmax_kernel(const float* w, int ldw, int N, int D, const float* c, int ldc,

@@ -22,6 +22,7 @@ _LAUNCHABLE = _ENTRIES | frozenset(N.TREE_ENTRIES)      # what `launch` accepts:
 _CUT_LAUNCHABLE = frozenset(N.CUT_ENTRIES)              # ... and, in a set of its own, the table of sd_hip_cut.h
 _KMEANS_LAUNCHABLE = frozenset(N.KMEANS_ENTRIES)        # ... and the table of sd_hip_kmeans.h
 _VAD_LAUNCHABLE = frozenset(N.VAD_ENTRIES)              # ... and the table of sd_hip_vad.h
+_SCD_LAUNCHABLE = frozenset(N.SCD_ENTRIES)              # ... and the table of sd_hip_scd.h
 
 
 def _current_stream(index: int) -> int:
@@ -36,7 +37,8 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
 def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
-    if name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE and name not in _VAD_LAUNCHABLE:
+    if (name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE and name not in _VAD_LAUNCHABLE
+            and name not in _SCD_LAUNCHABLE):
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -733,6 +735,40 @@ def vad_segments_grouped(probs: torch.Tensor, first_frame: torch.Tensor, first_s
            seg_start.data_ptr() or None, seg_end.data_ptr() or None, (_ptr(mask) or None) if want_mask else None, bad.data_ptr(),
            ws.data_ptr(), ws.numel() * ws.element_size())
     return n_segs, seg_start, seg_end, mask, bad
+
+
+# ----------------------------------------------------------------------------- speaker-change detection (include/sd_hip_scd.h)
+
+def scd_split_grouped(rows: torch.Tensor, first_row: torch.Tensor, seg_start: torch.Tensor, seg_end: torch.Tensor, first_piece: torch.Tensor,
+                      piece_cap: int, hop_ms: float, thr: float, min_speech_s: float, eps: float = 1e-8, want_sims: bool = False,
+                      want_mask: bool = False, ws: Workspace | torch.Tensor | None = None):
+    """Pass 2 of `anti_stick_diarize.scd_split_segments` for many segments in one launch: rows f32 [n_rows, dim] (unit stride inside a
+    row), segment g its rows [first_row[g], first_row[g + 1]) (int32 [G + 1], non-decreasing, 0 first, n_rows last) between
+    seg_start[g] and seg_end[g] seconds (f64 [G]), first_piece int32 [G + 1] likewise with piece_cap last, every segment's share at
+    least max(1, its rows // 2) -> (n_peaks int32 [G], n_pieces int32 [G], piece_start f64 [piece_cap], piece_end f64 [piece_cap],
+    sims f32 [n_rows] or None, peak_mask uint8 [n_rows] or None, bad int32 [G]; all still on the device).  `ws`: a `Workspace`, or a
+    uint8 tensor of at least sd_scd_split_workspace_bytes(n_rows, G), to reuse across calls (allocated when None)."""
+    _need_cuda(rows, first_row, seg_start, seg_end, first_piece)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or (rows.shape[1] > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1]):
+        raise ValueError(f"rows must be a 2-d f32 tensor with unit stride inside a row, got {tuple(rows.shape)} {rows.dtype} strides {rows.stride()}")
+    n_rows, dim = int(rows.shape[0]), int(rows.shape[1])
+    ld = int(rows.stride(0)) if n_rows > 1 else dim
+    G, piece_cap = first_row.numel() - 1, int(piece_cap)
+    _table("first_row", first_row, torch.int32, G + 1)
+    _table("first_piece", first_piece, torch.int32, G + 1)
+    _table("seg_start", seg_start, torch.float64, G)
+    _table("seg_end", seg_end, torch.float64, G)
+    dev = rows.device
+    n_peaks, n_pieces, bad = (torch.empty((G,), dtype=torch.int32, device=dev) for _ in range(3))
+    piece_start, piece_end = (torch.empty((piece_cap,), dtype=torch.float64, device=dev) for _ in range(2))
+    sims = torch.empty((n_rows,), dtype=torch.float32, device=dev) if want_sims else None
+    mask = torch.empty((n_rows,), dtype=torch.uint8, device=dev) if want_mask else None
+    ws = _workspace(ws, int(N.load().sd_scd_split_workspace_bytes(n_rows, G)), dev)
+    launch("sd_scd_split_grouped_f32", rows, rows.data_ptr() or None, ld, dim, n_rows, first_row.data_ptr(), G, seg_start.data_ptr(),
+           seg_end.data_ptr(), C.c_double(hop_ms), C.c_double(thr), C.c_double(min_speech_s), C.c_float(eps), first_piece.data_ptr(), piece_cap,
+           n_peaks.data_ptr(), n_pieces.data_ptr(), piece_start.data_ptr() or None, piece_end.data_ptr() or None, _ptr(sims) or None,
+           _ptr(mask) or None, bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return n_peaks, n_pieces, piece_start, piece_end, sims, mask, bad
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)
