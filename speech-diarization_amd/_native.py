@@ -254,6 +254,16 @@ SCD_ENTRIES = {
                                       _P, _Z, _P]),
 }
 
+# include/sd_hip_turns.h: window labels to relabelled labels and speaker-turn runs for many recordings in one launch, same shared object, a
+# table and a version of their own.  TURNS_ENTRIES for the reason TREE_ENTRIES has its name: the *_PROTOTYPES tables are a closed set
+SD_TURNS_ABI_VERSION = 1
+SD_TURNS_LDS_WINDOWS = 4096
+TURNS_ENTRIES = {
+    "sd_turns_abi_version": (_I, []),
+    "sd_turns_workspace_bytes": (_Z, [_I, _I]),
+    "sd_turns_grouped": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+}
+
 # include/sd_hip_diag.h: f64 whitening statistics / transform and cluster centres, same shared object, a table and a version of their own
 SD_DIAG_ABI_VERSION = 1
 _D = C.c_double
@@ -310,6 +320,7 @@ def load() -> C.CDLL:
                 ("sd_hip_kmeans.h", KMEANS_ENTRIES, "sd_kmeans_abi_version", SD_KMEANS_ABI_VERSION, "k-means "),
                 ("sd_hip_vad.h", VAD_ENTRIES, "sd_vad_abi_version", SD_VAD_ABI_VERSION, "VAD "),
                 ("sd_hip_scd.h", SCD_ENTRIES, "sd_scd_abi_version", SD_SCD_ABI_VERSION, "SCD "),
+                ("sd_hip_turns.h", TURNS_ENTRIES, "sd_turns_abi_version", SD_TURNS_ABI_VERSION, "turns "),
                 ("sd_hip_diag.h", DIAG_PROTOTYPES, "sd_diag_abi_version", SD_DIAG_ABI_VERSION, "diag "),
                 ("sd_hip_trace.h", TRACE_PROTOTYPES, "sd_trace_abi_version", SD_TRACE_ABI_VERSION, "trace ")):
             missing = [name for name in table if not hasattr(lib, name)]

@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libsd_hip.so"
 STAMP = PKG_DIR / "csrc" / ".build_stamp"
 OFFLOAD_ARCH = "gfx950"
 
-SOURCES = ["sd_api.hip", "sd_conv_gemm.hip", "sd_conv_gemm_f16.hip", "sd_res2net_f16.hip", "sd_fbank.hip", "sd_fbank_utt16.hip", "sd_fbank_generic.hip", "sd_pool.hip", "sd_scores.hip", "sd_asp_fused.hip", "sd_affinity.hip", "sd_ecapa.hip", "sd_spectral.hip", "sd_ahc.hip", "sd_hdbscan.hip", "diag/sd_diag.hip", "ahc/sd_ahc_grouped.hip", "hdbscan/sd_hdb_grouped.hip", "tree/sd_tree_labels.hip", "cut/sd_ahc_cut.hip", "kmeans/sd_kmeans.hip", "vad/sd_vad.hip", "scd/sd_scd.hip"]
+SOURCES = ["sd_api.hip", "sd_conv_gemm.hip", "sd_conv_gemm_f16.hip", "sd_res2net_f16.hip", "sd_fbank.hip", "sd_fbank_utt16.hip", "sd_fbank_generic.hip", "sd_pool.hip", "sd_scores.hip", "sd_asp_fused.hip", "sd_affinity.hip", "sd_ecapa.hip", "sd_spectral.hip", "sd_ahc.hip", "sd_hdbscan.hip", "diag/sd_diag.hip", "ahc/sd_ahc_grouped.hip", "hdbscan/sd_hdb_grouped.hip", "tree/sd_tree_labels.hip", "cut/sd_ahc_cut.hip", "kmeans/sd_kmeans.hip", "vad/sd_vad.hip", "scd/sd_scd.hip", "turns/sd_turns.hip"]
 
 
 def _hipcc() -> str:
@@ -39,7 +39,7 @@ def compile_flags() -> list[str]:
 
 def _fingerprint() -> str:
     h = hashlib.sha256()
-    files = sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.h")) + sorted((CSRC / "diag").glob("*")) + sorted((CSRC / "ahc").glob("*")) + sorted((CSRC / "hdbscan").glob("*")) + sorted((CSRC / "tree").glob("*")) + sorted((CSRC / "cut").glob("*")) + sorted((CSRC / "kmeans").glob("*")) + sorted((CSRC / "vad").glob("*")) + sorted((CSRC / "scd").glob("*")) + sorted(INCLUDE.glob("*.h"))
+    files = sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.h")) + sorted((CSRC / "diag").glob("*")) + sorted((CSRC / "ahc").glob("*")) + sorted((CSRC / "hdbscan").glob("*")) + sorted((CSRC / "tree").glob("*")) + sorted((CSRC / "cut").glob("*")) + sorted((CSRC / "kmeans").glob("*")) + sorted((CSRC / "vad").glob("*")) + sorted((CSRC / "scd").glob("*")) + sorted((CSRC / "turns").glob("*")) + sorted(INCLUDE.glob("*.h"))
     for f in files:
         h.update(f.name.encode())
         h.update(f.read_bytes())

@@ -152,7 +152,7 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
                   encoder: Encoder | None = None, clustering: str = "spectral", clustering_threshold: float = 0.70,
                   window_s: float = 2.0, hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True,
                   return_details: bool = False, world: str | None = None,
-                  speaker_bounds: bool = False, vad: str = "host") -> list[tuple[float, float, str | int]]:
+                  speaker_bounds: bool = False, vad: str = "host", turns: str = "host") -> list[tuple[float, float, str | int]]:
     """-> [(start_s, end_s, "SPEAKER_xx")], RTTM written to `rttm_filepath` when given.
 
     `world="dist"` (under torchrun, after `dist.init_from_env()`): BASELINE.json configs[2].  Every rank runs the
@@ -175,9 +175,14 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
     `vad="device"` (default "host"): the speech regions come from the two launches of `vad_gpu` (include/sd_hip_vad.h) on the signal,
     which is uploaded once and embedded from the same buffer; the same regions wherever no frame probability lies within a few 1e-7
     of a threshold.  `vad_scorer` must then be None or a `vad.EnergyScorer` (ValueError otherwise: hand device probabilities of your
-    own to `vad_gpu.segments_from_probs_groups`).  HIP path only."""
+    own to `vad_gpu.segments_from_probs_groups`).  HIP path only.
+
+    `turns="device"` (default "host"), with every `clustering`: relabelling by first appearance and `labels_to_turns` are one upload,
+    one launch and one download (`turns_gpu.labels_to_turns_groups`, include/sd_hip_turns.h) instead of a Python loop per window,
+    region and run; the same labels and turns, value for value.  HIP path only."""
     _check_speaker_bounds(speaker_bounds, clustering)
     _check_vad(vad, vad_scorer, encoder is None)
+    _check_turns(turns, encoder is None)
     y, sr, uri = _load(audio_filepath)
     use_gpu = encoder is None
     if encoder is None:
@@ -227,8 +232,13 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
                                              **_cluster_bounds(speaker_bounds, min_speakers, max_speakers, [len(X)], one=True))
         else:
             raise ValueError(f"unknown clustering {clustering!r}")
-        labels = cluster.relabel_by_first_appearance(labels)
-        segments = [(s, e, rttm.speaker_label(k)) for s, e, k in labels_to_turns(speech, centres, regions, labels)]
+        if turns == "device":
+            from . import turns_gpu
+            labels, spans = turns_gpu.labels_to_turns_groups([speech], [centres], [regions], [labels])[0]
+        else:
+            labels = cluster.relabel_by_first_appearance(labels)
+            spans = labels_to_turns(speech, centres, regions, labels)
+        segments = [(s, e, rttm.speaker_label(k)) for s, e, k in spans]
         details.update(labels=labels, embeddings=embs, affinity=K, window_starts=starts)
     if rttm_filepath and (world is None or _rank() == 0):
         with open(rttm_filepath, "w") as f:
@@ -239,7 +249,7 @@ def diarize_audio(audio_filepath: str | Path | dict, min_speech_duration_s: floa
 def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s: float, min_speakers: int, max_speakers: int,
                    rttm_filepaths=None, *, clustering: str = "ahc_gpu", clustering_threshold: float = 0.70, window_s: float = 2.0,
                    hop_s: float = 0.25, vad_scorer=None, center_embeddings: bool = True, return_details: bool = False,
-                   speaker_bounds: bool = False, vad: str = "host"):
+                   speaker_bounds: bool = False, vad: str = "host", turns: str = "host"):
     """`diarize_audio(..., clustering="ahc_gpu")` for a list of recordings at once -> one segment list per recording (with
     `return_details`: a list of (segments, details)); the RTTM of recording i goes to `rttm_filepaths[i]` when that is given.
 
@@ -253,11 +263,16 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
 
     `vad="device"` (default "host"): every recording is uploaded first (the same buffer, one window of zeros after each), the speech
     regions of all of them come from the two launches of `vad_gpu` on that buffer, and the windows are embedded from it: the signal is
-    never framed on the host.  `vad_scorer`: None or a `vad.EnergyScorer`, as in `diarize_audio`."""
+    never framed on the host.  `vad_scorer`: None or a `vad.EnergyScorer`, as in `diarize_audio`.
+
+    `turns="device"` (default "host"): after the grouped AHC, the labels of ALL recordings are relabelled and turned into turns by ONE
+    call of `turns_gpu.labels_to_turns_groups` (one upload, one launch, one download) instead of a Python loop per recording, region
+    and run; `details["labels"]` are the device's relabelled labels.  The same labels and turns, value for value."""
     if clustering != "ahc_gpu":
         raise ValueError(f"diarize_audios clusters all recordings in one driver, which exists for clustering='ahc_gpu' only, got {clustering!r}")
     _check_speaker_bounds(speaker_bounds, clustering)
     _check_vad(vad, vad_scorer, True)
+    _check_turns(turns, True)
     audios = list(audios)
     rttm_filepaths = [None] * len(audios) if rttm_filepaths is None else list(rttm_filepaths)
     if len(rttm_filepaths) != len(audios):
@@ -299,12 +314,20 @@ def diarize_audios(audios, min_speech_duration_s: float, min_silence_duration_s:
         labels = ahc_gpu.ahc_cosine_groups(_device_rows(X, True, clustering), sizes, clustering_threshold,
                                            **_cluster_bounds(speaker_bounds, min_speakers, max_speakers, sizes))
     out = []
-    for r, a, b, lab, path in zip(recs, bounds[:-1], bounds[1:], labels, rttm_filepaths):
+    turned = [None] * len(recs)
+    if turns == "device" and offset:                     # ONE launch for the folder
+        from . import turns_gpu
+        turned = turns_gpu.labels_to_turns_groups([r["speech"] for r in recs], [r["centres"] for r in recs], [r["regions"] for r in recs], labels)
+    for r, a, b, lab, path, done in zip(recs, bounds[:-1], bounds[1:], labels, rttm_filepaths, turned):
         segments: list[tuple[float, float, str | int]] = []
         details = {"speech": r["speech"], "labels": np.zeros(0, dtype=int), "embeddings": np.zeros((0, 192), np.float32)}
         if r["speech"]:
-            lab = cluster.relabel_by_first_appearance(lab)
-            segments = [(s, e, rttm.speaker_label(k)) for s, e, k in labels_to_turns(r["speech"], r["centres"], r["regions"], lab)]
+            if done is not None:
+                lab, spans = done
+            else:
+                lab = cluster.relabel_by_first_appearance(lab)
+                spans = labels_to_turns(r["speech"], r["centres"], r["regions"], lab)
+            segments = [(s, e, rttm.speaker_label(k)) for s, e, k in spans]
             details.update(labels=lab, embeddings=embs[a:b], affinity=None, window_starts=r["starts"])
         if path:
             with open(path, "w") as f:
@@ -339,6 +362,13 @@ def _check_vad(vad_route: str, vad_scorer, hip_path: bool) -> None:
         vad_gpu.energy_scorer(vad_scorer)
         if not hip_path:
             raise RuntimeError("vad='device' runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
+
+
+def _check_turns(turns_route: str, hip_path: bool) -> None:
+    if turns_route not in ("host", "device"):
+        raise ValueError(f"turns must be 'host' or 'device', got {turns_route!r}")
+    if turns_route == "device" and not hip_path:
+        raise RuntimeError("turns='device' runs on the HIP path (no injected encoder, a visible GPU); there is no CPU fallback")
 
 
 def _speech_regions_device(signal_dev, first_sample, n_samples, sr: int, min_speech_duration_s: float, min_silence_duration_s: float,
@@ -482,10 +512,12 @@ def extract_speaker_stems(audio: str | Path | dict, segments: list[tuple[float, 
 
 class Diarizer:
     def __init__(self, hparams: DiarizationParameters, encoder: Encoder | None = None, clustering: str = "spectral",
-                 speaker_bounds: bool = False, vad: str = "host"):
+                 speaker_bounds: bool = False, vad: str = "host", *, turns: str = "host"):
         _check_speaker_bounds(speaker_bounds, clustering)
         _check_vad(vad, None, encoder is None)
+        _check_turns(turns, encoder is None)
         self.vad = vad
+        self.turns = turns
         self.hparams = hparams
         self.encoder = encoder
         self.clustering = clustering
@@ -496,7 +528,8 @@ class Diarizer:
         segments = diarize_audio(apath, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                                  min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepath=rttm_filepath,
                                  encoder=self.encoder, clustering=self.clustering,
-                                 clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds, vad=self.vad)
+                                 clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds, vad=self.vad,
+                                 turns=self.turns)
         segments = [s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s]
         return sorted(segments)
 
@@ -508,7 +541,7 @@ class Diarizer:
         many = diarize_audios(apaths, hp.min_speech_duration_s, min_silence_duration_s=hp.min_silence_duration_s,
                               min_speakers=hp.min_speakers, max_speakers=hp.max_speakers, rttm_filepaths=rttm_filepaths,
                               clustering=self.clustering, clustering_threshold=hp.clustering_threshold, speaker_bounds=self.speaker_bounds,
-                              vad=self.vad)
+                              vad=self.vad, turns=self.turns)
         return [sorted(s for s in segments if s[1] - s[0] >= hp.min_speech_duration_s) for segments in many]
 
     def merge_segments(self, segments):

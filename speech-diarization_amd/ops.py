@@ -23,6 +23,7 @@ _CUT_LAUNCHABLE = frozenset(N.CUT_ENTRIES)              # ... and, in a set of i
 _KMEANS_LAUNCHABLE = frozenset(N.KMEANS_ENTRIES)        # ... and the table of sd_hip_kmeans.h
 _VAD_LAUNCHABLE = frozenset(N.VAD_ENTRIES)              # ... and the table of sd_hip_vad.h
 _SCD_LAUNCHABLE = frozenset(N.SCD_ENTRIES)              # ... and the table of sd_hip_scd.h
+_TURNS_LAUNCHABLE = frozenset(N.TURNS_ENTRIES)          # ... and the table of sd_hip_turns.h
 
 
 def _current_stream(index: int) -> int:
@@ -38,7 +39,7 @@ def launch(name: str, on: torch.Tensor, *args) -> None:
     """The one checked launch of the binding: entry `name` of the C ABI on the device of `on`, `args` followed by the current stream
     of that device (every launching entry takes its stream last), a non-zero status raised as `SdError` under the same `name`."""
     if (name not in _LAUNCHABLE and name not in _CUT_LAUNCHABLE and name not in _KMEANS_LAUNCHABLE and name not in _VAD_LAUNCHABLE
-            and name not in _SCD_LAUNCHABLE):
+            and name not in _SCD_LAUNCHABLE and name not in _TURNS_LAUNCHABLE):
         raise ValueError(f"{name!r} is in none of the prototype tables of _native: not an entry of libsd_hip.so")
     with torch.cuda.device(on.device.index):            # by index: this runs once per launch, and torch resolves an int at once
         N.check(getattr(N.load(), name)(*args, _stream(on)), name)
@@ -769,6 +770,40 @@ def scd_split_grouped(rows: torch.Tensor, first_row: torch.Tensor, seg_start: to
            n_peaks.data_ptr(), n_pieces.data_ptr(), piece_start.data_ptr() or None, piece_end.data_ptr() or None, _ptr(sims) or None,
            _ptr(mask) or None, bad.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
     return n_peaks, n_pieces, piece_start, piece_end, sims, mask, bad
+
+
+# ----------------------------------------------------------------------------- speaker turns (include/sd_hip_turns.h)
+
+def turns_grouped(first_window: torch.Tensor, first_region: torch.Tensor, region_first_window: torch.Tensor, centre: torch.Tensor,
+                  region_start: torch.Tensor, n_frames: torch.Tensor, frame_s: float, labels: torch.Tensor,
+                  ws: Workspace | torch.Tensor | None = None):
+    """`cluster.relabel_by_first_appearance` and the runs of `diarization_baseline.labels_to_turns` for many recordings in one launch:
+    recording g its windows [first_window[g], first_window[g + 1]) and its regions [first_region[g], first_region[g + 1]) (int32
+    [G + 1], non-decreasing, 0 first), region r its windows [region_first_window[r], region_first_window[r + 1]) (int32 [R + 1]), the
+    window centres f64 [W] in seconds, region_start f64 [R], n_frames int32 [R], labels int32 [W] -> (new_labels int32 [W], n_runs
+    int32 [G], run_region, run_first, run_end, run_label int32 [W] with a recording's runs from first_window[g] on, bad int32 [G]; all
+    still on the device).  `bad` is non-zero, and the recording has no runs, where a label is not below the recording's window count
+    or a table, the centres or the frame counts break their promise (include/sd_hip_turns.h).  `ws`: a `Workspace`, or a uint8 tensor
+    of at least sd_turns_workspace_bytes(W, G), to reuse across calls (allocated when None)."""
+    _need_cuda(first_window, first_region, region_first_window, centre, region_start, n_frames, labels)
+    G, R, W = first_window.numel() - 1, region_first_window.numel() - 1, labels.numel()
+    _table("first_window", first_window, torch.int32, G + 1)
+    _table("first_region", first_region, torch.int32, G + 1)
+    _table("region_first_window", region_first_window, torch.int32, R + 1)
+    _table("centre", centre, torch.float64, W)
+    _table("region_start", region_start, torch.float64, R)
+    _table("n_frames", n_frames, torch.int32, R)
+    _table("labels", labels, torch.int32, W)
+    dev = labels.device
+    new_labels, run_region, run_first, run_end, run_label = (torch.empty((W,), dtype=torch.int32, device=dev) for _ in range(5))
+    n_runs, bad = (torch.empty((G,), dtype=torch.int32, device=dev) for _ in range(2))
+    ws = _workspace(ws, int(N.load().sd_turns_workspace_bytes(W, G)), dev)
+    launch("sd_turns_grouped", labels, first_window.data_ptr(), first_region.data_ptr(), G, region_first_window.data_ptr(), R,
+           centre.data_ptr() or None, W, region_start.data_ptr() or None, n_frames.data_ptr() or None, C.c_double(frame_s),
+           labels.data_ptr() or None, new_labels.data_ptr() or None, n_runs.data_ptr(), run_region.data_ptr() or None,
+           run_first.data_ptr() or None, run_end.data_ptr() or None, run_label.data_ptr() or None, bad.data_ptr(), ws.data_ptr(),
+           ws.numel() * ws.element_size())
+    return new_labels, n_runs, run_region, run_first, run_end, run_label, bad
 
 
 # ----------------------------------------------------------------------------- density clustering (include/sd_hip_hdbscan.h)

@@ -35,6 +35,8 @@ def main():
                     help="with --clustering ahc_gpu: clamp the cluster count into [--min-speakers, --max-speakers] by a dendrogram cut on the device")
     ap.add_argument("--vad", default="host", choices=("host", "device"),
                     help="device: the speech regions from the two launches of vad_gpu.py on the uploaded signal, which is embedded from the same buffer")
+    ap.add_argument("--turns", default="host", choices=("host", "device"),
+                    help="device: relabelling and labels_to_turns in one launch of turns_gpu.py instead of a Python loop per window, region and run")
     ap.add_argument("--gpus", type=int, default=1, help="ranks to start (one per GPU) when not already under torchrun")
     a = ap.parse_args()
     if a.speaker_bounds and a.clustering != "ahc_gpu":
@@ -57,7 +59,7 @@ def main():
     t0 = time.time()
     segs, det = db.diarize_audio(a.audio, 0.35, 0.1, a.min_speakers, a.max_speakers, rttm_filepath=a.rttm or os.path.splitext(a.audio)[0] + ".rttm",
                                  clustering=a.clustering, return_details=True, world="dist" if world > 1 else None,
-                                 speaker_bounds=a.speaker_bounds, vad=a.vad)
+                                 speaker_bounds=a.speaker_bounds, vad=a.vad, turns=a.turns)
     if rank == 0:
         print(f"world={world} backend={tdist.get_backend() if world > 1 else 'none'} windows={det['embeddings'].shape[0]} "
               f"speakers={len({k for _, _, k in segs})} turns={len(segs)} wall={time.time() - t0:.2f}s")
