@@ -14,6 +14,9 @@ finite and large, survives fmaxf, ReLU and NaN-dropping clamps) and 0x00.
 
 Imported by the tests (not a fixture file); works on the CPU too, where the self-test of tests/test_buffer_rules.py runs.
 """
+import itertools
+import weakref
+
 import torch
 
 GUARD_BYTES = 4 << 20
@@ -32,9 +35,20 @@ def _first_changed(region: torch.Tensor, byte: int):
     return int(torch.nonzero(bad.reshape(-1))[0, 0])
 
 
+_LIVE = weakref.WeakSet()          # every Guarded that still exists: tests/helpers/captured.py snapshots and restores their payloads
+_SERIAL = itertools.count()
+
+
+def live() -> list:
+    """The guarded buffers that exist now, in the order they were made."""
+    return sorted(_LIVE, key=lambda g: g.serial)
+
+
 class Guarded:
     def __init__(self, nbytes: int, fill: int, device, guard: int = GUARD_BYTES, name: str = ""):
         self.nbytes, self.name, self.guard = int(nbytes), name, int(guard)
+        self.serial = next(_SERIAL)
+        _LIVE.add(self)
         self.raw = torch.full((2 * guard + 256 + self.nbytes,), GUARD_BYTE, dtype=torch.uint8, device=device)
         self.off = guard + (-(self.raw.data_ptr() + guard)) % 256
         self.payload = self.raw[self.off:self.off + self.nbytes]

@@ -10,6 +10,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import ahc_ref as A  # noqa: E402
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 import spectral_ref as R  # noqa: E402
 from launch_log import expect_launches  # noqa: E402
@@ -137,13 +138,13 @@ def test_both_entries_at_exact_buffer_sizes(dev, n, d, ld):
         gc = G.guarded_from(torch.from_numpy(count), dev, "count")
         gn, gb = G.guarded(n * 4, poison, dev, "nn"), G.guarded(n * 4, poison, dev, "best")
         gw = G.guarded(need, poison, dev, "ws")
-        assert lib.sd_ahc_nearest_f32(gS.ptr, ld, n, d, gi.ptr, gn.ptr, gb.ptr, gw.ptr, need - 1, None) == -3        # one byte short
-        N.check(lib.sd_ahc_nearest_f32(gS.ptr, ld, n, d, gi.ptr, gn.ptr, gb.ptr, gw.ptr, need, None), "sd_ahc_nearest_f32")
+        assert CAP.call("sd_ahc_nearest_f32", gS.ptr, ld, n, d, gi.ptr, gn.ptr, gb.ptr, gw.ptr, need - 1) == -3        # one byte short
+        N.check(CAP.call("sd_ahc_nearest_f32", gS.ptr, ld, n, d, gi.ptr, gn.ptr, gb.ptr, gw.ptr, need), "sd_ahc_nearest_f32")
         torch.cuda.synchronize()
         G.assert_guards_intact(gS, gi, gn, gb, gw)
         assert torch.equal(gn.view(torch.int32), want_nn) and torch.equal(_bits(gb.view(torch.float32)), _bits(want_best)), poison
         gt, gm = G.guarded(n * 4, poison, dev, "target"), G.guarded(4, poison, dev, "n_merged")
-        N.check(lib.sd_ahc_merge_f32(gS.ptr, ld, n, d, gc.ptr, gi.ptr, gn.ptr, gb.ptr, thr, gt.ptr, gm.ptr, None), "sd_ahc_merge_f32")
+        N.check(CAP.call("sd_ahc_merge_f32", gS.ptr, ld, n, d, gc.ptr, gi.ptr, gn.ptr, gb.ptr, thr, gt.ptr, gm.ptr), "sd_ahc_merge_f32")
         torch.cuda.synchronize()
         G.assert_guards_intact(gS, gc, gi, gn, gb, gt, gm)
         w_s, w_c, w_i, w_t, w_m = A.merge_f32(S[:, :d], count, inv, want_nn.cpu().numpy(), want_best.cpu().numpy(), thr)
@@ -164,12 +165,12 @@ def test_lib_refuses_on_the_device_too(dev):
     nn = torch.full((64,), 7, dtype=torch.int32, device=dev)
     best = torch.full((64,), 7.0, device=dev)
     ws = torch.empty(int(lib.sd_ahc_nearest_workspace_bytes(64, 192)), dtype=torch.uint8, device=dev)
-    assert lib.sd_ahc_nearest_f32(S.data_ptr(), 190, 64, 190, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), None) == -1
-    assert lib.sd_ahc_nearest_f32(S.data_ptr() + 4, 192, 63, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), None) == -1
-    assert lib.sd_ahc_nearest_f32(S.data_ptr(), 192, 64, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel() - 1, None) == -3
+    assert CAP.call("sd_ahc_nearest_f32", S.data_ptr(), 190, 64, 190, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel()) == -1
+    assert CAP.call("sd_ahc_nearest_f32", S.data_ptr() + 4, 192, 63, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel()) == -1
+    assert CAP.call("sd_ahc_nearest_f32", S.data_ptr(), 192, 64, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel() - 1) == -3
     torch.cuda.synchronize()
     assert bool((nn == 7).all()) and bool((best == 7.0).all())
-    assert lib.sd_ahc_nearest_f32(S.data_ptr(), 192, 64, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), None) == 0
+    assert CAP.call("sd_ahc_nearest_f32", S.data_ptr(), 192, 64, 192, inv.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel()) == 0
     torch.cuda.synchronize()
     assert float(best[5]) == 192.0 and int(nn[0]) == 1 and int(nn[5]) == 0
 

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
 import ahc_grouped_ref as AG  # noqa: E402
 import ahc_ref as A  # noqa: E402
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 import spectral_ref as R  # noqa: E402
 from launch_log import expect_launches, launches  # noqa: E402
@@ -173,8 +174,8 @@ def test_entry_at_exact_buffer_sizes(dev, n, d, ld, max_group):
         gn, gb, gbad = G.guarded(n * 4, poison, dev, "nn"), G.guarded(n * 4, poison, dev, "best"), G.guarded(4, poison, dev, "bad")
         gw = G.guarded(need, poison, dev, "ws")
         args = (gS.ptr, ld, n, d, gi.ptr, gg.ptr, max_group, gn.ptr, gb.ptr, gbad.ptr, gw.ptr)
-        assert lib.sd_ahc_nearest_grouped_f32(*args, need - 1, None) == -3                 # one byte short
-        N.check(lib.sd_ahc_nearest_grouped_f32(*args, need, None), "sd_ahc_nearest_grouped_f32")
+        assert CAP.call("sd_ahc_nearest_grouped_f32", *args, need - 1) == -3                 # one byte short
+        N.check(CAP.call("sd_ahc_nearest_grouped_f32", *args, need), "sd_ahc_nearest_grouped_f32")
         torch.cuda.synchronize()
         G.assert_guards_intact(gS, gi, gg, gn, gb, gbad, gw)
         assert torch.equal(gn.view(torch.int32), want_nn) and torch.equal(_bits(gb.view(torch.float32)), _bits(want_best)), poison

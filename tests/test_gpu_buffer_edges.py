@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 from kernel_selection import CONV_KERNELS, restore_conv_kernel, select_conv_kernel  # noqa: E402
 
@@ -50,8 +51,8 @@ def _arg(a):
 
 
 def call(name, *args):
-    """The raw entry on the current stream -> its status."""
-    return getattr(N.load(), name)(*[_arg(a) for a in args], _stream())
+    """The raw entry on the current stream -> its status (eagerly, or captured and replayed inside tests/helpers/captured.py's scopes)."""
+    return CAP.call(name, *args)
 
 
 def ok(name, *args):
@@ -526,7 +527,7 @@ def _conv_packed(T_list, cin, cout, k, dil, epilogues):
             else:
                 kw.update(bias=A.data(d["b"].float(), "bias"), scale=A.data(d["scale"].float(), "scale"), shift=A.data(d["shift"].float(), "shift"))
             a = _args(**kw)
-            N.check(N.load().sd_conv1d_cl_packed_f32(C.byref(a), fs_g.ptr, B, _stream()), "sd_conv1d_cl_packed_f32")
+            ok("sd_conv1d_cl_packed_f32", C.byref(a), fs_g, B)
             return res
         got = under_poisons(dev, one)
         if epilogues:                                                       # test_packed_conv_epilogues_and_tile_counts
@@ -565,7 +566,7 @@ def _seg_gemm(M, cin, cout):
             scr = A.scratch(need, "scratch")
             a = _args(x=x_g, lda=cin + 8, a_col0=a_col0, w=w_g, y=y, ldo=cout + 12, o_col0=4, M=M, T=1, cin=cin, cin_pad=wp.shape[2], cout=cout,
                       taps=1, dil=1, bias=bias, act=_ACT["relu"], scale=sc, shift=sh, act2=_ACT["sigmoid"])
-            N.check(N.load().sd_seg_gemm_f32(C.byref(a), scr.ptr if need else None, need, _stream()), "sd_seg_gemm_f32")
+            ok("sd_seg_gemm_f32", C.byref(a), scr.ptr if need else None, need)
             return {"y": yv}
         got = under_poisons(dev, one)["y"]
         assert (got.double() - ref).abs().max() < 2e-6                      # test_seg_gemm_matches_torch
@@ -611,7 +612,7 @@ def _res2net_chain(B, T, dil, n, ld):
                 L.scale, L.shift = A.data(d["scale"], "scale").ptr, A.data(d["shift"], "shift").ptr
                 L.cin, L.cin_pad, L.cout, L.taps, L.dil, L.w_dtype = 128, 128, 128, 3, dil, N.SD_DT_F16
             ws = A.scratch(need, "ws")
-            N.check(lib.sd_res2net_chain_f16(r_g.ptr, ld, B, T, arr, n, ws.ptr, need, _stream()), "sd_res2net_chain_f16")
+            ok("sd_res2net_chain_f16", r_g, ld, B, T, arr, n, ws, need)
             return {"r": r_g.view(F16, B * T, ld)}
         got = under_poisons(dev, one)["r"].double()
         assert torch.equal(got[:, :128], r[:, :128].double()) and torch.equal(got[:, 128 * (n + 1):], r[:, 128 * (n + 1):].double())
@@ -1125,7 +1126,7 @@ def _fbank(kind, sr, B, n, mean_norm=True):
         def one(A):
             w_g, ws = A.data(wav, "wav"), A.scratch(need, "ws")
             o_g, ov = A.out_cut(B * T, nm, nm + 8, F32, "out")
-            N.check(N.load().sd_fbank_f32(plan.handle, w_g.ptr, B, n, int(mean_norm), o_g.ptr, nm + 8, ws.ptr, need, _stream()), "sd_fbank_f32")
+            ok("sd_fbank_f32", plan.handle, w_g, B, n, int(mean_norm), o_g, nm + 8, ws, need)
             return {"out": ov}
         got = under_poisons(dev, one)["out"]
         assert torch.equal(got.view(B, T, nm), want)
@@ -1159,8 +1160,7 @@ def _fbank_windows(kind, sr, n_total, n, starts):
         def one(A):
             s_g, st_g, ws = A.data(sig, "signal"), A.data(torch.tensor(starts, dtype=I64), "starts"), A.scratch(need, "ws")
             o_g, ov = A.out_cut(B * T, nm, nm + 8, F32, "out")
-            N.check(N.load().sd_fbank_windows_f32(plan.handle, s_g.ptr, n_total, st_g.ptr, B, n, 1, o_g.ptr, nm + 8, ws.ptr, need, _stream()),
-                    "sd_fbank_windows_f32")
+            ok("sd_fbank_windows_f32", plan.handle, s_g, n_total, st_g, B, n, 1, o_g, nm + 8, ws, need)
             return {"out": ov}
         assert torch.equal(under_poisons(dev, one)["out"].view(B, T, nm), want)
     return run
@@ -1223,8 +1223,7 @@ def _fbank_packed(n_total, spans):
             st_g, ln_g = A.data(torch.tensor(starts, dtype=I64), "starts"), A.data(torch.tensor(lens, dtype=I32), "lens")
             fs_g = A.data(torch.from_numpy(fs), "frame_start")
             o_g, ov = A.out_cut(M, nm, nm + 8, F32, "out")
-            N.check(N.load().sd_fbank_packed_f32(plan.handle, s_g.ptr, n_total, st_g.ptr, ln_g.ptr, fs_g.ptr, B, M, n_max, o_g.ptr, nm + 8, ws.ptr,
-                                                 need, _stream()), "sd_fbank_packed_f32")
+            ok("sd_fbank_packed_f32", plan.handle, s_g, n_total, st_g, ln_g, fs_g, B, M, n_max, o_g, nm + 8, ws, need)
             return {"out": ov}
         got = under_poisons(dev, one)["out"]
         for s, (a, n) in enumerate(spans):                                  # bitwise the span alone (test_fbank_packed_is_bitwise_the_span_alone)
@@ -1381,12 +1380,12 @@ def _forward(geom, prec, B, T, lens=False, oracle=False, sel=None):
                 f_g, ws = A.data(feats, "feats"), A.scratch(need, "workspace")
                 emb = A.scratch(B * dim * 4, "emb")
                 args = (W, f_g.ptr, B, T) + ((A.data(rel, "rel_len").ptr,) if lens else ()) + (emb.ptr, ws.ptr)
-                st = getattr(lib, entry)(*args, need - 1, _stream())
+                st = call(entry, *args, need - 1)
                 torch.cuda.synchronize()
                 assert st == SD_ERR_WORKSPACE, (st, N.last_error())
                 assert bool((emb.payload == A.poison).all()), "a refused call wrote to emb"
                 G.assert_guards_intact(*A.bufs)
-                N.check(getattr(lib, entry)(*args, need, _stream()), entry)
+                ok(entry, *args, need)
                 return {"emb": emb.view(F32, B, dim)}
             got = under_poisons(dev, one)["emb"]                             # (finite under lengths too: every row of _rel_for keeps a frame)
             want = eng.embed(wav, rel).cpu()
@@ -1423,10 +1422,10 @@ def _forward_packed(geom, T_list, oracle=False, sel=None):
             def one(A):
                 f_g, fs_g, ws = A.data(feats, "feats"), A.data(torch.from_numpy(fs), "frame_start"), A.scratch(need, "workspace")
                 emb = A.scratch(B * dim * 4, "emb")
-                st = lib.sd_ecapa_forward_packed_f32(W, f_g.ptr, fs_g.ptr, B, M, emb.ptr, ws.ptr, need - 1, _stream())
+                st = call("sd_ecapa_forward_packed_f32", W, f_g, fs_g, B, M, emb, ws, need - 1)
                 torch.cuda.synchronize()
                 assert st == SD_ERR_WORKSPACE and bool((emb.payload == A.poison).all())
-                N.check(lib.sd_ecapa_forward_packed_f32(W, f_g.ptr, fs_g.ptr, B, M, emb.ptr, ws.ptr, need, _stream()), "sd_ecapa_forward_packed_f32")
+                ok("sd_ecapa_forward_packed_f32", W, f_g, fs_g, B, M, emb, ws, need)
                 return {"emb": emb.view(F32, B, dim)}
             got = under_poisons(dev, one)["emb"]
             want = eng.embed_spans(sig, np.asarray(starts), np.asarray(lens), frame_budget=M).cpu()

@@ -3,7 +3,6 @@
 bit), random inputs against numpy f64 under the summation bound, guard bands around every pointer, `whiten_l2_rows` against
 `cluster.whiten_l2`, `resegment(device="cuda")` against the host route, the context spans against one-at-a-time embedding, and the
 whole `diagnose` on a synthetic conversation.  Every kernel's launch label is asserted (tests/test_diag_rules.py holds the list)."""
-import ctypes as C
 import os
 import sys
 
@@ -13,6 +12,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
+import captured as CAP  # noqa: E402
 import diag_cases as DC  # noqa: E402
 import guarded as G  # noqa: E402
 from launch_log import expect_launches  # noqa: E402
@@ -211,13 +211,12 @@ def test_no_entry_leaves_its_buffers(dev, n, d, ld):
     xp[:, :d] = xv
     ldg, ldw, ldo, k = d + 3, d + 1, ld, 5
     labels = rng.integers(-1, k + 1, size=n).astype(np.int32)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     x = G.guarded_from(torch.from_numpy(xp), dev, "x")
     mean = G.guarded(d * 8, 0x7B, dev, "mean")
     gram = G.guarded(d * ldg * 8, 0x7B, dev, "gram")
     need = int(lib.sd_whiten_stats_workspace_bytes(n, d))
     ws = G.guarded(need, 0xFF, dev, "ws")
-    N.check(lib.sd_whiten_stats_f64(x.ptr, ld, n, d, mean.ptr, gram.ptr, ldg, ws.ptr, need, stream), "sd_whiten_stats_f64")
+    N.check(CAP.call("sd_whiten_stats_f64", x.ptr, ld, n, d, mean.ptr, gram.ptr, ldg, ws.ptr, need), "sd_whiten_stats_f64")
     torch.cuda.synchronize()
     g = gram.view(torch.float64, d, ldg)
     G.assert_columns_keep(g, 0, d, 0x7B, "gram")
@@ -229,7 +228,7 @@ def test_no_entry_leaves_its_buffers(dev, n, d, ld):
     w_np = rng.standard_normal((d, ldw))
     w = G.guarded_from(torch.from_numpy(w_np), dev, "w")
     out = G.guarded(n * ldo * 4, 0x7B, dev, "out")
-    N.check(lib.sd_whiten_apply_f64(x.ptr, ld, n, d, mean.ptr, w.ptr, ldw, 1e-9, out.ptr, ldo, stream), "sd_whiten_apply_f64")
+    N.check(CAP.call("sd_whiten_apply_f64", x.ptr, ld, n, d, mean.ptr, w.ptr, ldw, 1e-9, out.ptr, ldo), "sd_whiten_apply_f64")
     torch.cuda.synchronize()
     o = out.view(torch.float32, n, ldo)
     G.assert_columns_keep(o, 0, d, 0x7B, "out")
@@ -239,7 +238,7 @@ def test_no_entry_leaves_its_buffers(dev, n, d, ld):
     lab = G.guarded_from(torch.from_numpy(labels), dev, "labels")
     cen = G.guarded(k * ldo * 4, 0x7B, dev, "centres")
     cnt = G.guarded(k * 4, 0x7B, dev, "count")
-    N.check(lib.sd_label_centroids_f32(x.ptr, ld, n, d, lab.ptr, k, 1e-9, cen.ptr, ldo, cnt.ptr, stream), "sd_label_centroids_f32")
+    N.check(CAP.call("sd_label_centroids_f32", x.ptr, ld, n, d, lab.ptr, k, 1e-9, cen.ptr, ldo, cnt.ptr), "sd_label_centroids_f32")
     torch.cuda.synchronize()
     c = cen.view(torch.float32, k, ldo)
     G.assert_columns_keep(c, 0, d, 0x7B, "centres")

@@ -11,6 +11,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 import hdbscan_ref as H  # noqa: E402
 from launch_log import expect_launches  # noqa: E402
@@ -238,16 +239,16 @@ def test_both_entries_at_exact_buffer_sizes(dev, n, d, ld):
     for poison in G.POISONS:
         gS = G.guarded_from(flat, dev, "rows")
         gc, gw = G.guarded(n * 4, poison, dev, "core"), G.guarded(need_c, poison, dev, "core ws")
-        assert lib.sd_hdb_core_f32(gS.ptr, ld, n, d, k, gc.ptr, gw.ptr, need_c - 1, None) == -3                    # one byte short
-        N.check(lib.sd_hdb_core_f32(gS.ptr, ld, n, d, k, gc.ptr, gw.ptr, need_c, None), "sd_hdb_core_f32")
+        assert CAP.call("sd_hdb_core_f32", gS.ptr, ld, n, d, k, gc.ptr, gw.ptr, need_c - 1) == -3                    # one byte short
+        N.check(CAP.call("sd_hdb_core_f32", gS.ptr, ld, n, d, k, gc.ptr, gw.ptr, need_c), "sd_hdb_core_f32")
         torch.cuda.synchronize()
         G.assert_guards_intact(gS, gc, gw)
         assert torch.equal(_bits(gc.view(torch.float32)), _bits(want_core)), poison
         gp = G.guarded_from(torch.from_numpy(comp), dev, "comp")
         gn, gb = G.guarded(n * 4, poison, dev, "nn"), G.guarded(n * 4, poison, dev, "best")
         go = G.guarded(need_o, poison, dev, "outgoing ws")
-        assert lib.sd_hdb_outgoing_f32(gS.ptr, ld, n, d, gc.ptr, gp.ptr, gn.ptr, gb.ptr, go.ptr, need_o - 1, None) == -3
-        N.check(lib.sd_hdb_outgoing_f32(gS.ptr, ld, n, d, gc.ptr, gp.ptr, gn.ptr, gb.ptr, go.ptr, need_o, None), "sd_hdb_outgoing_f32")
+        assert CAP.call("sd_hdb_outgoing_f32", gS.ptr, ld, n, d, gc.ptr, gp.ptr, gn.ptr, gb.ptr, go.ptr, need_o - 1) == -3
+        N.check(CAP.call("sd_hdb_outgoing_f32", gS.ptr, ld, n, d, gc.ptr, gp.ptr, gn.ptr, gb.ptr, go.ptr, need_o), "sd_hdb_outgoing_f32")
         torch.cuda.synchronize()
         G.assert_guards_intact(gS, gc, gp, gn, gb, go)
         assert torch.equal(gn.view(torch.int32), want_nn) and torch.equal(_bits(gb.view(torch.float32)), _bits(want_best)), poison
@@ -264,17 +265,17 @@ def test_lib_refuses_on_the_device_too(dev):
     best = torch.full((64,), 7.0, device=dev)
     need = int(lib.sd_hdb_outgoing_workspace_bytes(64, 192))
     ws = torch.empty(max(need, int(lib.sd_hdb_core_workspace_bytes(64, 192, 16))), dtype=torch.uint8, device=dev)
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 192, 64, 192, 17, core.data_ptr(), ws.data_ptr(), ws.numel(), None) == -2
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 192, 64, 192, 64, core.data_ptr(), ws.data_ptr(), ws.numel(), None) == -2
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 192, 10, 192, 10, core.data_ptr(), ws.data_ptr(), ws.numel(), None) == -1
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 190, 64, 190, 2, core.data_ptr(), ws.data_ptr(), ws.numel(), None) == -1
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 192, 64, 192, 2, core.data_ptr(), ws.data_ptr(), 0, None) == -3
-    assert lib.sd_hdb_outgoing_f32(S.data_ptr() + 4, 192, 63, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), None) == -1
-    assert lib.sd_hdb_outgoing_f32(S.data_ptr(), 192, 64, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), need - 1, None) == -3
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 192, 64, 192, 17, core.data_ptr(), ws.data_ptr(), ws.numel()) == -2
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 192, 64, 192, 64, core.data_ptr(), ws.data_ptr(), ws.numel()) == -2
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 192, 10, 192, 10, core.data_ptr(), ws.data_ptr(), ws.numel()) == -1
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 190, 64, 190, 2, core.data_ptr(), ws.data_ptr(), ws.numel()) == -1
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 192, 64, 192, 2, core.data_ptr(), ws.data_ptr(), 0) == -3
+    assert CAP.call("sd_hdb_outgoing_f32", S.data_ptr() + 4, 192, 63, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel()) == -1
+    assert CAP.call("sd_hdb_outgoing_f32", S.data_ptr(), 192, 64, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), need - 1) == -3
     torch.cuda.synchronize()
     assert bool((nn == 7).all()) and bool((best == 7.0).all()) and bool((core == 7.0).all())
-    assert lib.sd_hdb_outgoing_f32(S.data_ptr(), 192, 64, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), None) == 0
-    assert lib.sd_hdb_core_f32(S.data_ptr(), 192, 64, 192, 3, core.data_ptr(), ws.data_ptr(), ws.numel(), None) == 0
+    assert CAP.call("sd_hdb_outgoing_f32", S.data_ptr(), 192, 64, 192, core.data_ptr(), comp.data_ptr(), nn.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel()) == 0
+    assert CAP.call("sd_hdb_core_f32", S.data_ptr(), 192, 64, 192, 3, core.data_ptr(), ws.data_ptr(), ws.numel()) == 0
     torch.cuda.synchronize()
     assert float(best[5]) == 7.0 and int(nn[0]) == 1 and int(nn[5]) == 0 and float(core[9]) == 192.0
 

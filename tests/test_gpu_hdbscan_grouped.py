@@ -11,6 +11,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 import hdbscan_grouped_ref as HG  # noqa: E402
 import hdbscan_ref as H  # noqa: E402
@@ -312,8 +313,8 @@ def test_entries_at_exact_buffer_sizes(dev, n, d, ld, max_group, k):
             gbad = G.guarded(4, poison, dev, "bad")
             gw = G.guarded(nc, poison, dev, "core ws")
             args = (gS.ptr, ld, n, d, k, gg.ptr, mg, gc.ptr, gbad.ptr, gw.ptr)
-            assert lib.sd_hdb_core_grouped_f32(*args, nc - 1, None) == -3                      # one byte short
-            N.check(lib.sd_hdb_core_grouped_f32(*args, nc, None), "sd_hdb_core_grouped_f32")
+            assert CAP.call("sd_hdb_core_grouped_f32", *args, nc - 1) == -3                      # one byte short
+            N.check(CAP.call("sd_hdb_core_grouped_f32", *args, nc), "sd_hdb_core_grouped_f32")
             torch.cuda.synchronize()
             G.assert_guards_intact(gS, gg, gc, gbad, gw)
             assert (int(gbad.view(torch.int32)[0]) == 0) == good, (poison, mg)
@@ -324,8 +325,8 @@ def test_entries_at_exact_buffer_sizes(dev, n, d, ld, max_group, k):
             gn, gb, gbad2 = G.guarded(n * 4, poison, dev, "nn"), G.guarded(n * 4, poison, dev, "best"), G.guarded(4, poison, dev, "bad")
             gwo = G.guarded(no, poison, dev, "outgoing ws")
             args = (gS.ptr, ld, n, d, gci.ptr, gcomp.ptr, gg.ptr, mg, gn.ptr, gb.ptr, gbad2.ptr, gwo.ptr)
-            assert lib.sd_hdb_outgoing_grouped_f32(*args, no - 1, None) == -3
-            N.check(lib.sd_hdb_outgoing_grouped_f32(*args, no, None), "sd_hdb_outgoing_grouped_f32")
+            assert CAP.call("sd_hdb_outgoing_grouped_f32", *args, no - 1) == -3
+            N.check(CAP.call("sd_hdb_outgoing_grouped_f32", *args, no), "sd_hdb_outgoing_grouped_f32")
             torch.cuda.synchronize()
             G.assert_guards_intact(gS, gg, gci, gcomp, gn, gb, gbad2, gwo)
             assert (int(gbad2.view(torch.int32)[0]) == 0) == good, (poison, mg)
@@ -345,7 +346,7 @@ def test_lib_refuses_on_the_device_too(dev):
                      dtype=torch.uint8, device=dev)
 
     def c(rows=S.data_ptr(), ld=192, n=64, d=192, k=2, max_group=64, ws_bytes=ws.numel()):
-        return lib.sd_hdb_core_grouped_f32(rows, ld, n, d, k, group.data_ptr(), max_group, core.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws_bytes, None)
+        return CAP.call("sd_hdb_core_grouped_f32", rows, ld, n, d, k, group.data_ptr(), max_group, core.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws_bytes)
 
     def o(rows=S.data_ptr(), ld=192, n=64, d=192, max_group=64, ws_bytes=ws.numel()):
         return lib.sd_hdb_outgoing_grouped_f32(rows, ld, n, d, core.data_ptr(), comp.data_ptr(), group.data_ptr(), max_group, nn.data_ptr(),

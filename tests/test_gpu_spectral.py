@@ -11,6 +11,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "helpers"))
+import captured as CAP  # noqa: E402
 import guarded as G  # noqa: E402
 import spectral_ref as R  # noqa: E402
 from launch_log import expect_launches  # noqa: E402
@@ -120,12 +121,11 @@ def test_lib_refuses_on_the_device_too(dev):
 
 def _edge_degree(dev, n, ld, zd, poison):
     from speech_diarization_amd import _native as N
-    lib = N.load()
     K = R.grid_affinity(n, ld, seed=n)
     flat = torch.from_numpy(K.reshape(-1)[: (n - 1) * ld + n].copy())
     gK = G.guarded_from(flat, dev, "K")                           # the last row ends at its last column: no padding behind it
     gd = G.guarded(n * 4, poison, dev, "deg")
-    N.check(lib.sd_affinity_degree_f32(gK.ptr, n, ld, int(zd), gd.ptr, None), "sd_affinity_degree_f32")
+    N.check(CAP.call("sd_affinity_degree_f32", gK.ptr, n, ld, int(zd), gd.ptr), "sd_affinity_degree_f32")
     torch.cuda.synchronize()
     G.assert_guards_intact(gK, gd)
     return gd.view(torch.float32).clone()
@@ -143,7 +143,7 @@ def _edge_apply(dev, n, ld, zd, b, ldv, ldy, poison):
     gY = G.guarded(((n - 1) * ldy + b) * 4, poison, dev, "Y")
     need = int(lib.sd_affinity_apply_workspace_bytes(n, b))
     gw = G.guarded(need, poison, dev, "ws")
-    N.check(lib.sd_affinity_apply_f32(gK.ptr, n, ld, int(zd), gs.ptr, gV.ptr, ldv, b, gY.ptr, ldy, gw.ptr, need, None), "sd_affinity_apply_f32")
+    N.check(CAP.call("sd_affinity_apply_f32", gK.ptr, n, ld, int(zd), gs.ptr, gV.ptr, ldv, b, gY.ptr, ldy, gw.ptr, need), "sd_affinity_apply_f32")
     torch.cuda.synchronize()
     G.assert_guards_intact(gK, gs, gV, gY, gw)
     y = gY.view(torch.float32)
